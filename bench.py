@@ -2,7 +2,7 @@
 """Headline benchmark: Gibbs draws/sec on synthetic 3-state Gaussian-HMM windows
 (BASELINE.json configs[1]: K=3, T=1000, 256 windows, 1000 draws per GPU).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 A "step" is one batched estimate call (hmcg_estimate_batch_device) over this rank's 256
 windows with inputs already resident in HBM: 0 burn-in + 1000 kept sweeps per window,
@@ -237,6 +237,24 @@ def alu_roofline(kernel_ms, key):
     return out
 
 
+def dump_outputs(dirpath, panel, gathered=None, limit_bytes=64 << 20):
+    """--dump-outputs: what the timed path's caller receives from its last step -- the per-draw outputs and the per-window
+    summary and status of this rank's panel (plus, for N > 1, the summary gathered to rank 0) -- as DIR/<name>.npy in float64.
+    The inputs are fixed (synthetic panel from fixed window ids, seed 1234), so two builds can be compared array by array."""
+    import numpy as np
+    arrays = {k: getattr(panel, k) for k in ("mu", "sig2", "A", "pi_end", "fcast", "summary", "status")}
+    if gathered is not None:
+        arrays["summary_gathered"] = gathered
+    arrays = {k: v.detach().cpu().numpy().astype(np.float64) for k, v in arrays.items() if v is not None}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > limit_bytes:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, limit_bytes))
+    os.makedirs(dirpath, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(dirpath, k + ".npy"), a)
+    return sorted(arrays)
+
+
 def spawn_ranks(args):
     """Parent of an N-GPU run: no torch.cuda, no HIP call here -- the ranks are fresh child processes."""
     with socket.socket() as s:
@@ -266,6 +284,8 @@ def main():
     ap.add_argument("--threads-per-window", type=int, default=0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra", action="store_true", help="skip the extra shapes (profiling runs of the headline kernel)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the outputs of the last timed step as DIR/<name>.npy (float64)")
     ap.add_argument("--rehearse-shared-gpu", action="store_true",
                     help="multi-rank plumbing rehearsal on a one-GPU box: every rank uses cuda:0 and the process group "
                          "is gloo (RCCL refuses two ranks on one device); never used for reported numbers")
@@ -303,10 +323,12 @@ def main():
     yreal = fut[:, HORIZON - 1:HORIZON]
     panel = hdev.DevicePanel(Y, Tw, K, DRAWS, (HORIZON,), yreal, device=local_rank)
 
+    gathered = [None]
+
     def step():
         ms = panel.run(burnin=0, seed=1234, window_base=ids[0], threads_per_window=args.threads_per_window, timed=True)
         if world > 1:
-            shard.gather_blocks(panel.summary, ids, W_total)
+            gathered[0] = shard.gather_blocks(panel.summary, ids, W_total)
         return ms
 
     def fence():
@@ -350,6 +372,9 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
     bad = int((panel.status != 0).sum().item())
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, panel, gathered[0])
 
     if rank == 0:
         value = W_total * DRAWS * args.steps / dt
@@ -370,6 +395,7 @@ def main():
             "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
             "dtype": "f64", "data": "synthetic",
             "rehearsal": bool(args.rehearse_shared_gpu),
+            "dumped_outputs": dumped,
             "config": {"workload": "configs[1]: 3-state Gaussian HMM, T=1000, 256 windows per GPU, 0 burn-in + 1000 "
                                    "draws per window per step, h=12 forecast per draw, on-device summary means",
                        "K": K, "T": T, "windows_per_gpu": W_PER_GPU, "draws_per_window": DRAWS,

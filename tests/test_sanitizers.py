@@ -5,6 +5,8 @@ on this pool, so this is the CPU side only):
     AddressSanitizer + UBSan and under ThreadSanitizer;
   * the oracle's C restatement under AddressSanitizer + UBSan (tests/sanitize/oracle_harness.c)."""
 import os
+import platform
+import shutil
 import subprocess
 
 import pytest
@@ -13,14 +15,23 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SAN = os.path.join(ROOT, "tests", "sanitize")
 
 
-def build_and_run(tmp_path, name, compiler, flags, sources, args=(), libs=()):
+def no_aslr_prefix():
+    """GCC's ThreadSanitizer runtime aborts at start-up ("unexpected memory mapping") on kernels with high mmap ASLR entropy:
+    run the instrumented binary with address randomisation off for that one process (setarch -R), where the host allows it."""
+    setarch = shutil.which("setarch")
+    if setarch and subprocess.run([setarch, platform.machine(), "-R", "true"], capture_output=True).returncode == 0:
+        return [setarch, platform.machine(), "-R"]
+    return []
+
+
+def build_and_run(tmp_path, name, compiler, flags, sources, args=(), libs=(), prefix=()):
     exe = str(tmp_path / name)
     cmd = [compiler, "-O1", "-g", "-fno-omit-frame-pointer"] + flags + ["-o", exe] + sources + list(libs)
     subprocess.check_call(cmd)
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1",
                TSAN_OPTIONS="halt_on_error=1")
     env.pop("LD_PRELOAD", None)
-    r = subprocess.run([exe] + list(args), capture_output=True, text=True, env=env, timeout=600)
+    r = subprocess.run(list(prefix) + [exe] + list(args), capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     assert "ok" in r.stdout and "ERROR" not in r.stderr and "WARNING: ThreadSanitizer" not in r.stderr, r.stderr[-3000:]
 
@@ -41,7 +52,7 @@ def test_host_code_under_tsan(tmp_path):
     out = tmp_path / "csv"
     out.mkdir()
     build_and_run(tmp_path, "host_tsan", "g++", ["-std=c++17", "-fsanitize=thread", "-I" + os.path.join(ROOT, "include")], HOST_SRC,
-                  [str(out)], ["-lpthread"])
+                  [str(out)], ["-lpthread"], prefix=no_aslr_prefix())
 
 
 @pytest.mark.timeout(900)
