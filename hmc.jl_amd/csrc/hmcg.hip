@@ -19,10 +19,8 @@
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
-#include <condition_variable>
 #include <functional>
 #include <mutex>
-#include <numeric>
 #include <string>
 #include <thread>
 #include <vector>
@@ -93,12 +91,6 @@ struct Arena {
     }
 };
 
-// offsets into an arena, 256-byte aligned; pointers are taken after ensure()
-struct Layout {
-    size_t total = 0;
-    size_t add(size_t bytes) { const size_t off = total; total += (bytes + 255) & ~(size_t)255; return off; }
-};
-
 constexpr int RING = 3;            // chunk buffers in flight (device and pinned)
 constexpr int MAXBUCKET = 8;       // length buckets of one call (steps-per-thread classes 1, 2, 3, 4, 6, 8, 16)
 
@@ -109,7 +101,7 @@ struct DeviceCtx {
     int phys = -1;                 // the HIP device behind it (== device unless HMCG_VIRTUAL_DEVICES is set)
     hipStream_t stream = nullptr, copy = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;          // kernel timing
-    hipEvent_t ev_scr = nullptr;                      // device entry: last use of the shared scratch (scr, mom) on any stream
+    hipEvent_t ev_scr = nullptr;                      // device entry: last use of the shared arenas (scr, mom, ord) on any stream
     hipEvent_t evk[RING] = {}, evc[RING] = {};        // chunk pipeline: kernel done / copy done
     hipStream_t bstream[MAXBUCKET - 1] = {};          // length-bucketed dispatch: the shorter buckets' launches run beside the longest
     hipEvent_t ev_fork = nullptr, ev_join[MAXBUCKET - 1] = {};
@@ -369,11 +361,10 @@ int make_plan(const hmcg_config* cfg, const hmcg_extras* ex, int W, int cu_count
     if (cfg->sweep_base > n_samples * (cfg->burnin + cfg->nrun)) { set_err("sweep_base beyond the run"); return HMCG_E_BADARG; }
     // Flavour: helper waves pay off while every window has a CU to itself; with more windows than CUs the capped
     // plain variant lets two windows share a CU instead (a helped block takes the whole register file).
-    // HMCG_FLAVOUR=p1|p2|h and HMCG_HELPERS=0|1 override the table (diagnostics, tools/variant_sweep.py).
+    // HMCG_FLAVOUR=p1|p2|h overrides the table (diagnostics, tools/variant_sweep.py).
     const bool small_batch = W <= cu_count;
-    int force = -1;
-    if (const char* henv = diag_env("HMCG_HELPERS")) force = atoi(henv) != 0 ? H : (small_batch ? P1 : P2);
-    if (const char* fenv = diag_env("HMCG_FLAVOUR")) force = flavour_code(fenv);
+    const char* fenv = diag_env("HMCG_FLAVOUR");
+    const int force = fenv ? flavour_code(fenv) : -1;
     Plan pl;
     pl.use_sig = use_sig; pl.use_smooth = use_smooth;
     // HMCG_FORCE_BIG=1 (diagnostics): the LDS-resident kernel also where a register-resident variant exists
@@ -423,10 +414,9 @@ int make_plan(const hmcg_config* cfg, const hmcg_extras* ex, int W, int cu_count
     }
 #endif
     if (!pl.v) {                                       // large K, or a window too long for the register-resident variants
-        const BigVariant* tab = use_sig ? (use_smooth ? g_big_sigsmooth_variants : g_big_sig_variants) : (use_smooth ? g_big_smooth_variants : g_big_variants);
-        const int ntab = use_sig ? (use_smooth ? g_n_big_sigsmooth_variants : g_n_big_sig_variants) : (use_smooth ? g_n_big_smooth_variants : g_n_big_variants);
-        for (int i = 0; i < ntab; ++i) if (tab[i].K == cfg->K) pl.bv = &tab[i];
-        if (pl.bv) {
+        auto big = [&](bool stream) { return &(*g_big[use_sig][use_smooth][stream])[cfg->K - BIG_KMIN]; };
+        if (cfg->K >= BIG_KMIN && cfg->K < BIG_KMIN + BIG_NK) {
+            pl.bv = big(false);
             pl.bigL = (maxT + pl.bv->NT - 1) / pl.bv->NT;
             pl.dyn = (size_t)pl.bv->NT * pl.bigL * (8 + 8 + 4 + 1) + 16;
             // dynamic + static LDS of the instantiation must fit the CU's 160 KiB
@@ -434,13 +424,8 @@ int make_plan(const hmcg_config* cfg, const hmcg_extras* ex, int W, int cu_count
             if (cfg->threads_per_window != 0 && cfg->threads_per_window != pl.bv->NT) pl.bv = nullptr;
             else if (pl.dyn + stat > 160 * 1024 || diag_env("HMCG_FORCE_STREAM")) {
                 // too long for the LDS: the same kernel with its per-step arrays in an HBM scratch (HMCG_FORCE_STREAM: tests)
-                pl.bv = nullptr;
-                const BigVariant* stab = use_sig ? (use_smooth ? g_big_sigsmooth_stream_variants : g_big_sig_stream_variants)
-                                                 : (use_smooth ? g_big_smooth_stream_variants : g_big_stream_variants);
-                const int nstab = use_sig ? (use_smooth ? g_n_big_sigsmooth_stream_variants : g_n_big_sig_stream_variants)
-                                          : (use_smooth ? g_n_big_smooth_stream_variants : g_n_big_stream_variants);
-                for (int i = 0; i < nstab; ++i) if (stab[i].K == cfg->K) pl.bv = &stab[i];
-                pl.stream = pl.bv != nullptr;
+                pl.bv = big(true);
+                pl.stream = true;
                 pl.dyn = 16;
             }
         }
@@ -628,6 +613,17 @@ int print_stamps(const hmcg::KernelParams& p, const Plan& pl, unsigned long long
 #endif
 
 // ---- device-resident entry: one launch over caller-owned HBM buffers -----------------------------------------
+
+// Grows one of the device entry's context-owned arenas (scr, mom, ord).  An enqueue-only call on any stream may still be
+// using the old buffer: growing waits for its last use (ev_scr) before the old one is freed.
+int grow_shared(DeviceCtx& c, Arena& a, size_t bytes)
+{
+    if (a.cap >= bytes) return 0;
+    HIP_TRY(hipEventSynchronize(c.ev_scr));
+    if (a.ensure(bytes)) { set_err("workspace allocation failed (%zu B device)", bytes); return HMCG_E_NOMEM; }
+    return 0;
+}
+
 int launch_device(DeviceCtx& c, const hmcg_config* cfg, const double* dY, const int32_t* dT, const double* dyreal, double* dmu,
                   double* dsig2, double* dA, double* dpi_end, double* dfcast, double* dsummary, int32_t* dstatus,
                   const hmcg_extras* ex, hipStream_t stream, hmcg_timing* timing)
@@ -664,16 +660,14 @@ int launch_device(DeviceCtx& c, const hmcg_config* cfg, const double* dY, const 
     if (uses_scratch) HIP_TRY(hipStreamWaitEvent(stream, c.ev_scr, 0));
     int32_t* ord = nullptr;
     if (use_lists) {
-        if (c.ord.cap < bucket_list_bytes(cfg->W)) HIP_TRY(hipStreamSynchronize(stream));        // growing it frees the old one
-        if (c.ord.ensure(bucket_list_bytes(cfg->W))) { set_err("workspace allocation failed (%zu B device)", bucket_list_bytes(cfg->W)); return HMCG_E_NOMEM; }
+        if ((rc = grow_shared(c, c.ord, bucket_list_bytes(cfg->W)))) return rc;
         ord = reinterpret_cast<int32_t*>(c.ord.base);
     }
     if (pl.bv) {
         HIP_TRY(hipFuncSetAttribute(pl.fptr(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.dyn));
         const size_t fbytes = (pl.scratch_bytes(cfg->W, cfg->K) + 255) & ~(size_t)255;
         const size_t sbytes = fbytes + pl.stream_bytes(cfg->W);
-        if (c.scr.cap < sbytes) HIP_TRY(hipStreamSynchronize(stream));        // growing the scratch frees the old one
-        if (c.scr.ensure(sbytes)) { set_err("workspace allocation failed (%zu B device)", sbytes); return HMCG_E_NOMEM; }
+        if ((rc = grow_shared(c, c.scr, sbytes))) return rc;
         p.fscr = reinterpret_cast<double*>(c.scr.base);
         if (pl.stream) { p.sscr = reinterpret_cast<uint8_t*>(c.scr.base + fbytes); p.stream_stride = (int64_t)pl.slab_bytes(); }
     }
@@ -691,8 +685,7 @@ int launch_device(DeviceCtx& c, const hmcg_config* cfg, const double* dY, const 
     if (ex && ex->corr) {
         // correlations of the rounded draws (calccorr): one pass over the draw arrays while they are in HBM
         const size_t mbytes = sizeof(double) * (size_t)cfg->W * hmcg_host::moments_stride(cfg->K);
-        if (c.mom.cap < mbytes) HIP_TRY(hipStreamSynchronize(stream));        // growing the table frees the old one
-        if (c.mom.ensure(mbytes)) { set_err("workspace allocation failed (%zu B device)", mbytes); return HMCG_E_NOMEM; }
+        if ((rc = grow_shared(c, c.mom, mbytes))) return rc;
         hmcg_host::MomentsArgs ma{dmu, dsig2, dpi_end, dA, dfcast, reinterpret_cast<double*>(c.mom.base), cfg->nrun, cfg->nrun, cfg->W, cfg->K, cfg->H, true};
         HIP_TRY(hmcg_host::launch_moments(ma, stream));
         HIP_TRY(hmcg_host::launch_corr_finalize(reinterpret_cast<double*>(c.mom.base), ex->corr, cfg->W, cfg->K, stream));
@@ -715,250 +708,180 @@ int launch_device(DeviceCtx& c, const hmcg_config* cfg, const double* dY, const 
 
 // ---- host entry on one device --------------------------------------------------------------------------------
 
-struct HostArrays {
-    const double* Y; const int32_t* T; const double* yreal;
-    double* mu; double* sig2; double* A; double* pi_end; double* fcast; double* summary; int32_t* status;
-    const hmcg_extras* ex;
-};
-
-// Runs the n windows idx[0..n) (rows of the caller's arrays; idx == nullptr: rows 0..n-1) on device context c.
+// One host-entry call on one device, step by step: plan() picks the kernel and cuts the chain into chunks, lay_out() places
+// every buffer in the two arenas, stage_inputs() packs and sends what the kernels read, run_chunks() runs the chain and
+// scatters each chunk's draws into the caller's arrays, collect_outputs() hands back the rest.  The per-window arrays are
+// rows of one table (host_util.hpp, host_buffers); the per-draw chunk columns are laid out here.
 // Caller holds c.mu and has made c.device current.
-int run_host_on_device(DeviceCtx& c, const hmcg_config* cfg, const int32_t* idx, int n, const HostArrays& h, hmcg_timing* timing)
-{
-    const auto t_call = std::chrono::steady_clock::now();
-    // HMCG_TRACE=1 (diagnostics): host-side timeline of the call on stderr -- where the wall time beyond the kernels goes
-    static const bool trace_on = diag_env("HMCG_TRACE") != nullptr;
+struct HostCall {
+    DeviceCtx& c;
+    const hmcg_config* cfg;
+    const int32_t* idx;            // the call's windows: rows idx[0..n) of the caller's arrays (nullptr: rows 0..n-1)
+    int n;
+    const HostArrays& h;
+    hmcg_timing* timing;
+    std::chrono::steady_clock::time_point t_call = std::chrono::steady_clock::now();
     std::vector<std::pair<const char*, double>> trace;
-    auto mark = [&](const char* what) {
-        if (trace_on) trace.emplace_back(what, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count());
-    };
-    // HMCG_FAIL_DEVICE=id (diagnostics): the host entry fails on that device id before it touches anything -- lets a test
-    // see hmcg_estimate_batch_multi report one worker's error while the others complete
-    if (const char* fe = diag_env("HMCG_FAIL_DEVICE")) {
-        if (atoi(fe) == c.device) { set_err("injected failure (HMCG_FAIL_DEVICE=%d)", c.device); return HMCG_E_NOMEM; }
-    }
-    Plan pl;
-    int minT = 0;                                                  // the shortest valid window of this device's share
-    if (h.T) {
-        for (int i = 0; i < n; ++i) {
-            const int t = h.T[idx ? (size_t)idx[i] : (size_t)i];
-            if (t >= 2 && (minT == 0 || t < minT)) minT = t;
-        }
-    }
-    const HostLengths hl{h.T, idx, n};
-    int rc = make_plan(cfg, h.ex, n, c.cu_count, minT, h.T ? &hl : nullptr, &pl);
-    if (rc) return rc;
-    if (!h.Y || !h.T) { set_err("Y and T are required"); return HMCG_E_BADARG; }
-    const hmcg_extras* ex = h.ex;
-    const size_t K = (size_t)cfg->K, ld = (size_t)cfg->ldY, H = (size_t)cfg->H, N = (size_t)n;
-    const int n_samples = cfg->n_samples > 1 ? cfg->n_samples : 1;
-    const long long nd_total = (long long)n_samples * cfg->nrun;       // kept draws per window over the whole run
-    const size_t NS = 3 * K + K * K + 2 * H;
-    const bool resume_in = (cfg->flags & HMCG_FLAG_RESUME) != 0;
-    constexpr int32_t ST_SKIPPED = HMCG_ST_NONFINITE | HMCG_ST_BAD_T | HMCG_ST_BAD_RANGE;
-    auto row = [&](int i) -> size_t { return idx ? (size_t)idx[i] : (size_t)i; };
 
+    Plan pl;
     // per-draw output columns of one window, in the order they sit in a chunk buffer
     struct Col { double* host; size_t ncol; size_t off; };
-    // (the sixth group, extras.pi_smooth_draws, is K * ldY columns wide: samples.pib[Nrun, N, D] of every window)
-    Col cols[6] = { {h.mu, K, 0}, {h.sig2, K, 0}, {h.A, K * K, 0}, {h.pi_end, K, 0}, {h.fcast, 2 * H, 0},
-                    {ex ? ex->pi_smooth_draws : nullptr, K * ld, 0} };
+    Col cols[6] = {};
     size_t ncols = 0;
-    const bool want_corr = ex && ex->corr;          // needs every draw column on the device, wanted by the caller or not
-    bool copy_out = false;
-    for (Col& cc : cols) {
-        if (!(cc.host || (want_corr && &cc != &cols[5])) || nd_total == 0) cc.ncol = 0;
-        if (cc.host && cc.ncol) copy_out = true;
-        cc.off = ncols; ncols += cc.ncol;
-    }
-    const bool stream_draws = ncols > 0;
-    const size_t NCC = (size_t)hmcg_host::corr_columns(cfg->K), mom_stride = hmcg_host::moments_stride(cfg->K);
+    bool stream_draws = false, copy_out = false, want_corr = false;
+    long long nd_total = 0;        // kept draws per window over the whole run
+    int total_sweeps = 0, se = 0;
+    std::vector<Chunk> chunks;
 
-    const int total_sweeps = n_samples * (cfg->burnin + cfg->nrun);
-    int sb = cfg->sweep_base, se = total_sweeps;
-    if (cfg->sweep_count > 0 && sb + cfg->sweep_count < se) se = sb + cfg->sweep_count;
-    const int per = std::max(1, cfg->burnin + cfg->nrun);
-    // chunk capacity: the ring of RING chunk buffers stays within ~1 GiB of device memory (and as much pinned memory)
-    long long cap = nd_total > 0 ? nd_total : 1;
-    if (stream_draws) {
-        const long long budget = (1LL << 30) / RING / (long long)(8 * ncols * N);
-        cap = std::max(1LL, std::min(cap, budget));
-    }
-    if (const char* cenv = diag_env("HMCG_CHUNK_DRAWS")) { const long long v = atoll(cenv); if (v > 0) cap = std::min(cap, v); }
-    const bool one_chunk_env = diag_env("HMCG_NO_CHUNKS") != nullptr;           // diagnostics: one launch, as the device entry
-    std::vector<Chunk> chunks = plan_chunks(sb, se, per, cfg->burnin, cfg->nrun, one_chunk_env ? (1LL << 40) : cap, stream_draws && !one_chunk_env,
-                                            diag_env("HMCG_CHUNK_FLOOR_DIV"), diag_env("HMCG_CHUNK_KEEP"));
-    long long chunk_max = 0;
-    for (const Chunk& ch : chunks) chunk_max = std::max(chunk_max, ch.d1 - ch.d0);
-    const bool chunked = chunks.size() > 1;
-
-    // ---- layouts ----
-    // Both arenas open with the same INPUT block (Y, T, ids, yreal, the optional per-window inputs: same order, same sizes), so
-    // one H2D carries it; the device arena follows with the blocks a fresh (non-resumed) call needs zeroed, contiguous, so one
-    // memset clears them; status and summary sit next to each other on both sides, so one D2H brings them back.  (Every
-    // separate copy or memset is a node on the stream ahead of the first kernel: ten of them cost more than the 2 MB of Y.)
-    Layout LD, LP;
-    const bool need_ckpt = chunked || resume_in || (ex && (ex->xstate || ex->sumacc)) || se < total_sweeps;
-    const bool want_xi = ex && ex->x_init, want_xf = ex && ex->x_final;
-    const bool user_pif = ex && ex->pif_final, want_pif = user_pif || pl.needs_pif();     // scratch of the smoothing kernel
-    const bool want_sm = ex && ex->pi_smooth_mean, want_fm = ex && ex->pi_filter_mean;
-    const bool want_sv = ex && ex->sigvals && ex->nsave_ld > 0;
-    const size_t nsv = want_sv ? (size_t)n_samples * (size_t)ex->nsave_ld : 0;
-    const bool want_ss = ex && ex->sample_summary;
-    const size_t nss = want_ss ? (size_t)n_samples * NS : 0;
-    const bool has_yr = h.yreal && H, has_sr = ex && ex->sig_range, has_svr = ex && ex->save_range, has_ep = ex && ex->end_pos,
-               has_ssg = ex && ex->sigma_signal;
-    size_t o_dY, o_dT, o_dwid, o_dyr = 0, o_dxi = 0, o_dsr = 0, o_dsvr = 0, o_dep = 0, o_dss = 0;
-    size_t o_pY, o_pT, o_pwid, o_pyr = 0, o_pxi = 0, o_psr = 0, o_psvr = 0, o_pep = 0, o_pss = 0;
-    auto both = [&](size_t bytes, size_t& od, size_t& op) { od = LD.add(bytes); op = LP.add(bytes); };
-    both(8 * N * ld, o_dY, o_pY); both(4 * N, o_dT, o_pT); both(4 * N, o_dwid, o_pwid);
-    if (has_yr) both(8 * N * H, o_dyr, o_pyr);
-    if (want_xi) both(4 * N * ld, o_dxi, o_pxi);
-    if (has_sr) both(8 * N, o_dsr, o_psr);
-    if (has_svr) both(8 * N, o_dsvr, o_psvr);
-    if (has_ep) both(4 * N, o_dep, o_pep);
-    if (has_ssg) both(8 * N, o_dss, o_pss);
-    const size_t input_bytes = LD.total;                       // == LP.total: the block [0, input_bytes) of either arena
-    // device: the zeroed block
-    const size_t zero_begin = LD.total;
-    const size_t o_dst = LD.add(4 * N);
-    const size_t o_dsum = h.summary ? LD.add(8 * N * NS) : 0;
-    const size_t o_dxs = need_ckpt ? LD.add(N * ld) : 0, o_dacc = need_ckpt ? LD.add(8 * N * (NS + K)) : 0;
-    const size_t o_dxf = want_xf ? LD.add(4 * N * ld) : 0;
-    const size_t o_dsv = want_sv ? LD.add(8 * N * nsv) : 0;
-    const size_t o_dss2 = want_ss ? LD.add(8 * N * nss) : 0;
-    const size_t o_dpif = want_pif ? LD.add(8 * N * ld * K) : 0;
-    const size_t o_dsm = want_sm ? LD.add(8 * N * ld * K) : 0, o_dfm = want_fm ? LD.add(8 * N * ld * K) : 0;
-    const size_t zero_bytes = LD.total - zero_begin;
-    const size_t chunk_bytes = 8 * ncols * N * (size_t)chunk_max;
-    size_t o_dchunk[RING] = {}, o_pchunk[RING] = {};
-    const int nring = stream_draws ? (int)std::min<size_t>(RING, chunks.size()) : 0;
-    for (int r = 0; r < nring; ++r) o_dchunk[r] = LD.add(chunk_bytes);
-    const size_t o_dmom = want_corr ? LD.add(8 * N * mom_stride) : 0, o_dcorr = want_corr ? LD.add(8 * N * NCC * NCC) : 0;
-    const bool use_lists = pl.nb > 1;
-    const size_t o_dord = use_lists ? LD.add(bucket_list_bytes((int)N)) : 0;
-    const size_t o_dfs = pl.bv ? LD.add(pl.scratch_bytes(n, cfg->K)) : 0;
-    const size_t o_dstr = pl.stream ? LD.add(pl.stream_bytes(n)) : 0;
-    // pinned staging beyond the input block: small outputs (status | summary adjacent, as on the device), chunk ring, extras
-    const size_t o_pst = LP.add(4 * N);
-    const size_t o_psum = h.summary ? LP.add(8 * N * NS) : 0;
-    const size_t o_pst0 = LP.add(4 * N);      // status words as they stand after the first launch: which windows were skipped
-    for (int r = 0; r < nring; ++r) o_pchunk[r] = LP.add(chunk_bytes);
-    const size_t o_pxs = need_ckpt ? LP.add(N * ld) : 0, o_pacc = need_ckpt ? LP.add(8 * N * (NS + K)) : 0;
-    const size_t o_pxf = want_xf ? LP.add(4 * N * ld) : 0;
-    const size_t o_ppif = user_pif ? LP.add(8 * N * ld * K) : 0;
-    const size_t o_psm = want_sm ? LP.add(8 * N * ld * K) : 0, o_pfm = want_fm ? LP.add(8 * N * ld * K) : 0;
-    const size_t o_psv = want_sv ? LP.add(8 * N * nsv) : 0;
-    const size_t o_pss2 = want_ss ? LP.add(8 * N * nss) : 0;
-    const size_t o_pcorr = want_corr ? LP.add(8 * N * NCC * NCC) : 0;
-    if (c.dev.ensure(LD.total) || c.pin.ensure(LP.total)) {
-        set_err("workspace allocation failed (%zu B device, %zu B pinned)", LD.total, LP.total);
-        return HMCG_E_NOMEM;
-    }
-    char* D = c.dev.base;
-    char* P = c.pin.base;
-    hipStream_t s = c.stream;
-#define DP(T_, off) reinterpret_cast<T_*>(D + (off))
-#define PP(T_, off) reinterpret_cast<T_*>(P + (off))
-
-    // ---- pack the inputs (rows idx[i] of the caller's arrays) into pinned staging, one H2D each ----
-    // (Y is the bulk, 2 MB at the headline shape: its first half sets out while the second half is packed)
-#define H2D(doff, poff, bytes) HIP_TRY(hipMemcpyAsync(D + (doff), P + (poff), (bytes), hipMemcpyHostToDevice, s))
-    const int n_early = ((size_t)8 * ld * n >= ((size_t)1 << 20) && o_pY == 0 && o_dY == 0 && !diag_env("HMCG_NO_EARLY_H2D")) ? n / 2 : 0;
-    for (int i = 0; i < n; ++i) {
-        const size_t g = row(i);
-        if (i == n_early && n_early > 0) { mark("half packed"); H2D(0, 0, (size_t)8 * ld * n_early); mark("first half sent"); }
-        memcpy(PP(double, o_pY) + (size_t)i * ld, h.Y + g * ld, 8 * ld);
-        PP(int32_t, o_pT)[i] = h.T[g];
-        PP(uint32_t, o_pwid)[i] = (ex && ex->window_ids) ? ex->window_ids[g] : cfg->window_base + (uint32_t)g;
-        if (h.yreal && H) memcpy(PP(double, o_pyr) + (size_t)i * H, h.yreal + g * H, 8 * H);
-        // (a RESUME call carries the caller's status words on; whether a window is skipped is for THIS call's kernel to say)
-        if (resume_in) PP(int32_t, o_pst)[i] = h.status ? (h.status[g] & ~ST_SKIPPED) : 0;
-        if (want_xi) memcpy(PP(int32_t, o_pxi) + (size_t)i * ld, ex->x_init + g * ld, 4 * ld);
-        if (ex && ex->sig_range) { PP(int32_t, o_psr)[2 * i] = ex->sig_range[2 * g]; PP(int32_t, o_psr)[2 * i + 1] = ex->sig_range[2 * g + 1]; }
-        if (ex && ex->save_range) { PP(int32_t, o_psvr)[2 * i] = ex->save_range[2 * g]; PP(int32_t, o_psvr)[2 * i + 1] = ex->save_range[2 * g + 1]; }
-        if (ex && ex->end_pos) PP(int32_t, o_pep)[i] = ex->end_pos[g];
-        if (ex && ex->sigma_signal) PP(double, o_pss)[i] = ex->sigma_signal[g];
-        if (resume_in) {
-            memcpy(PP(uint8_t, o_pxs) + (size_t)i * ld, ex->xstate + g * ld, ld);
-            if (ex->sumacc) memcpy(PP(double, o_pacc) + (size_t)i * (NS + K), ex->sumacc + g * (NS + K), 8 * (NS + K));
-            if (want_sm) memcpy(PP(double, o_psm) + (size_t)i * ld * K, ex->pi_smooth_mean + g * ld * K, 8 * ld * K);
-            if (want_fm) memcpy(PP(double, o_pfm) + (size_t)i * ld * K, ex->pi_filter_mean + g * ld * K, 8 * ld * K);
-            if (want_ss) memcpy(PP(double, o_pss2) + (size_t)i * nss, ex->sample_summary + g * nss, 8 * nss);
-        }
-    }
-    mark("packed");
-    {
-        const size_t sent = (size_t)8 * ld * n_early;          // Y, T, ids, yreal and the optional per-window inputs
-        H2D(sent, sent, input_bytes - sent);
-    }
-    if (resume_in) {
-        H2D(o_dst, o_pst, 4 * N);
-        H2D(o_dxs, o_pxs, N * ld);
-        if (ex->sumacc) H2D(o_dacc, o_pacc, 8 * N * (NS + K)); else HIP_TRY(hipMemsetAsync(D + o_dacc, 0, 8 * N * (NS + K), s));
-        if (want_sm) H2D(o_dsm, o_psm, 8 * N * ld * K);
-        if (want_fm) H2D(o_dfm, o_pfm, 8 * N * ld * K);
-        if (want_ss) H2D(o_dss2, o_pss2, 8 * N * nss);
-        // outputs a skipped window never writes read as zero
-        if (h.summary) HIP_TRY(hipMemsetAsync(D + o_dsum, 0, 8 * N * NS, s));
-        if (want_xf) HIP_TRY(hipMemsetAsync(D + o_dxf, 0, 4 * N * ld, s));
-        if (want_pif) HIP_TRY(hipMemsetAsync(D + o_dpif, 0, 8 * N * ld * K, s));
-        if (want_sv) HIP_TRY(hipMemsetAsync(D + o_dsv, 0, 8 * N * nsv, s));
-    } else {
-        // status, summary, the checkpoint blocks (they live in the recycled arena: a skipped window writes none of them and
-        // must not hand the caller an earlier call's bytes), x_final, sigvals, the per-sample summaries, pif, the running
-        // smoothed / filtered sums: one memset
-        HIP_TRY(hipMemsetAsync(D + zero_begin, 0, zero_bytes, s));
-    }
-#undef H2D
-    hmcg_extras dex{};
-    dex.struct_size = (int32_t)sizeof(hmcg_extras);
-    dex.window_ids = DP(uint32_t, o_dwid);
-    if (want_xi) dex.x_init = DP(int32_t, o_dxi);
-    if (want_xf) dex.x_final = DP(int32_t, o_dxf);
-    if (want_pif) dex.pif_final = DP(double, o_dpif);
-    if (need_ckpt) { dex.xstate = DP(uint8_t, o_dxs); dex.sumacc = DP(double, o_dacc); }
-    if (want_sm) dex.pi_smooth_mean = DP(double, o_dsm);
-    if (want_fm) dex.pi_filter_mean = DP(double, o_dfm);
-    if (ex && ex->sig_range) dex.sig_range = DP(int32_t, o_dsr);
-    if (ex && ex->save_range) dex.save_range = DP(int32_t, o_dsvr);
-    if (ex && ex->end_pos) dex.end_pos = DP(int32_t, o_dep);
-    if (ex && ex->sigma_signal) dex.sigma_signal = DP(double, o_dss);
-    if (want_sv) { dex.sigvals = DP(double, o_dsv); dex.nsave_ld = ex->nsave_ld; }
-    if (want_ss) dex.sample_summary = DP(double, o_dss2);
-
-    hmcg::KernelParams base = base_params(cfg, n, DP(double, o_dY), DP(int32_t, o_dT), (h.yreal && H) ? DP(double, o_dyr) : nullptr,
-                                          DP(int32_t, o_dst), &dex, pl.use_sig);
-    base.summary = h.summary ? DP(double, o_dsum) : nullptr;
-    if (pl.bv) base.fscr = DP(double, o_dfs);
-    if (pl.stream) { base.sscr = DP(uint8_t, o_dstr); base.stream_stride = (int64_t)pl.slab_bytes(); }
-    if (pl.bv) HIP_TRY(hipFuncSetAttribute(pl.fptr(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.dyn));
-
-    // ---- the chunk pipeline ----
-    // kernel c -> evk[c % RING] -> SDMA copy of its chunk buffer into pinned staging (copy stream) -> evc[c % RING]
-    // -> host scatter into the caller's arrays.  A chunk buffer is [array][window][column][draw] with the chunk's own
-    // draw count as leading dimension (one contiguous block: a plain 1-D copy, which the SDMA engines carry without
-    // touching the CUs -- a helped sweep kernel leaves no registers for a blit kernel to run beside it).  Kernel
-    // c + RING reuses both the device and the pinned buffer of chunk c: the host enqueues it only after it has waited
-    // for copy c and scattered chunk c.
-    if (use_lists) { rc = build_bucket_lists(pl, DP(int32_t, o_dT), n, DP(int32_t, o_dord), s); if (rc) return rc; }
-    mark("inputs enqueued");
-    const int nch = (int)chunks.size();
-    double kernel_ms = 0.0;
+    BufTable bt{};
+    char* D = nullptr;
+    char* P = nullptr;
+    size_t o_dchunk[RING] = {}, o_pchunk[RING] = {}, o_pst0 = 0;
+    int32_t* dord = nullptr;       // the bucketed dispatch's window lists
+    double *dmom = nullptr, *dcorr = nullptr;
+    hmcg::KernelParams base{};
     // per-chunk timing events, two per chunk: around the sweep kernel(s) alone -- the copy-out of the last chunk rides the
     // same stream behind its kernel and is not kernel time.  (Created only when timing is requested; released on every path.)
     struct TimingEvents {
         std::vector<hipEvent_t> ev;
         ~TimingEvents() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
     } tev;
-    if (timing) {
-        tev.ev.assign(2 * (size_t)nch, nullptr);
-        for (auto& e : tev.ev) HIP_TRY(hipEventCreate(&e));
+
+    size_t row(int i) const { return idx ? (size_t)idx[i] : (size_t)i; }
+    // HMCG_TRACE=1 (diagnostics): host-side timeline of the call on stderr -- where the wall time beyond the kernels goes
+    static bool trace_on() { static const bool on = diag_env("HMCG_TRACE") != nullptr; return on; }
+    double ms_so_far() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count(); }
+    void mark(const char* what) { if (trace_on()) trace.emplace_back(what, ms_so_far()); }
+
+    int plan()
+    {
+        // HMCG_FAIL_DEVICE=id (diagnostics): the host entry fails on that device id before it touches anything -- lets a test
+        // see hmcg_estimate_batch_multi report one worker's error while the others complete
+        if (const char* fe = diag_env("HMCG_FAIL_DEVICE")) {
+            if (atoi(fe) == c.device) { set_err("injected failure (HMCG_FAIL_DEVICE=%d)", c.device); return HMCG_E_NOMEM; }
+        }
+        int minT = 0;                                                  // the shortest valid window of this device's share
+        for (int i = 0; h.T && i < n; ++i) {
+            const int t = h.T[row(i)];
+            if (t >= 2 && (minT == 0 || t < minT)) minT = t;
+        }
+        const HostLengths hl{h.T, idx, n};
+        int rc = make_plan(cfg, h.ex, n, c.cu_count, minT, h.T ? &hl : nullptr, &pl);
+        if (rc) return rc;
+        if (!h.Y || !h.T) { set_err("Y and T are required"); return HMCG_E_BADARG; }
+        const hmcg_extras* ex = h.ex;
+        const size_t K = (size_t)cfg->K, ld = (size_t)cfg->ldY, H = (size_t)cfg->H, N = (size_t)n;
+        const int n_samples = cfg->n_samples > 1 ? cfg->n_samples : 1;
+        nd_total = (long long)n_samples * cfg->nrun;
+        // (the sixth group, extras.pi_smooth_draws, is K * ldY columns wide: samples.pib[Nrun, N, D] of every window)
+        const Col all[6] = { {h.mu, K, 0}, {h.sig2, K, 0}, {h.A, K * K, 0}, {h.pi_end, K, 0}, {h.fcast, 2 * H, 0},
+                             {ex ? ex->pi_smooth_draws : nullptr, K * ld, 0} };
+        want_corr = ex && ex->corr;                 // needs every draw column on the device, wanted by the caller or not
+        for (int g = 0; g < 6; ++g) {
+            Col& cc = cols[g] = all[g];
+            if (!(cc.host || (want_corr && g != 5)) || nd_total == 0) cc.ncol = 0;
+            if (cc.host && cc.ncol) copy_out = true;
+            cc.off = ncols; ncols += cc.ncol;
+        }
+        stream_draws = ncols > 0;
+
+        total_sweeps = n_samples * (cfg->burnin + cfg->nrun);
+        const int sb = cfg->sweep_base;
+        se = total_sweeps;
+        if (cfg->sweep_count > 0 && sb + cfg->sweep_count < se) se = sb + cfg->sweep_count;
+        const int per = std::max(1, cfg->burnin + cfg->nrun);
+        // chunk capacity: the ring of RING chunk buffers stays within ~1 GiB of device memory (and as much pinned memory)
+        long long cap = nd_total > 0 ? nd_total : 1;
+        if (stream_draws) {
+            const long long budget = (1LL << 30) / RING / (long long)(8 * ncols * N);
+            cap = std::max(1LL, std::min(cap, budget));
+        }
+        if (const char* cenv = diag_env("HMCG_CHUNK_DRAWS")) { const long long v = atoll(cenv); if (v > 0) cap = std::min(cap, v); }
+        const bool one_chunk_env = diag_env("HMCG_NO_CHUNKS") != nullptr;           // diagnostics: one launch, as the device entry
+        chunks = plan_chunks(sb, se, per, cfg->burnin, cfg->nrun, one_chunk_env ? (1LL << 40) : cap, stream_draws && !one_chunk_env,
+                             diag_env("HMCG_CHUNK_FLOOR_DIV"), diag_env("HMCG_CHUNK_KEEP"));
+        return 0;
     }
-    auto scatter = [&](int cidx) {
+
+    // The table's rows first (the input block, the zeroed block, the other per-window arrays -- host_buffers), then the chunk
+    // ring and the scratch of this plan.  (Every separate copy or memset is a node on the stream ahead of the first kernel:
+    // ten of them cost more than the 2 MB of Y.)
+    int lay_out()
+    {
+        const hmcg_extras* ex = h.ex;
+        const bool need_ckpt = chunks.size() > 1 || (cfg->flags & HMCG_FLAG_RESUME) || (ex && (ex->xstate || ex->sumacc)) || se < total_sweeps;
+        bt = host_buffers(*cfg, h, n, need_ckpt, pl.needs_pif(), hmcg_host::moments_stride(cfg->K));
+        long long chunk_max = 0;
+        for (const Chunk& ch : chunks) chunk_max = std::max(chunk_max, ch.d1 - ch.d0);
+        const size_t chunk_bytes = 8 * ncols * (size_t)n * (size_t)chunk_max;
+        const int nring = stream_draws ? (int)std::min<size_t>(RING, chunks.size()) : 0;
+        for (int r = 0; r < nring; ++r) o_dchunk[r] = bt.dev.add(chunk_bytes);
+        const size_t o_dord = pl.nb > 1 ? bt.dev.add(bucket_list_bytes(n)) : 0;
+        const size_t o_dfs = pl.bv ? bt.dev.add(pl.scratch_bytes(n, cfg->K)) : 0;
+        const size_t o_dstr = pl.stream ? bt.dev.add(pl.stream_bytes(n)) : 0;
+        o_pst0 = bt.pin.add(4 * (size_t)n);      // status words as they stand after the first launch: which windows were skipped
+        for (int r = 0; r < nring; ++r) o_pchunk[r] = bt.pin.add(chunk_bytes);
+        if (c.dev.ensure(bt.dev.total) || c.pin.ensure(bt.pin.total)) {
+            set_err("workspace allocation failed (%zu B device, %zu B pinned)", bt.dev.total, bt.pin.total);
+            return HMCG_E_NOMEM;
+        }
+        D = c.dev.base;
+        P = c.pin.base;
+        DevSlots ds = device_slots(bt, D);
+        if (ds.ex.sigvals) ds.ex.nsave_ld = ex->nsave_ld;
+        base = base_params(cfg, n, ds.Y, ds.T, ds.yreal, ds.status, &ds.ex, pl.use_sig);
+        base.summary = ds.summary;
+        if (pl.bv) base.fscr = reinterpret_cast<double*>(D + o_dfs);
+        if (pl.stream) { base.sscr = reinterpret_cast<uint8_t*>(D + o_dstr); base.stream_stride = (int64_t)pl.slab_bytes(); }
+        if (pl.nb > 1) dord = reinterpret_cast<int32_t*>(D + o_dord);
+        dmom = ds.mom;
+        dcorr = ds.ex.corr;
+        return 0;
+    }
+
+    // Pack the rows idx[i] of the caller's arrays into pinned staging, send the input block (the first half of Y sets out
+    // while the second half is packed: 2 MB at the headline shape), then either the RESUME state or one memset.
+    int stage_inputs()
+    {
+        hipStream_t s = c.stream;
+        const size_t N = (size_t)n, ybytes = bt.row[B_Y].bytes;       // Y at offset 0 of both arenas
+        const int n_early = ybytes * N >= ((size_t)1 << 20) ? n / 2 : 0;
+        const size_t sent = ybytes * n_early;
+        pack_rows(bt, P, idx, 0, n_early);
+        if (n_early > 0) { mark("half packed"); HIP_TRY(hipMemcpyAsync(D, P, sent, hipMemcpyHostToDevice, s)); mark("first half sent"); }
+        pack_rows(bt, P, idx, n_early, n);
+        mark("packed");
+        HIP_TRY(hipMemcpyAsync(D + sent, P + sent, bt.input_bytes - sent, hipMemcpyHostToDevice, s));
+        if (bt.resume) {
+            // the chain state, then the running sums: sent from staging, or zeroed where the caller keeps none (sumacc)
+            for (const bool ckpt : {true, false})
+                for (const Buf& b : bt.row) {
+                    if (!b.bytes || b.role != Role::inout || b.ckpt != ckpt) continue;
+                    if (b.staged()) { HIP_TRY(hipMemcpyAsync(D + b.doff, P + b.poff, N * b.bytes, hipMemcpyHostToDevice, s)); }
+                    else HIP_TRY(hipMemsetAsync(D + b.doff, 0, N * b.bytes, s));
+                }
+            // outputs a skipped window never writes read as zero
+            for (const Buf& b : bt.row)
+                if (b.bytes && b.zeroed && b.role == Role::out) HIP_TRY(hipMemsetAsync(D + b.doff, 0, N * b.bytes, s));
+        } else {
+            // status, summary, the checkpoint blocks (they live in the recycled arena: a skipped window writes none of them and
+            // must not hand the caller an earlier call's bytes), x_final, sigvals, the per-sample summaries, pif, the running
+            // smoothed / filtered sums: one memset
+            HIP_TRY(hipMemsetAsync(D + bt.zero_begin, 0, bt.zero_end - bt.zero_begin, s));
+        }
+        if (pl.bv) HIP_TRY(hipFuncSetAttribute(pl.fptr(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.dyn));
+        const int rc = dord ? build_bucket_lists(pl, base.T, n, dord, s) : 0;
+        mark("inputs enqueued");
+        return rc;
+    }
+
+    // Chunk cidx of pinned staging into the caller's per-draw arrays, shared with the scatter helpers.
+    void scatter(int cidx)
+    {
         const Chunk& ch = chunks[cidx];
-        const size_t ndc = (size_t)(ch.d1 - ch.d0);
-        const double* src = PP(double, o_pchunk[cidx % RING]);
+        const size_t ndc = (size_t)(ch.d1 - ch.d0), N = (size_t)n, ld = (size_t)cfg->ldY;
+        const double* src = reinterpret_cast<const double*>(P + o_pchunk[cidx % RING]);
+        const int32_t* skip = reinterpret_cast<const int32_t*>(P + o_pst0);
         if (!copy_out || ndc == 0) return;
         const std::function<void(int, int)> part = [&](int pi, int np) {          // windows [i0, i1) of this chunk
             const int i0 = (int)((long long)n * pi / np), i1 = (int)((long long)n * (pi + 1) / np);
@@ -966,7 +889,7 @@ int run_host_on_device(DeviceCtx& c, const hmcg_config* cfg, const int32_t* idx,
                 const size_t g = row(i);
                 // a skipped window produced nothing -- its block of the (recycled) chunk buffer holds an earlier call's bytes:
                 // the contract (hmcg.h) says its outputs read zero
-                const bool skipped = (PP(int32_t, o_pst0)[i] & ST_SKIPPED) != 0;
+                const bool skipped = (skip[i] & bt.skip_mask) != 0;
                 for (const Col& cc : cols) {
                     if (!cc.host) continue;
                     if (skipped) {
@@ -986,36 +909,34 @@ int run_host_on_device(DeviceCtx& c, const hmcg_config* cfg, const int32_t* idx,
         if (8 * ncols * N * ndc < ((size_t)1 << 20)) part(0, 1);                  // small chunks: not worth a hand-off
         else c.pool.run(part);
         mark("scattered");
-    };
-    // The copy of chunk c waits on the copy stream for the kernel's event (device-side hand-off); the host blocks on the copy's
-    // event and scatters.  (HMCG_HOST_CHAIN, diagnostics: the host itself watches for the end of kernel c and then issues the
-    // copy, polling the two events in turn -- same timeline, one spinning core; kept because it shows in the trace WHEN each
-    // kernel was seen to end, which is how the late first copy of `profiles/r04/trace_host_entry_skip_words.txt` was found.)
-    const bool device_chain = diag_env("HMCG_HOST_CHAIN") == nullptr;
-    std::vector<char> self_issued((size_t)nch, 0);
-    auto enqueue_kernel = [&](int cidx) -> int {
+    }
+
+    // Kernel(s) of chunk cidx, then its copy-out: on the copy stream behind the kernel's event, or -- the last chunk, hidden
+    // behind nothing -- on the compute stream itself right behind its kernel.  (An SDMA copy: 54 GB/s beside a running sweep
+    // kernel.  Nothing small may go ahead of it on the copy stream: a copy of a few KB is a shader copy in the HIP runtime and
+    // waits for a free CU, i.e. for the end of the NEXT sweep kernel.)
+    int enqueue_chunk(int cidx)
+    {
+        hipStream_t s = c.stream;
+        const int nch = (int)chunks.size();
         const Chunk& ch = chunks[cidx];
         const int slot = cidx % RING;
         hmcg::KernelParams p = base;
         p.sweep_begin = ch.s0; p.sweep_end = ch.s1;
-        p.resume = (resume_in || cidx > 0) ? 1 : 0;
+        p.resume = (bt.resume || cidx > 0) ? 1 : 0;
         p.final_launch = (ch.s1 == total_sweeps) ? 1 : 0;
-        const size_t ndc = (size_t)(ch.d1 - ch.d0);
+        const size_t ndc = (size_t)(ch.d1 - ch.d0), N = (size_t)n;
         p.nd_ld = (int32_t)std::max<size_t>(ndc, 1); p.draw_off = (int32_t)ch.d0;
         // The LAST chunk's draws (1/32 of the run, 1.3 MB at the headline shape) are written by the kernel straight into the
         // pinned staging buffer: host memory the device addresses directly, complete at the end of the kernel -- there is no
         // copy behind the last kernel (it cost ~0.1 ms of the call's tail: nothing left to hide it behind).  Only the last:
         // a kernel that writes across the link runs 11 % slower (measured with every chunk direct).
-        const bool direct_tail = stream_draws && copy_out && (cidx == nch - 1 || diag_env("HMCG_DIRECT_ALL")) && !want_corr && nch > 1 &&
-                                 diag_env("HMCG_NO_TAIL_COPY") == nullptr && diag_env("HMCG_NO_DIRECT_TAIL") == nullptr;
+        const bool tail = cidx == nch - 1 && !want_corr;
+        const bool direct_tail = stream_draws && copy_out && tail && nch > 1 && diag_env("HMCG_NO_DIRECT_TAIL") == nullptr;
         if (stream_draws) {
-            double* cb = direct_tail ? PP(double, o_pchunk[slot]) : DP(double, o_dchunk[slot]);
-            p.mu = cols[0].ncol ? cb + ndc * cols[0].off * N : nullptr;
-            p.sig2 = cols[1].ncol ? cb + ndc * cols[1].off * N : nullptr;
-            p.A = cols[2].ncol ? cb + ndc * cols[2].off * N : nullptr;
-            p.pi_end = cols[3].ncol ? cb + ndc * cols[3].off * N : nullptr;
-            p.fcast = cols[4].ncol ? cb + ndc * cols[4].off * N : nullptr;
-            p.pi_smooth_draws = cols[5].ncol ? cb + ndc * cols[5].off * N : nullptr;
+            double* cb = reinterpret_cast<double*>(direct_tail ? P + o_pchunk[slot] : D + o_dchunk[slot]);
+            double** outs[6] = { &p.mu, &p.sig2, &p.A, &p.pi_end, &p.fcast, &p.pi_smooth_draws };
+            for (int g = 0; g < 6; ++g) *outs[g] = cols[g].ncol ? cb + ndc * cols[g].off * N : nullptr;
             // (a skipped window writes nothing into its block: the scatter zeroes its rows of the caller's arrays instead of
             //  copying them -- no memset node per chunk on the stream)
         }
@@ -1023,154 +944,117 @@ int run_host_on_device(DeviceCtx& c, const hmcg_config* cfg, const int32_t* idx,
         // zeroed here): the scatter knows which windows' blocks hold nothing once that kernel has ended
         if (cidx == 0 && stream_draws && copy_out) {
             memset(P + o_pst0, 0, 4 * N);
-            p.skip_host = PP(int32_t, o_pst0);
+            p.skip_host = reinterpret_cast<int32_t*>(P + o_pst0);
         }
         if (timing) HIP_TRY(hipEventRecord(tev.ev[2 * (size_t)cidx], s));
-        const int lrc = launch_kernel(c, pl, p, s, use_lists ? DP(int32_t, o_dord) : nullptr);
-        if (lrc) return lrc;
+        const int rc = launch_kernel(c, pl, p, s, dord);
+        if (rc) return rc;
         if (timing) HIP_TRY(hipEventRecord(tev.ev[2 * (size_t)cidx + 1], s));
-        if (stream_draws) {
-            // the last chunk's copy-out hides behind nothing: it goes on the compute stream itself, right behind its kernel
-            // (or is no copy at all: direct_tail)
-            const bool tail_copy = cidx == nch - 1 && !want_corr && diag_env("HMCG_NO_TAIL_COPY") == nullptr;
-            if (tail_copy || direct_tail || device_chain) {
-                hipStream_t cs = tail_copy ? s : c.copy;
-                if (!tail_copy) {
-                    HIP_TRY(hipEventRecord(c.evk[slot], s));
-                    HIP_TRY(hipStreamWaitEvent(c.copy, c.evk[slot], 0));
-                }
-                if (ndc > 0 && copy_out && !direct_tail)
-                    HIP_TRY(hipMemcpyAsync(P + o_pchunk[slot], D + o_dchunk[slot], 8 * ncols * N * ndc, hipMemcpyDeviceToHost, cs));
-                HIP_TRY(hipEventRecord(c.evc[slot], cs));
-                self_issued[(size_t)cidx] = 1;
-            } else {
-                HIP_TRY(hipEventRecord(c.evk[slot], s));
-            }
-            if (want_corr && ndc > 0) {
-                // second moments of the chunk's rounded draws, in HBM, beside the chunk's copy-out (calccorr)
-                hmcg_host::MomentsArgs ma{p.mu, p.sig2, p.pi_end, p.A, p.fcast, DP(double, o_dmom), (long long)ndc, (long long)ndc,
-                                          n, cfg->K, cfg->H, ch.d0 == 0};
-                HIP_TRY(hmcg_host::launch_moments(ma, s));
-            }
+        if (!stream_draws) return 0;
+        hipStream_t cs = tail ? s : c.copy;
+        if (!tail) {
+            HIP_TRY(hipEventRecord(c.evk[slot], s));
+            HIP_TRY(hipStreamWaitEvent(c.copy, c.evk[slot], 0));
+        }
+        if (ndc > 0 && copy_out && !direct_tail)
+            HIP_TRY(hipMemcpyAsync(P + o_pchunk[slot], D + o_dchunk[slot], 8 * ncols * N * ndc, hipMemcpyDeviceToHost, cs));
+        HIP_TRY(hipEventRecord(c.evc[slot], cs));
+        if (want_corr && ndc > 0) {
+            // second moments of the chunk's rounded draws, in HBM, beside the chunk's copy-out (calccorr)
+            hmcg_host::MomentsArgs ma{p.mu, p.sig2, p.pi_end, p.A, p.fcast, dmom, (long long)ndc, (long long)ndc, n, cfg->K, cfg->H, ch.d0 == 0};
+            HIP_TRY(hmcg_host::launch_moments(ma, s));
         }
         return 0;
-    };
-    auto issue_copy = [&](int cidx) -> int {          // kernel cidx is known to be complete: no device-side wait
-        const Chunk& ch = chunks[cidx];
-        const int slot = cidx % RING;
-        const size_t ndc = (size_t)(ch.d1 - ch.d0);
-        // (an SDMA copy: 54 GB/s beside a running sweep kernel.  Nothing small may go ahead of it on this stream: a copy of
-        //  a few KB is a shader copy in the HIP runtime and waits for a free CU, i.e. for the end of the NEXT sweep kernel)
-        if (ndc > 0 && copy_out)
-            HIP_TRY(hipMemcpyAsync(P + o_pchunk[slot], D + o_dchunk[slot], 8 * ncols * N * ndc, hipMemcpyDeviceToHost, c.copy));
-        HIP_TRY(hipEventRecord(c.evc[slot], c.copy));
-        return 0;
-    };
-    auto after_last_kernel = [&]() -> int {
-        mark("kernels enqueued");
-        if (want_corr) HIP_TRY(hmcg_host::launch_corr_finalize(DP(double, o_dmom), DP(double, o_dcorr), n, cfg->K, s));
-        // ---- small outputs and one-off extras: D2H on the compute stream (after the last kernel) ----
-#define D2H(poff, doff, bytes) HIP_TRY(hipMemcpyAsync(P + (poff), D + (doff), (bytes), hipMemcpyDeviceToHost, s))
-        D2H(o_pst, o_dst, (h.summary ? o_dsum + 8 * N * NS : o_dst + 4 * N) - o_dst);        // status | summary, adjacent on both sides
-        if (want_xf) D2H(o_pxf, o_dxf, 4 * N * ld);
-        if (user_pif) D2H(o_ppif, o_dpif, 8 * N * ld * K);
-        if (want_sm) D2H(o_psm, o_dsm, 8 * N * ld * K);
-        if (want_fm) D2H(o_pfm, o_dfm, 8 * N * ld * K);
-        if (want_sv) D2H(o_psv, o_dsv, 8 * N * nsv);
-        if (want_ss) D2H(o_pss2, o_dss2, 8 * N * nss);
-        if (want_corr) D2H(o_pcorr, o_dcorr, 8 * N * NCC * NCC);
-        if (ex && ex->xstate) D2H(o_pxs, o_dxs, N * ld);
-        if (ex && ex->sumacc) D2H(o_pacc, o_dacc, 8 * N * (NS + K));
-#undef D2H
-        return 0;
-    };
-    auto done = [&](hipEvent_t e, bool& yes) -> int {
-        const hipError_t q = hipEventQuery(e);
-        if (q == hipSuccess) { yes = true; return 0; }
-        yes = false;
-        if (q == hipErrorNotReady) return 0;
-        set_err("hipEventQuery failed: %s (%s:%d)", hipGetErrorString(q), __FILE__, __LINE__);
-        return (int)q;
-    };
+    }
+
+    // Behind the last kernel, on the compute stream: the correlations, then every returned row of the table (table order;
+    // status | summary in one copy).
+    int enqueue_returns()
     {
-        int enq = 0, iss = 0, sca = 0;
-        while (enq < nch || (stream_draws && sca < nch)) {
-            bool progress = false;
+        mark("kernels enqueued");
+        if (want_corr) HIP_TRY(hmcg_host::launch_corr_finalize(dmom, dcorr, n, cfg->K, c.stream));
+        const size_t N = (size_t)n;
+        size_t doff = 0, poff = 0, len = 0;
+        for (const Buf& b : bt.row) {
+            if (!b.returned()) continue;
+            if (b.same_copy && len) { len = b.doff + N * b.bytes - doff; continue; }
+            if (len) HIP_TRY(hipMemcpyAsync(P + poff, D + doff, len, hipMemcpyDeviceToHost, c.stream));
+            doff = b.doff; poff = b.poff; len = N * b.bytes;
+        }
+        if (len) HIP_TRY(hipMemcpyAsync(P + poff, D + doff, len, hipMemcpyDeviceToHost, c.stream));
+        return 0;
+    }
+
+    // The chunk pipeline: kernel c -> evk[c % RING] -> SDMA copy of its chunk buffer into pinned staging (copy stream) ->
+    // evc[c % RING] -> host scatter into the caller's arrays.  A chunk buffer is [array][window][column][draw] with the chunk's
+    // own draw count as leading dimension (one contiguous block: a plain 1-D copy, which the SDMA engines carry without touching
+    // the CUs -- a helped sweep kernel leaves no registers for a blit kernel to run beside it).  Kernel c + RING reuses both
+    // the device and the pinned buffer of chunk c: it is enqueued only after the host has waited for copy c and scattered it.
+    int run_chunks()
+    {
+        const int nch = (int)chunks.size();
+        if (timing) {
+            tev.ev.assign(2 * (size_t)nch, nullptr);
+            for (auto& e : tev.ev) HIP_TRY(hipEventCreate(&e));
+        }
+        int rc = 0;
+        for (int enq = 0, sca = 0; enq < nch || (stream_draws && sca < nch);) {
             while (enq < nch && (!stream_draws || enq < sca + RING)) {
-                rc = enqueue_kernel(enq);
-                if (rc) return rc;
-                if (++enq == nch) { rc = after_last_kernel(); if (rc) return rc; }
-                progress = true;
+                if ((rc = enqueue_chunk(enq))) return rc;
+                if (++enq == nch && (rc = enqueue_returns())) return rc;
             }
             if (!stream_draws) break;
-            if (iss < enq) {
-                bool yes = self_issued[(size_t)iss] != 0;
-                if (!yes) {
-                    rc = done(c.evk[iss % RING], yes);
-                    if (rc) return rc;
-                    if (yes) { mark("kernel seen"); rc = issue_copy(iss); if (rc) return rc; }
+            HIP_TRY(hipEventSynchronize(c.evc[sca % RING]));
+            mark("copy landed");
+            scatter(sca++);
+        }
+        mark("chunks scattered");
+        return 0;
+    }
+
+    int collect_outputs()
+    {
+        HIP_TRY(hipStreamSynchronize(c.stream));
+        mark("stream idle");
+        unpack_rows(bt, P, idx, n);
+        mark("small outputs copied");
+        const int nch = (int)chunks.size();
+        if (trace_on()) {
+            fprintf(stderr, "[trace] device %d, %d windows, %d chunks:", c.device, n, nch);
+            for (const auto& t : trace) fprintf(stderr, " %s %.3f |", t.first, t.second);
+            if (timing) {
+                fprintf(stderr, " chunk kernels (ms @ start after the first one's start):");
+                for (int cidx = 0; cidx < nch; ++cidx) {
+                    float ms = 0.f, at = 0.f;
+                    (void)hipEventElapsedTime(&ms, tev.ev[2 * (size_t)cidx], tev.ev[2 * (size_t)cidx + 1]);
+                    (void)hipEventElapsedTime(&at, tev.ev[0], tev.ev[2 * (size_t)cidx]);
+                    fprintf(stderr, " %.3f@%.3f", ms, at);
                 }
-                if (yes) { ++iss; progress = true; }
             }
-            if (sca < iss) {
-                bool yes = false;
-                rc = done(c.evc[sca % RING], yes);
-                if (rc) return rc;
-                if (yes) { mark("copy landed"); scatter(sca); ++sca; progress = true; }
-            }
-            if (!progress) {
-                // nothing but the oldest outstanding copy to wait for: block on it; otherwise (host chain) keep polling
-                if (sca < iss && iss == enq) HIP_TRY(hipEventSynchronize(c.evc[sca % RING]));
-                else __builtin_ia32_pause();
-            }
+            fprintf(stderr, "\n");
         }
-    }
-    mark("chunks scattered");
-    HIP_TRY(hipStreamSynchronize(s));
-    mark("stream idle");
-    for (int i = 0; i < n; ++i) {
-        const size_t g = row(i);
-        // (a skipped window's per-draw rows were zeroed by the scatter, chunk by chunk; its correlation matrix here)
-        if (want_corr && (PP(int32_t, o_pst)[i] & ST_SKIPPED)) memset(PP(double, o_pcorr) + (size_t)i * NCC * NCC, 0, 8 * NCC * NCC);
-        if (h.status) h.status[g] = PP(int32_t, o_pst)[i];
-        if (h.summary) memcpy(h.summary + g * NS, PP(double, o_psum) + (size_t)i * NS, 8 * NS);
-        if (want_xf) memcpy(ex->x_final + g * ld, PP(int32_t, o_pxf) + (size_t)i * ld, 4 * ld);
-        if (user_pif) memcpy(ex->pif_final + g * ld * K, PP(double, o_ppif) + (size_t)i * ld * K, 8 * ld * K);
-        if (want_sm) memcpy(ex->pi_smooth_mean + g * ld * K, PP(double, o_psm) + (size_t)i * ld * K, 8 * ld * K);
-        if (want_fm) memcpy(ex->pi_filter_mean + g * ld * K, PP(double, o_pfm) + (size_t)i * ld * K, 8 * ld * K);
-        if (want_sv) memcpy(ex->sigvals + g * nsv, PP(double, o_psv) + (size_t)i * nsv, 8 * nsv);
-        if (want_ss) memcpy(ex->sample_summary + g * nss, PP(double, o_pss2) + (size_t)i * nss, 8 * nss);
-        if (want_corr) memcpy(ex->corr + g * NCC * NCC, PP(double, o_pcorr) + (size_t)i * NCC * NCC, 8 * NCC * NCC);
-        if (ex && ex->xstate) memcpy(ex->xstate + g * ld, PP(uint8_t, o_pxs) + (size_t)i * ld, ld);
-        if (ex && ex->sumacc) memcpy(ex->sumacc + g * (NS + K), PP(double, o_pacc) + (size_t)i * (NS + K), 8 * (NS + K));
-    }
-#undef DP
-#undef PP
-    mark("small outputs copied");
-    if (trace_on) {
-        fprintf(stderr, "[trace] device %d, %d windows, %d chunks:", c.device, n, nch);
-        for (const auto& t : trace) fprintf(stderr, " %s %.3f |", t.first, t.second);
         if (timing) {
-            fprintf(stderr, " chunk kernels (ms @ start after the first one's start):");
+            double kernel_ms = 0.0;
             for (int cidx = 0; cidx < nch; ++cidx) {
-                float ms = 0.f, at = 0.f;
-                (void)hipEventElapsedTime(&ms, tev.ev[2 * (size_t)cidx], tev.ev[2 * (size_t)cidx + 1]);
-                (void)hipEventElapsedTime(&at, tev.ev[0], tev.ev[2 * (size_t)cidx]);
-                fprintf(stderr, " %.3f@%.3f", ms, at);
+                float ms = 0.f;
+                HIP_TRY(hipEventElapsedTime(&ms, tev.ev[2 * (size_t)cidx], tev.ev[2 * (size_t)cidx + 1]));
+                kernel_ms += ms;       // the chunk's sweep kernel(s); a wait for a ring slot falls before the first event
             }
+            fill_timing(timing, pl, c, kernel_ms, nch, ms_so_far(), n);
         }
-        fprintf(stderr, "\n");
+        return 0;
     }
-    if (timing) {
-        for (int cidx = 0; cidx < nch; ++cidx) {
-            float ms = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms, tev.ev[2 * (size_t)cidx], tev.ev[2 * (size_t)cidx + 1]));
-            kernel_ms += ms;       // the chunk's sweep kernel(s); a wait for a ring slot falls before the first event
-        }
-        const double call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
-        fill_timing(timing, pl, c, kernel_ms, nch, call_ms, n);
-    }
-    return 0;
+};
+
+int run_host_on_device(DeviceCtx& c, const hmcg_config* cfg, const int32_t* idx, int n, const HostArrays& h, hmcg_timing* timing)
+{
+    HostCall k{c, cfg, idx, n, h, timing};
+    int rc = k.plan();
+    if (!rc) rc = k.lay_out();
+    if (!rc) rc = k.stage_inputs();
+    if (!rc) rc = k.run_chunks();
+    if (!rc) rc = k.collect_outputs();
+    return rc;
 }
 
 }  // namespace

@@ -31,11 +31,18 @@ struct BigVariant {
     int K, NT;
     BigKernelFn fn;
 };
-// LDS-resident kernels (gibbs_big.hpp): large K, or windows too long for the register-resident variants
-extern const BigVariant g_big_variants[], g_big_smooth_variants[], g_big_stream_variants[], g_big_sig_variants[], g_big_sig_stream_variants[],
-    g_big_sigsmooth_variants[], g_big_smooth_stream_variants[], g_big_sigsmooth_stream_variants[];
-extern const int g_n_big_variants, g_n_big_smooth_variants, g_n_big_stream_variants, g_n_big_sig_variants, g_n_big_sig_stream_variants,
-    g_n_big_sigsmooth_variants, g_n_big_smooth_stream_variants, g_n_big_sigsmooth_stream_variants;
+// LDS-resident kernels (gibbs_big.hpp): large K, or windows too long for the register-resident variants.  Every form --
+// signal path, smoothing pass, HBM-streaming -- is compiled for K = 2..8: g_big[sig][smooth][stream][K - 2], filled by the
+// variants_big*.hip units.
+constexpr int BIG_KMIN = 2, BIG_NK = 7;
+using BigForm = BigVariant[BIG_NK];
+extern const BigForm* const g_big[2][2][2];
+#define HMCG_BIG(K_, SIG_, SM_, ST_) { K_, 256, hmcg::gibbs_sweeps_kernel_big<K_, 256, SM_, ST_, SIG_> }
+#define HMCG_BIG_FORM(SIG_, SM_, ST_)                                                                                \
+    { HMCG_BIG(2, SIG_, SM_, ST_), HMCG_BIG(3, SIG_, SM_, ST_), HMCG_BIG(4, SIG_, SM_, ST_), HMCG_BIG(5, SIG_, SM_, ST_), \
+      HMCG_BIG(6, SIG_, SM_, ST_), HMCG_BIG(7, SIG_, SM_, ST_), HMCG_BIG(8, SIG_, SM_, ST_) }
+// the forms, one per [sig][smooth][stream]
+extern const BigForm g_big_000, g_big_001, g_big_010, g_big_011, g_big_100, g_big_101, g_big_110, g_big_111;
 
 #define HMCG_V(K_, L_, NT_, SIG_, SM_, NH_, OCC_, PS_, PB_) \
     { K_, L_, NT_, hmcg::gibbs_sweeps_kernel<K_, L_, NT_, SIG_, SM_, NH_, OCC_>, SIG_, SM_, NH_, OCC_, PS_, PB_ }

@@ -3,9 +3,12 @@
 //   * hmcg_hostutil::ScatterPool -- the helper threads of the host entry's scatter: start / run / stop / start again with a
 //     job posted at once (the generation race of ADVICE r2), many jobs, jobs that write disjoint parts of one array;
 //   * hmcg_hostutil::partition_windows, plan_chunks -- invariants on random shapes;
+//   * hmcg_hostutil::host_buffers, pack_rows, unpack_rows -- the table of a host-entry call's per-window arrays on random
+//     configurations: the arena layouts' invariants, and pack + unpack against the caller's rows;
 //   * hmcg_csv.cpp -- hmcg_format_float, hmcg_write_table_csv and hmcg_save_results_csv with its thread pool.
 // Exits 0 when every check holds; sanitizer reports make it exit non-zero by themselves.
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstring>
 #include <random>
@@ -95,6 +98,155 @@ static int chunk_checks()
     return 0;
 }
 
+static size_t al(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// The layouts of host_buffers on random configurations, and pack_rows + unpack_rows against the caller's rows.
+static int buffer_checks()
+{
+    std::mt19937 g(13);
+    auto coin = [&]() { return (g() & 1) != 0; };
+    const BufId zeroed_ids[] = {B_STATUS, B_SUMMARY, B_XSTATE, B_SUMACC, B_XFINAL, B_SIGVALS, B_SSUM, B_PIF, B_SMOOTH, B_FILTER};
+    const BufId resume_ids[] = {B_STATUS, B_XSTATE, B_SUMACC, B_SMOOTH, B_FILTER, B_SSUM};     // what a RESUME call reads back
+    for (int rep = 0; rep < 400; ++rep) {
+        hmcg_config cfg{};
+        cfg.K = 2 + (int)(g() % 7); cfg.ldY = 2 + (int)(g() % 300); cfg.H = (int)(g() % 5); cfg.n_samples = (int)(g() % 4);
+        cfg.window_base = g();
+        const bool resume = coin();
+        cfg.flags = resume ? HMCG_FLAG_RESUME : 0;
+        const int n = 1 + (int)(g() % 40), W = n + (int)(g() % 20);
+        std::vector<int32_t> perm((size_t)W);                      // a random subset of the caller's W rows in random order
+        std::iota(perm.begin(), perm.end(), 0);
+        std::shuffle(perm.begin(), perm.end(), g);
+        const int32_t* idx = coin() ? perm.data() : nullptr;       // (or rows 0..n-1)
+        // every caller array on or off; a non-null placeholder until the table says how wide its rows are
+        char on;
+        auto opt = [&]() -> void* { return coin() ? &on : nullptr; };
+        hmcg_extras ex{};
+        ex.struct_size = (int32_t)sizeof ex;
+        HostArrays h{};
+        h.Y = (const double*)&on; h.T = (const int32_t*)&on;
+        h.yreal = (const double*)opt(); h.summary = (double*)opt(); h.status = (int32_t*)opt();
+        ex.x_init = (const int32_t*)opt(); ex.x_final = (int32_t*)opt(); ex.pif_final = (double*)opt();
+        ex.xstate = (uint8_t*)(resume ? &on : opt()); ex.sumacc = (double*)opt(); ex.window_ids = (const uint32_t*)opt();
+        ex.sig_range = (const int32_t*)opt(); ex.save_range = (const int32_t*)opt(); ex.sigma_signal = (const double*)opt();
+        ex.sigvals = (double*)opt(); ex.nsave_ld = (int32_t)(g() % 4); ex.end_pos = (const int32_t*)opt();
+        ex.pi_smooth_mean = (double*)opt(); ex.pi_filter_mean = (double*)opt(); ex.corr = (double*)opt();
+        ex.sample_summary = (double*)opt();
+        h.ex = &ex;
+        const bool need_ckpt = resume || ex.xstate || ex.sumacc || coin(), need_pif = coin();
+        BufTable t = host_buffers(cfg, h, n, need_ckpt, need_pif, 1 + g() % 100);
+        const size_t N = (size_t)n;
+
+        // ---- layouts ----
+        CHECK(t.resume == resume);
+        CHECK(t.row[B_Y].doff == 0 && t.row[B_Y].poff == 0 && t.row[B_Y].bytes == 8 * (size_t)cfg.ldY);
+        for (int i = 0; i < NBUF; ++i) {
+            const Buf& a = t.row[i];
+            CHECK((a.bytes == 0) == (a.doff == NO_OFF));
+            if (!a.bytes) { CHECK(a.poff == NO_OFF); continue; }
+            CHECK(a.doff % 256 == 0 && a.doff + N * a.bytes <= t.dev.total);
+            if (a.staged()) CHECK(a.poff % 256 == 0 && a.poff + N * a.bytes <= t.pin.total);
+            if (a.role == Role::in) CHECK(a.staged() && a.doff == a.poff && a.doff + N * a.bytes <= t.input_bytes);
+            else CHECK(a.doff >= t.input_bytes && (!a.staged() || a.poff >= t.input_bytes));
+            CHECK(a.zeroed == (a.doff >= t.zero_begin && a.doff < t.zero_end));
+            if (a.host || (a.role == Role::inout && a.hook == Hook::resume_status)) CHECK(a.staged() || a.role == Role::in);
+            for (int j = 0; j < i; ++j) {                          // no two buffers overlap, on either side
+                const Buf& b = t.row[j];
+                if (!b.bytes) continue;
+                CHECK(a.doff + al(N * a.bytes) <= b.doff || b.doff + al(N * b.bytes) <= a.doff);
+                if (a.staged() && b.staged()) CHECK(a.poff + al(N * a.bytes) <= b.poff || b.poff + al(N * b.bytes) <= a.poff);
+            }
+        }
+        // the input block: Y, T, ids and the optional per-window inputs, the same bytes in both arenas
+        size_t in_bytes = 0;
+        for (const Buf& b : t.row) if (b.bytes && b.role == Role::in) in_bytes += al(N * b.bytes);
+        CHECK(in_bytes == t.input_bytes && t.zero_begin == t.input_bytes);
+        // the zeroed block: contiguous, exactly the outputs a skipped window never writes
+        size_t z_bytes = 0;
+        for (BufId id : zeroed_ids) { CHECK(t.row[id].zeroed); z_bytes += t.row[id].bytes ? al(N * t.row[id].bytes) : 0; }
+        int nz = 0;
+        for (const Buf& b : t.row) nz += b.zeroed ? 1 : 0;
+        CHECK(nz == (int)(sizeof zeroed_ids / sizeof zeroed_ids[0]));
+        CHECK(z_bytes == t.zero_end - t.zero_begin && t.row[B_STATUS].bytes == 4);
+        for (int i = 0; i < NBUF; ++i) {
+            bool r = false;
+            for (BufId id : resume_ids) r |= id == i;
+            CHECK((t.row[i].role == Role::inout) == r && (t.row[i].role == Role::in) == (i <= B_SIGMA));
+            CHECK(t.row[i].ckpt == (i == B_STATUS || i == B_XSTATE || i == B_SUMACC));
+        }
+        // status and summary adjacent on both sides, returned in one copy
+        const Buf &st = t.row[B_STATUS], &sm = t.row[B_SUMMARY];
+        CHECK(st.staged() && st.returned());
+        if (sm.bytes) CHECK(sm.same_copy && sm.doff == st.doff + al(4 * N) && sm.poff == st.poff + al(4 * N));
+        for (const Buf& b : t.row) CHECK(!b.same_copy || &b == &sm);
+        // the device slots: each row's pointer where the kernels look for it
+        std::vector<char> dev(t.dev.total);
+        const DevSlots ds = device_slots(t, dev.data());
+        CHECK((const char*)ds.Y == dev.data() && (const char*)ds.ex.window_ids == dev.data() + t.row[B_WID].doff);
+        CHECK((ds.ex.sumacc != nullptr) == need_ckpt && (ds.ex.corr != nullptr) == (ex.corr != nullptr) && (ds.mom != nullptr) == (ex.corr != nullptr));
+        CHECK((ds.summary != nullptr) == (h.summary != nullptr) && (const char*)ds.status == dev.data() + st.doff);
+
+        // ---- pack, then unpack: every caller row comes back, nothing else is touched ----
+        std::vector<std::vector<char>> caller(NBUF), before(NBUF);
+        for (int i = 0; i < NBUF; ++i) {
+            Buf& b = t.row[i];
+            if (!b.host) continue;
+            caller[i].resize((size_t)W * b.bytes + 1);
+            for (auto& c : caller[i]) c = (char)g();
+            if (i == B_STATUS)                                    // caller status words without skip bits: they round-trip
+                for (int w = 0; w < W; ++w) reinterpret_cast<int32_t*>(caller[i].data())[w] &= ~t.skip_mask;
+            before[i] = caller[i];
+            b.host = caller[i].data();
+        }
+        const unsigned char canary = 0xA5;
+        std::vector<char> pin(t.pin.total + 64, (char)canary);
+        const int split = (int)(g() % (unsigned)(n + 1));
+        pack_rows(t, pin.data(), idx, 0, split);
+        pack_rows(t, pin.data(), idx, split, n);
+        std::vector<char> packed_mask(pin.size(), 0);
+        for (int r = 0; r < NBUF; ++r) {
+            const Buf& b = t.row[r];
+            if (!b.sent(resume)) continue;
+            for (int i = 0; i < n; ++i) {
+                const size_t gr = idx ? (size_t)idx[i] : (size_t)i;
+                const char* p = pin.data() + b.poff + (size_t)i * b.bytes;
+                if (r == B_WID && !b.host) CHECK(*reinterpret_cast<const uint32_t*>(p) == cfg.window_base + (uint32_t)gr);
+                else if (r == B_STATUS && !b.host) CHECK(*reinterpret_cast<const int32_t*>(p) == 0);
+                else CHECK(memcmp(p, caller[r].data() + gr * b.bytes, b.bytes) == 0);
+                memset(packed_mask.data() + (p - pin.data()), 1, b.bytes);
+            }
+        }
+        for (size_t q = 0; q < pin.size(); ++q) CHECK(packed_mask[q] || (unsigned char)pin[q] == canary);   // nothing else written
+        for (int r = 0; r < NBUF; ++r) if (t.row[r].role == Role::in && t.row[r].host) CHECK(caller[r] == before[r]);
+        // the device's results: every returned row that was not sent gets fresh bytes, and a few windows are skipped
+        for (int r = 0; r < NBUF; ++r) {
+            const Buf& b = t.row[r];
+            if (!b.returned() || b.sent(resume)) continue;
+            for (size_t q = 0; q < N * b.bytes; ++q) pin[b.poff + q] = (char)g();
+        }
+        int32_t* pst = reinterpret_cast<int32_t*>(pin.data() + st.poff);
+        for (int i = 0; i < n; ++i) pst[i] = (g() % 4 == 0) ? HMCG_ST_BAD_T : 0;
+        std::vector<std::vector<char>> want = caller;
+        for (int r = 0; r < NBUF; ++r) {
+            const Buf& b = t.row[r];
+            if (!b.returned() || !b.host) continue;
+            for (int i = 0; i < n; ++i) {
+                const size_t gr = idx ? (size_t)idx[i] : (size_t)i;
+                char* dst = want[r].data() + gr * b.bytes;
+                if (b.hook == Hook::zero_if_skipped && pst[i]) memset(dst, 0, b.bytes);
+                else memcpy(dst, pin.data() + b.poff + (size_t)i * b.bytes, b.bytes);
+            }
+        }
+        // (a RESUME call's inout rows come back as they went: the caller's own rows)
+        if (resume)
+            for (int r = 0; r < NBUF; ++r)
+                if (r != B_STATUS && t.row[r].role == Role::inout && t.row[r].host) CHECK(want[r] == before[r]);
+        unpack_rows(t, pin.data(), idx, n);
+        for (int r = 0; r < NBUF; ++r) CHECK(caller[r] == want[r]);
+    }
+    return 0;
+}
+
 static int csv_checks(const char* dir)
 {
     char buf[64];
@@ -139,6 +291,7 @@ int main(int argc, char** argv)
     if (pool_checks()) return 1;
     if (partition_checks()) return 1;
     if (chunk_checks()) return 1;
+    if (buffer_checks()) return 1;
     if (csv_checks(argv[1])) return 1;
     printf("host harness ok\n");
     return 0;

@@ -351,6 +351,49 @@ def test_signal_run_resumed_inside_a_noise_sample(hmclib):
     assert np.max(np.abs(one["sample_summary"].mean(axis=1) - one["summary"])) < 1e-12
 
 
+def test_signal_run_resumed_with_every_running_sum(hmclib):
+    """The chain above split at the same place, now carrying everything a RESUME call reads back at once -- xstate, sumacc,
+    status, sample_summary and the running smoothed / filtered means (the Python wrapper does not carry the last two, so
+    the calls go through the C ABI).  The pair must equal the single call bit for bit."""
+    import ctypes as C
+    K, T, W, burnin, nrun, n_samples, H = 3, 400, 4, 4, 9, 3, 1
+    NS = 3 * K + K * K + 2 * H
+    Y, Tw, fut = synth.generate_panel(W, T, K)
+    Y, Tw32, yreal = np.ascontiguousarray(Y, np.float64), np.ascontiguousarray(Tw, np.int32), np.ascontiguousarray(fut[:, 11:12])
+    sig = np.ascontiguousarray(np.stack([Tw - 25, Tw], axis=1).astype(np.int32))
+    sigma = np.array([0.4, 0.9, 0.1, 0.6])
+    L = _lib.load()
+    carried = ("status", "xstate", "sumacc", "sample_summary", "pi_smooth_mean", "pi_filter_mean")
+
+    def call(flags, sweep_base, sweep_count, state=None):
+        o = dict(status=np.zeros(W, np.int32), xstate=np.zeros((W, T), np.uint8), sumacc=np.zeros((W, NS + K)),
+                 sample_summary=np.zeros((W, n_samples, NS)), pi_smooth_mean=np.zeros((W, T, K)), pi_filter_mean=np.zeros((W, T, K)))
+        if state is not None:
+            o = {k: state[k].copy() for k in carried}
+        o["summary"] = np.zeros((W, NS))
+        o["mu"] = np.zeros((W, K, n_samples * nrun))
+        ex = _lib.Extras()
+        ex.struct_size = C.sizeof(_lib.Extras)
+        ex.sig_range, ex.sigma_signal = sig.ctypes.data, sigma.ctypes.data
+        for k in carried[1:]:
+            setattr(ex, k, o[k].ctypes.data)
+        cfg = _lib.make_config(W, K, T, T, burnin, nrun, (12,), flags=flags, sweep_base=sweep_base, alpha=2.0, nu=2.0,
+                               sweep_count=sweep_count, kappa=0.6, n_samples=n_samples)
+        p = _lib._np_ptr
+        rc = L.hmcg_estimate_batch(C.byref(cfg), p(Y), p(Tw32), p(yreal), p(o["mu"]), None, None, None, None, p(o["summary"]),
+                                   p(o["status"]), C.byref(ex), None)
+        assert rc == 0, L.hmcg_last_error()
+        return o
+
+    one = call(0, 0, 0)
+    a = call(0, 0, 19)
+    b = call(_lib.FLAG_RESUME, 19, 0, a)
+    for k in carried + ("summary",):
+        assert np.array_equal(b[k], one[k]), k
+    d = nrun + 2                   # kept draws of the first 19 sweeps: sample 0, then two of sample 1
+    assert np.array_equal(a["mu"][:, :, :d], one["mu"][:, :, :d]) and np.array_equal(b["mu"][:, :, d:], one["mu"][:, :, d:])
+
+
 def test_threads_per_window_variants_agree(hmclib, oracle):
     """The 128- and 512-thread decompositions scan in a different association order; they must
     still match the oracle (and hence each other) within tolerance with identical state paths."""
