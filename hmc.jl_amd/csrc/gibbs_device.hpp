@@ -102,11 +102,12 @@ struct KernelParams {
     // start while the sweep kernels hold every CU, and the chunk's SDMA copy queued behind it waited with it).  May be null.
     int32_t* skip_host;
     // length-bucketed dispatch (hmcg.hip, launch_kernel / bucket_lists_kernel): this launch runs the windows of ONE length class,
-    // t_lo < T[w] <= t_hi; another launch of the same call, with the steps-per-thread variant that fits them, runs the others
-    // beside it on its own stream.  order[0] = n, order[1] = t_lo, order[2] = t_hi, order[4..4+n) = the ids of the class's
-    // windows, compacted: block b runs window order[4 + b] for b < n and leaves at once otherwise.  The live blocks of a
-    // launch are then blocks 0..n-1 whatever the order of the caller's windows -- with the class's windows scattered over the
-    // grid between blocks that leave, a shuffled production batch took 9.5 ms against 6.4 sorted
+    // t_lo <= T[w] <= t_hi (both inclusive: the last class's t_lo is INT32_MIN, so every T has a class); another launch of
+    // the same call, with the steps-per-thread variant that fits them, runs the others beside it on its own stream.
+    // order[0] = n, order[1] = t_lo, order[2] = t_hi, order[4..4+n) = the ids of the class's windows, compacted: block b
+    // runs window order[4 + b] for b < n and leaves at once otherwise.  The live blocks of a launch are then blocks 0..n-1
+    // whatever the order of the caller's windows -- with the class's windows scattered over the grid between blocks that
+    // leave, a shuffled production batch took 9.5 ms against 6.4 sorted
     // (profiles/r04/production_460_order.txt).  n < 0 (the lists found every class in one run of the caller's windows: a
     // batch sorted by length, as the reference's expanding windows are): block b runs window b if its length is in the
     // class and leaves otherwise.  Null: one launch for everything, block b runs window b.
@@ -943,7 +944,7 @@ void gibbs_sweeps_kernel(const KernelParams p)
     const bool helper = NH > 0 && __builtin_amdgcn_readfirstlane(wave) >= NW;   // wave-uniform
     int st = 0;
 
-    if (T <= t_lo_ || T > t_hi_) __builtin_amdgcn_endpgm();   // another length bucket's window: this block leaves at once
+    if (T < t_lo_ || T > t_hi_) __builtin_amdgcn_endpgm();   // another length bucket's window: this block leaves at once
     if (T < 2 || T > NT * L || T > p.ldY) {   // uniform per block
         if (tid == 0) flag_skipped(p, w, HMCG_ST_BAD_T);
         return;

@@ -260,7 +260,8 @@ int validate(const hmcg_config* cfg)
 }
 
 // What runs: the kernel instantiation for this call's shape, chosen once per call.
-// One length bucket of a call: the windows with t_lo < T <= t_hi run on variant v (its own launch, beside the others).
+// One length bucket of a call: the windows with t_lo <= T <= t_hi run on variant v (its own launch, beside the others).
+// Both bounds are inclusive: the first bucket reaches INT32_MAX, the last starts AT INT32_MIN, so every T lies in exactly one.
 struct Bucket {
     const Variant* v;
     int t_lo, t_hi;
@@ -405,7 +406,7 @@ int make_plan(const hmcg_config* cfg, const hmcg_extras* ex, int W, int cu_count
                 }
                 // bucket j: windows longer than the next kept class holds, up to what this class holds (a skipped class is
                 // empty, so every window still runs on the smallest class that covers it)
-                const int t_hi = j == 0 ? INT32_MAX : 256 * Ls[keep[j]], t_lo = j == nk - 1 ? INT32_MIN : 256 * Ls[keep[j + 1]];
+                const int t_hi = j == 0 ? INT32_MAX : 256 * Ls[keep[j]], t_lo = j == nk - 1 ? INT32_MIN : 256 * Ls[keep[j + 1]] + 1;
                 pl.b[pl.nb++] = Bucket{pick_variant(cfg->K, 256 * Ls[keep[j]], 0, use_sig, use_smooth, small_batch, f), t_lo, t_hi};
             }
             if (pl.nb == 1) pl.nb = 0;             // one class after all: a plain single launch
@@ -477,7 +478,7 @@ __global__ void bucket_lists_kernel(const int32_t* T, int W, BucketRanges r, int
     int32_t* meta = ord + (size_t)MAXBUCKET * stride;
     const int w = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (w < W) {
-        auto bucket_of = [&](int t) { int k = 0; for (int b = 0; b < r.nb; ++b) if (t > r.lo[b] && t <= r.hi[b]) k = b; return k; };
+        auto bucket_of = [&](int t) { int k = 0; for (int b = 0; b < r.nb; ++b) if (t >= r.lo[b] && t <= r.hi[b]) k = b; return k; };
         const int mine = bucket_of(T[w]);           // exactly one bucket: the first reaches INT32_MAX, the last starts at INT32_MIN
         int32_t* list = ord + (size_t)mine * stride;
         const int pos = atomicAdd(&list[0], 1);

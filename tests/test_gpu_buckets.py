@@ -125,3 +125,41 @@ def test_shuffled_batch_equals_sorted_batch_on_both_entries(hmclib, panel460, mo
                                  want_state=True, window_ids=ids[perm])
     for k in NAMES + ("x_final", "status"):
         assert np.array_equal(h[k], g[k]), k
+
+
+@pytest.mark.parametrize("order", ["sorted", "shuffled"])
+def test_invalid_lengths_in_a_bucketed_batch(hmclib, order):
+    """Every invalid T in a batch that takes the bucketed dispatch is flagged ST_BAD_T and hands back the zeros that
+    include/hmcg.h documents for a skipped window -- T == INT32_MIN included: it used to belong to no length class (the last
+    one's lower bound was exclusive), landed in list 0 and left through that kernel's class test before the BAD_T check,
+    unflagged, with stale chunk-buffer bytes for outputs.  The valid windows are bit-identical to a call without the bad ones."""
+    lens = [130, 200, 256, 257, 300, 450, 512, 513, 579]
+    ldY = max(lens)
+    bad_T = [np.iinfo(np.int32).min, -1, 0, 1, ldY + 1, np.iinfo(np.int32).max]
+    Yv, Tv, futv = synth.generate_panel(len(lens), ldY, K, ragged=lens)
+    nv, nb = len(lens), len(bad_T)
+    Y = np.concatenate([Yv, np.ones((nb, ldY))])
+    Tw = np.array(lens + bad_T, dtype=np.int32)
+    yreal = np.concatenate([futv[:, [0, 11]], np.zeros((nb, 2))])
+    ids = np.arange(nv + nb)
+    perm = np.argsort(Tw, kind="stable") if order == "sorted" else np.random.default_rng(11).permutation(nv + nb)
+    burnin, nrun = 1, 4
+    # leave draws of an earlier call in the library's recycled chunk buffers
+    _lib.estimate_batch_host(Yv, Tv, K, burnin, nrun, HOR, futv[:, [0, 11]])
+    g = _lib.estimate_batch_host(np.ascontiguousarray(Y[perm]), Tw[perm], K, burnin, nrun, HOR, np.ascontiguousarray(yreal[perm]),
+                                 want_state=True, window_ids=ids[perm], nan_fill=False)
+    assert g["buckets"] > 1
+    ref = _lib.estimate_batch_host(Yv, Tv, K, burnin, nrun, HOR, futv[:, [0, 11]], want_state=True, window_ids=ids[:nv])
+    assert (ref["status"] == 0).all()
+    pos = np.argsort(perm)                                            # row of window i in the permuted call
+    for i in range(nv + nb):
+        r = pos[i]
+        if i >= nv:
+            assert g["status"][r] == _lib.ST_BAD_T, (Tw[i], g["status"][r])
+            for k in NAMES:
+                assert not g[k][r].any(), (Tw[i], k)
+        else:
+            assert g["status"][r] == 0
+            assert np.array_equal(g["x_final"][r], ref["x_final"][i])
+            for k in NAMES:
+                assert np.array_equal(g[k][r], ref[k][i], equal_nan=True), (lens[i], k)

@@ -87,10 +87,13 @@ def rescale():
         hi = hi[2:]
     if hi:
         emit("v_max_u32 %s, %s, v%d" % (VM, VM, hi[0]))
+    # 0 < be < 2040 tested on the unshifted maximum (high word - 2^20 < 0x7f7 << 20, unsigned: the same condition), so that
+    # two instructions stand between the compare and the v_cndmask that reads its vcc (the two wait states a VALU write of
+    # vcc needs before a VALU reads it; the compiler pads that pair, nothing does inside an asm statement)
+    emit("v_add_u32 %s, 0xfff00000, %s" % (VT, VM))
+    emit("v_cmp_gt_u32 vcc, 0x7f700000, %s" % VT)
     emit("v_lshrrev_b32 %s, 20, %s" % (VM, VM))
-    emit("v_add_u32 %s, -1, %s" % (VT, VM))
     emit("v_sub_u32 %s, 0x3fe, %s" % (VE, VM))
-    emit("v_cmp_gt_u32 vcc, 0x7f7, %s" % VT)
     emit("v_cndmask_b32 %s, 0, %s, vcc" % (VE, VE))
     for i in range(K * K):
         emit("v_ldexp_f64 %s, %s, %s" % (QREG(i), QREG(i), VE))

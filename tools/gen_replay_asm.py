@@ -126,10 +126,13 @@ def step_body(b, tag, incm):
         emit("v_cmp_nlt_f64 vcc, s[18:19], %s" % TMP)        # !(eps < min): some entry of this lane fails
         emit("s_cbranch_vccnz .Lhmcg_rep_fail%s_%%=" % tag)
     else:
-        emit("v_mov_b32 %s, 0" % FAIL)
+        # eight compares into eight masks first: a v_cndmask that reads a mask a VALU instruction has just written needs two
+        # wait states (the compiler pads that pair; nothing does inside an asm statement), here seven instructions stand between
         for s in range(K):
-            emit("v_cmp_lt_f64 vcc, s[18:19], %s" % AV(s))
-            emit("v_cndmask_b32 %s, %s, %s, vcc" % (T1, NIB(s), ZERO))
+            emit("v_cmp_lt_f64 %s, s[18:19], %s" % (MASK(s), AV(s)))
+        emit("v_cndmask_b32 %s, %s, %s, %s" % (FAIL, NIB(0), ZERO, MASK(0)))
+        for s in range(1, K):
+            emit("v_cndmask_b32 %s, %s, %s, %s" % (T1, NIB(s), ZERO, MASK(s)))
             emit("v_or_b32 %s, %s, %s" % (FAIL, FAIL, T1))
         emit("v_bfi_b32 %s, %s, %s, %s" % (MOK, FAIL, IU, MOK))
     if EPS_FAST:
@@ -197,23 +200,24 @@ emit("s_branch .Lhmcg_rep_done_%=")
 # ---- rare: some lane's total is not > 0 (every pdf of the step underflowed against its prefix): the uniform law, flagged ----
 for b in (("p", "1", "0") if EPS_FAST else ()):
     emit(".Lhmcg_rep_fail%s_%%=:" % b)
-    emit("v_mov_b32 %s, 0" % FAIL)
     for s in range(K):
-        emit("v_cmp_lt_f64 vcc, s[18:19], %s" % AV(s))       # eps() < pif[t,s]
-        emit("v_cndmask_b32 %s, %s, %s, vcc" % (T1, NIB(s), ZERO))
+        emit("v_cmp_lt_f64 %s, s[18:19], %s" % (MASK(s), AV(s)))   # eps() < pif[t,s]
+    emit("v_cndmask_b32 %s, %s, %s, %s" % (FAIL, NIB(0), ZERO, MASK(0)))
+    for s in range(1, K):
+        emit("v_cndmask_b32 %s, %s, %s, %s" % (T1, NIB(s), ZERO, MASK(s)))
         emit("v_or_b32 %s, %s, %s" % (FAIL, FAIL, T1))
     emit("v_bfi_b32 %s, %s, %s, %s" % (MOK, FAIL, IU, MOK))  # (fail & uniform) | (~fail & idx)
     emit("s_branch .Lhmcg_rep_merged%s_%%=" % b)
 for b in ("p", "1", "0"):
     emit(".Lhmcg_rep_rare%s_%%=:" % b)
     emit("s_and_saveexec_b64 %s, vcc" % MASK(0))
-    for s in range(K):
+    emit("v_add_u32 %s, %%[l], %%[t0]" % TCUR)
+    emit("v_cmp_gt_i32 vcc, %%[T], %s" % TCUR)                # t < T: the window is flagged
+    for s in range(K):                                       # (between the compare and the v_cndmask that reads its vcc)
         emit("v_mov_b32 v%d, 0" % (80 + 2 * s))
         emit("v_mov_b32 v%d, 0x3fc00000" % (81 + 2 * s))      # 1/8
     emit("v_mov_b32 v208, 0")
     emit("v_mov_b32 v209, 0x3ff00000")                       # total = 1
-    emit("v_add_u32 %s, %%[l], %%[t0]" % TCUR)
-    emit("v_cmp_gt_i32 vcc, %%[T], %s" % TCUR)                # t < T: the window is flagged
     emit("v_cndmask_b32 %s, 0, %s, vcc" % (T1, "%[flagv]"))
     emit("v_or_b32 %[st], %[st], " + T1)
     emit("s_mov_b64 exec, %s" % MASK(0))
