@@ -81,27 +81,12 @@ __device__ __forceinline__ uint32_t spread_nibbles(uint32_t x)      // 0x0000dcb
 }
 __device__ __forceinline__ ByteMap bytemap_from_nibbles(uint32_t m) { return ByteMap{spread_nibbles(m & 0xFFFFu), spread_nibbles(m >> 16)}; }
 
-// #{i < N : c[i] <= thr} for a non-decreasing c (cumulative sums of non-negative terms), N <= 7: a three-level bisection
-// -- 3 compares and 8 selects instead of N compare + add-with-carry pairs.  The same predicate as the linear count
-// (Categorical's CDF scan, src/Hmc.jl:481), so the draws do not change.
-template <int N>
-__device__ __forceinline__ int count_le_sorted(const double (&c)[N + 1], double thr)
-{
-    static_assert(N >= 1 && N <= 7, "three levels");
-    constexpr double INF = __builtin_huge_val();
-    auto C = [&](int i) __attribute__((always_inline)) { return i < N ? c[i < N ? i : 0] : INF; };
-    const bool b1 = C(3) <= thr;
-    const double m2 = b1 ? C(5) : C(1);
-    const double lo3 = b1 ? C(4) : C(0), hi3 = b1 ? C(6) : C(2);
-    const bool b2 = m2 <= thr;
-    const double m3 = b2 ? hi3 : lo3;
-    const bool b3 = m3 <= thr;
-    return (b1 ? 4 : 0) + (b2 ? 2 : 0) + (b3 ? 1 : 0);
-}
-
-// The same for K searches at once, level by level: idx[s] = #{i < K-1 : c[s][i] <= thr[s]}.  Written so that the K
-// compares of a level are independent instructions (each into its own condition register) instead of K serial
-// compare -> select chains through VCC.
+// K categorical searches at once: idx[s] = #{i < K-1 : c[s][i] <= thr[s]} for non-decreasing rows c[s] (cumulative sums
+// of non-negative terms), K-1 <= 7.  Each search is a three-level bisection -- 3 compares and 8 selects instead of K-1
+// compare + add-with-carry pairs -- with the same predicate as the linear count (Categorical's CDF scan,
+// src/Hmc.jl:481), so the draws do not change.  Written level by level so that the K compares of a level are
+// independent instructions (each into its own condition register) instead of K serial compare -> select chains
+// through VCC.
 template <int K>
 __device__ __forceinline__ void count_le_sorted_batch(const double (&c)[K][K], const double (&thr)[K], int (&idx)[K])
 {
@@ -859,16 +844,6 @@ __global__ __launch_bounds__(NT) void gibbs_sweeps_kernel_big(const KernelParams
         const bool do_smooth = SM && kept_sweep && (p.pi_smooth_mean != nullptr || p.pi_filter_mean != nullptr || p.pi_smooth_draws != nullptr);
         const int dk = SIG ? kept_index(p, sweep) : sweep - p.burnin_s;      // kept-draw index (meaningful when kept_sweep)
         (void)dk;
-#ifdef HMCG_BIG_NSC
-        constexpr int NSC = K == 8 ? HMCG_BIG_NSC : 0;     // the first NSC columns of A live in scalar registers for the whole phase
-#else
-        constexpr int NSC = 0;
-#endif
-        double a_sc[NSC > 0 ? NSC : 1][K];
-#pragma unroll
-        for (int s = 0; s < NSC; ++s)
-#pragma unroll
-            for (int k = 0; k < K; ++k) a_sc[s][k] = uniform_f64(Atp[s * K + k]);
 #ifndef HMCG_BIG_NO_ASM                            // (-DHMCG_BIG_NO_ASM: the C++ loop everywhere, for A/B timing)
         constexpr bool ASM_PRODUCT = K == 8 && !SM;
 #else
@@ -892,11 +867,7 @@ __global__ __launch_bounds__(NT) void gibbs_sweeps_kernel_big(const KernelParams
                 // each other), the dependent operation follows as the next group -- written as plain loops the scheduler
                 // keeps each value's chain together and interleaves only two of them (measured: 6.8 ticks per instruction)
 #define HMCG_EACH for (int g = 0; g < G; ++g) _Pragma("unroll") for (int s = 0; s < K; ++s)
-#ifdef HMCG_PDF_NOSB
-#define HMCG_SB
-#else
 #define HMCG_SB __builtin_amdgcn_sched_barrier(0)
-#endif
                 for (int l0 = 0; l0 < L; l0 += G) {
                     double x[G][K], nn[G][K], tj[G][K], fv[G][K], r[G][K], pp[G][K], yv[G];
                     int ni[G][K];
@@ -1003,11 +974,7 @@ __global__ __launch_bounds__(NT) void gibbs_sweeps_kernel_big(const KernelParams
             const uint32_t asm_voff = (uint32_t)threadIdx.x * 16u;
             const uint32_t asm_lds = (uint32_t)(uintptr_t)(lds_cdouble*)&th.A[0][0];
             int asm_l, asm_t, asm_u;
-#if defined(HMCG_BIG_ASM_TESTINC)                 // (timing experiments of tools/gen_product_asm.py --test-*: wrong results)
-#include HMCG_BIG_ASM_TESTINC
-#else
 #include "product_asm_k8.inc"
-#endif
             (void)asm_l; (void)asm_t; (void)asm_u;
             rescale_pow2<KK>(Q);
         } else {
@@ -1021,11 +988,7 @@ __global__ __launch_bounds__(NT) void gibbs_sweeps_kernel_big(const KernelParams
             // LDS (wave-uniform address: a broadcast read), the block's rows against it; every column is read once per block
             // (twice per step for K = 8: 64 broadcast reads instead of 32, far from loading the LDS pipe -- a two-rows form
             // that read A four times per step had been LDS-bound).
-#ifdef HMCG_BIG_RB
-            constexpr int RB = HMCG_BIG_RB;
-#else
             constexpr int RB = 4;
-#endif
             for (int l = 0; l < L; ++l) {
                 asm volatile("" ::: "memory");       // keep the A columns as per-step LDS reads (hoisting all 64 would spill)
                 if constexpr (SM) {
@@ -1048,7 +1011,7 @@ __global__ __launch_bounds__(NT) void gibbs_sweeps_kernel_big(const KernelParams
                     for (int s = 0; s < K; ++s) {
                         double a[K];
 #pragma unroll
-                        for (int k = 0; k < K; ++k) a[k] = s < NSC ? a_sc[s < NSC ? s : 0][k] : Atp[s * K + k];
+                        for (int k = 0; k < K; ++k) a[k] = Atp[s * K + k];
 #pragma unroll
                         for (int rr = 0; rr < RB; ++rr) {
                             if (r0 + rr < K) {
@@ -1083,15 +1046,6 @@ __global__ __launch_bounds__(NT) void gibbs_sweeps_kernel_big(const KernelParams
         scan_level_rowwise<K, DPP_ROW_SHR4, 0xF>(Q, N);
         scan_level_rowwise<K, DPP_ROW_SHR8, 0xF>(N, Q);
         rescale_pow2<KK>(Q);
-#ifdef HMCG_BIG_FULL_SCAN                         // (A/B: the two upper scan levels as full K x K products in every lane, as until round 4)
-        scan_level_rowwise<K, DPP_ROW_BCAST15, 0xA>(Q, N);
-        scan_level_rowwise<K, DPP_ROW_BCAST31, 0xC>(N, Q);
-        rescale_pow2<KK>(Q);
-        if (lane == 63) {
-#pragma unroll
-            for (int i = 0; i < KK; ++i) sh.wtot[wave][i] = Q[i];
-        }
-#else
         // The scan stops at the 16-lane rows (four DPP levels).  What the two upper levels produced -- 2 x K^3 multiply-adds in
         // EVERY lane -- is needed in two much smaller forms only: the wave's total W = R0 R1 R2 R3 (for the later waves), and
         // for the lanes of row j the vector u_j = v R0 ... R_{j-1} that enters the row (v: what enters the wave).  Both are
@@ -1125,7 +1079,6 @@ __global__ __launch_bounds__(NT) void gibbs_sweeps_kernel_big(const KernelParams
             pe = coop(sh.ptmp[wave][1], sh.rtot[wave][3]);
             if (evalid) sh.wtot[wave][er * K + ec] = pe;
         }
-#endif
         STAMP(5);
         __syncthreads();                                                     // Bc
         STAMP(6);
@@ -1136,30 +1089,10 @@ __global__ __launch_bounds__(NT) void gibbs_sweeps_kernel_big(const KernelParams
             // rho' W_0 ... W_{wave-1} is the same in every lane, and the last wave's three dependent products stand between every
             // other wave and barrier Bd.  As 64 redundant K x K vector-matrix products each was 64 FMAs behind 32 LDS reads
             // (~1 k ticks a step); cooperatively -- lane c of every 8-lane group carries entry c, reads column c of the total
-            // (K reads), gets the K entries of the vector by lane shuffles -- a step is K FMAs.  Same sums in the same order.
+            // (K reads), gets the K entries of the vector from the other lanes of its group -- a step is K FMAs.  Same sums in
+            // the same order.
             const int c8 = lane & 7, g8 = lane & ~7;
             const int cc = c8 < K ? c8 : 0;
-#ifdef HMCG_BIG_SHFL_CHAIN                            // (A/B: the vector's entries fetched by eight lane shuffles a step, as until round 4)
-            double vc = th.rho[cc];
-            for (int ww = 0; ww < wave_u; ++ww) {
-                double col[K];
-#pragma unroll
-                for (int r = 0; r < K; ++r) col[r] = sh.wtot[ww][r * K + cc];
-                double acc = __shfl(vc, g8, 64) * col[0];
-#pragma unroll
-                for (int r = 1; r < K; ++r) acc = fma(__shfl(vc, g8 | r, 64), col[r], acc);
-                vc = acc;
-            }
-            auto row_step = [&](int j) __attribute__((always_inline)) {
-                double col[K];
-#pragma unroll
-                for (int r = 0; r < K; ++r) col[r] = sh.rtot[wave_u][j][r * K + cc];
-                double acc = __shfl(vc, g8, 64) * col[0];
-#pragma unroll
-                for (int r = 1; r < K; ++r) acc = fma(__shfl(vc, g8 | r, 64), col[r], acc);
-                vc = acc;
-            };
-#else
             // A step v <- v M with lane c of every eight owning entry c: the entries of v reach the lane by DPP ROTATIONS of the
             // 16-lane row (both halves of a row hold the same eight entries, so row_ror:k hands lane c entry (c - k) mod 8) -- 14
             // vector moves and 8 multiply-adds per step, nothing through LDS on the dependent chain (the 8 lane shuffles a step
@@ -1184,9 +1117,8 @@ __global__ __launch_bounds__(NT) void gibbs_sweeps_kernel_big(const KernelParams
                 vc = acc;
             };
             for (int ww = 0; ww < wave_u; ++ww) coop_step(sh.wtot[ww]);
+            // (a lambda of its own: coop_step called in place below compiles to different code)
             auto row_step = [&](int j) __attribute__((always_inline)) { coop_step(sh.rtot[wave_u][j]); };
-#endif
-#ifndef HMCG_BIG_FULL_SCAN
             // u_j for the lanes of row j: three more steps of the same kind over this wave's row totals; a lane keeps the
             // vector of its own row
             {
@@ -1199,7 +1131,6 @@ __global__ __launch_bounds__(NT) void gibbs_sweeps_kernel_big(const KernelParams
                 }
                 vc = vrow;
             }
-#endif
 #pragma unroll
             for (int s = 0; s < K; ++s) av[s] = __shfl(vc, g8 | s, 64);
         }
@@ -1210,11 +1141,7 @@ __global__ __launch_bounds__(NT) void gibbs_sweeps_kernel_big(const KernelParams
                 double acc = 0.0;
 #pragma unroll
                 for (int r = 0; r < K; ++r)
-#ifdef HMCG_BIG_FULL_SCAN
-                    acc = fma(av[r], dpp_f64<DPP_WAVE_SHR1, 0xF>((r == s) ? 1.0 : 0.0, Q[r * K + s]), acc);
-#else
                     acc = fma(av[r], dpp_f64<DPP_ROW_SHR1, 0xF>((r == s) ? 1.0 : 0.0, Q[r * K + s]), acc);   // the row's exclusive prefix
-#endif
                 nv[s] = acc;
             }
             rescale_pow2<K>(nv);
@@ -1284,12 +1211,8 @@ __global__ __launch_bounds__(NT) void gibbs_sweeps_kernel_big(const KernelParams
             double fnext[K];                     // pdfs of the step ahead, on their way from the scratch
 #pragma unroll
             for (int s = 0; s < K; ++s) fnext[s] = fscr[fslot(0, s, threadIdx.x)];
-#ifdef HMCG_BIG_NSC_REPLAY
-            constexpr int NRES = NSC > 0 ? 0 : 2, NSR = NSC;      // the scalar columns serve the replay as well
-#else
-            constexpr int NRES = 2, NSR = 0;     // the first columns of A stay in registers: the step's first chains need not wait for LDS
-#endif
-            double a_first[NRES > 0 ? NRES : 1][K];
+            constexpr int NRES = 2;              // the first columns of A stay in registers: the step's first chains need not wait for LDS
+            double a_first[NRES][K];
 #pragma unroll
             for (int s = 0; s < NRES; ++s)
 #pragma unroll
@@ -1315,7 +1238,7 @@ __global__ __launch_bounds__(NT) void gibbs_sweeps_kernel_big(const KernelParams
                     for (int s = 0; s < K; ++s) {
                         double a[K];
 #pragma unroll
-                        for (int k = 0; k < K; ++k) a[k] = s < NSR ? a_sc[s < NSR ? s : 0][k] : (s < NRES ? a_first[s < NRES ? s : 0][k] : Atp[s * K + k]);
+                        for (int k = 0; k < K; ++k) a[k] = s < NRES ? a_first[s < NRES ? s : 0][k] : Atp[s * K + k];
                         double acc = av[0] * a[0];
                         cum[s][0] = acc;
 #pragma unroll

@@ -311,33 +311,6 @@ __device__ __forceinline__ double mt_try(double d, double c, double x, double lo
     return ok ? d * v : -1.0;
 }
 
-// ------------------------------------------------------------- math ------
-
-// exp(x) for x <= ~0 (emission pdfs): Cody-Waite reduction by ln2 and a degree-13 Taylor
-// polynomial on |r| <= ln2/2 (truncation < 2e-17), scaled by ldexp (gradual underflow).
-__device__ __forceinline__ double exp_fast(double x)
-{
-    x = fmax(x, -746.0);                       // exp(-746) rounds to 0 in binary64
-    const double n = rint(x * 1.4426950408889634);
-    double r = fma(-n, 6.93147180369123816490e-01, x);
-    r = fma(-n, 1.90821492927058770002e-10, r);
-    double p = 1.0 / 6227020800.0;
-    p = fma(p, r, 1.0 / 479001600.0);
-    p = fma(p, r, 1.0 / 39916800.0);
-    p = fma(p, r, 1.0 / 3628800.0);
-    p = fma(p, r, 1.0 / 362880.0);
-    p = fma(p, r, 1.0 / 40320.0);
-    p = fma(p, r, 1.0 / 5040.0);
-    p = fma(p, r, 1.0 / 720.0);
-    p = fma(p, r, 1.0 / 120.0);
-    p = fma(p, r, 1.0 / 24.0);
-    p = fma(p, r, 1.0 / 6.0);
-    p = fma(p, r, 0.5);
-    p = fma(p, r, 1.0);
-    p = fma(p, r, 1.0);
-    return ldexp(p, (int)n);
-}
-
 // ------------------------------------------------------- DPP helpers -----
 constexpr int DPP_ROW_SHR1 = 0x111, DPP_ROW_SHR2 = 0x112, DPP_ROW_SHR4 = 0x114, DPP_ROW_SHR8 = 0x118;
 constexpr int DPP_WAVE_SHR1 = 0x138, DPP_ROW_BCAST15 = 0x142, DPP_ROW_BCAST31 = 0x143;
@@ -640,18 +613,6 @@ __device__ __forceinline__ uint32_t map_const(int v)
     for (int s = 0; s < K; ++s) m |= (uint32_t)v << (4 * s);
     return m;
 }
-// (a o b)[s] = a[b[s]] : apply b first, then a.
-template <int K>
-__device__ __forceinline__ uint32_t map_compose(uint32_t a, uint32_t b)
-{
-    uint32_t m = 0;
-#pragma unroll
-    for (int s = 0; s < K; ++s) {
-        const uint32_t bs = (b >> (4 * s)) & 15u;
-        m |= ((a >> (4u * bs)) & 15u) << (4 * s);
-    }
-    return m;
-}
 __device__ __forceinline__ int map_apply(uint32_t m, int s) { return (int)((m >> (4 * s)) & 15u); }
 
 // Byte-per-entry state maps for K <= 4 (the register-resident kernel): entry s of map m is byte s.  Composition is ONE
@@ -931,13 +892,9 @@ void gibbs_sweeps_kernel(const KernelParams p)
         }
     }
     const int w = w_;
-#ifdef HMCG_VECTOR_WAVE                                     // (A/B only: the wave id as a per-lane value, as until round 3)
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-#else
     // the wave id is a SCALAR: everything that depends on it branches (s_cbranch_scc) instead of opening an exec-masked
     // region -- fewer lane masks parked in SGPRs, fewer join blocks (the places the allocator fault of DESIGN 5a strikes)
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-#endif
     const int T = p.T[w];
     const int t0 = tid * L;                                // helper threads: t0 >= NT*L >= T, so they own no step
     const int owner = (T - 1) / L, l_last = (T - 1) % L;   // thread and slot that hold the last time step

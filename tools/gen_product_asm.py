@@ -31,11 +31,8 @@ s[36:99] A rows 0..3.
 import os
 import sys
 
-TEST_NOLDS = "--test-nolds" in sys.argv        # timing experiments only (wrong results): no LDS reads / no scratch loads in the loop
-TEST_NOFV = "--test-nofv" in sys.argv
-IN_LOOP = False
 K = 8
-NSR = int(os.environ.get("PRODUCT_NSR", "4"))      # rows of A held in scalar registers (s[SBASE : SBASE + 16 NSR)); 4 measured best
+NSR = 4                                         # rows of A held in scalar registers (s[SBASE : SBASE + 16 NSR)); 4 measured best
 SBASE = 100 - 16 * NSR
 QREG = lambda i: "v[%d:%d]" % (2 * i, 2 * i + 1)
 ACC = lambda j: "v[%d:%d]" % (128 + 2 * j, 129 + 2 * j)
@@ -50,8 +47,6 @@ emit = out.append
 
 def read_row(buf, k):
     """four broadcast ds_read_b128: row k of A (64 bytes) into buffer buf"""
-    if TEST_NOLDS and IN_LOOP:
-        return
     for h in range(4):
         emit("ds_read_b128 v[%d:%d], %%[lds] offset:%d" % (192 + 16 * buf + 4 * h, 195 + 16 * buf + 4 * h, 64 * k + 16 * h))
 
@@ -61,8 +56,6 @@ def load_f(step, dst4):
     (the scratch is [L][4][NT][2] doubles: 16384 bytes per step), into the register quads dst4(pair).
     VOFF holds the lane's byte offset of the last step loaded and advances only while `step` < L: the loads behind the
     last step re-read it (they are issued unconditionally so that the vmcnt bookkeeping is static; nothing reads them)."""
-    if TEST_NOFV and IN_LOOP:
-        return
     if step != 0:                                            # (step 0: VOFF is the lane's offset of step 0 already)
         emit("s_cmp_lt_u32 %s, %%[L]" % step)
         emit("s_cselect_b32 %[t], 0x4000, 0")
@@ -174,7 +167,6 @@ def step_body(slot):
 
 
 emit(".Lhmcg_prod_loop_%=:")
-IN_LOOP = True
 step_body(0)
 emit("s_cbranch_scc1 .Lhmcg_prod_loop_%=")
 emit(".Lhmcg_prod_done_%=:")
@@ -182,8 +174,6 @@ emit("s_waitcnt vmcnt(0) lgkmcnt(0)")                        # the ring's loads 
 emit("s_nop 4")                                              # ... nothing of ours is in flight when the compiler's code resumes
 
 path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "hmc.jl_amd", "csrc", "product_asm_k8.inc")
-if TEST_NOLDS or TEST_NOFV:
-    path = "/tmp/t/product_asm_test.inc"
 with open(path, "w") as f:
     f.write("// GENERATED by tools/gen_product_asm.py -- do not edit.  The K = 8 chunk-product loop as one asm statement.\n")
     f.write("// Operands: outputs Q[0..63] bound to v[0:127]; %[l], %[t] scalar temporaries; inputs %[L] (steps), %[fb] (scratch\n")

@@ -25,7 +25,6 @@ v[200:207] idx accumulators, v208.. temporaries; s[36:99] A rows 0..3, s[20:35] 
 """
 import os
 import sys
-EPS_FAST = os.environ.get("REPLAY_EPS_FAST", "0") == "1"     # min-of-eight fast path for the eps() guard: measured 0.8 % SLOWER (a dependent chain of seven v_min)
 K = 8
 SBASE = 36
 AV = lambda r: "v[%d:%d]" % (2 * r, 2 * r + 1)
@@ -116,27 +115,18 @@ def step_body(b, tag, incm):
     emit("v_fma_f64 %s, %s, %s, %s" % (INV, TMP, INV, INV))
     for s in range(K):
         emit("v_mul_f64 %s, %s, %s" % (AV(s), NV(s), INV))   # pif[t,s]
-    # guard (:472-480): an entry whose pif[t,s] is not > eps() takes the uniform draw.  Almost never: the smallest of the
-    # eight against eps() first (no NaN can be here: a NaN anywhere makes the total NaN, which took the rare path above), and
-    # the per-state masks only in a wave where some lane fails
-    if EPS_FAST:
-        emit("v_min_f64 %s, %s, %s" % (TMP, AV(0), AV(1)))
-        for s in range(2, K):
-            emit("v_min_f64 %s, %s, %s" % (TMP, TMP, AV(s)))
-        emit("v_cmp_nlt_f64 vcc, s[18:19], %s" % TMP)        # !(eps < min): some entry of this lane fails
-        emit("s_cbranch_vccnz .Lhmcg_rep_fail%s_%%=" % tag)
-    else:
-        # eight compares into eight masks first: a v_cndmask that reads a mask a VALU instruction has just written needs two
-        # wait states (the compiler pads that pair; nothing does inside an asm statement), here seven instructions stand between
-        for s in range(K):
-            emit("v_cmp_lt_f64 %s, s[18:19], %s" % (MASK(s), AV(s)))
-        emit("v_cndmask_b32 %s, %s, %s, %s" % (FAIL, NIB(0), ZERO, MASK(0)))
-        for s in range(1, K):
-            emit("v_cndmask_b32 %s, %s, %s, %s" % (T1, NIB(s), ZERO, MASK(s)))
-            emit("v_or_b32 %s, %s, %s" % (FAIL, FAIL, T1))
-        emit("v_bfi_b32 %s, %s, %s, %s" % (MOK, FAIL, IU, MOK))
-    if EPS_FAST:
-        emit(".Lhmcg_rep_merged%s_%%=:" % tag)
+    # guard (:472-480): an entry whose pif[t,s] is not > eps() takes the uniform draw, in every step and without a branch
+    # (testing the smallest of the eight first and branching to the masks only where some lane fails was measured 0.8 %
+    # slower: a dependent chain of seven v_min).  Eight compares into eight masks first: a v_cndmask that reads a mask a
+    # VALU instruction has just written needs two wait states (the compiler pads that pair; nothing does inside an asm
+    # statement), here seven instructions stand between
+    for s in range(K):
+        emit("v_cmp_lt_f64 %s, s[18:19], %s" % (MASK(s), AV(s)))     # eps() < pif[t,s]
+    emit("v_cndmask_b32 %s, %s, %s, %s" % (FAIL, NIB(0), ZERO, MASK(0)))
+    for s in range(1, K):
+        emit("v_cndmask_b32 %s, %s, %s, %s" % (T1, NIB(s), ZERO, MASK(s)))
+        emit("v_or_b32 %s, %s, %s" % (FAIL, FAIL, T1))
+    emit("v_bfi_b32 %s, %s, %s, %s" % (MOK, FAIL, IU, MOK))  # (fail & uniform) | (~fail & idx)
     emit("ds_write_b32 %s, %s" % (AM, MOK))                  # g_{t-1}
     emit("v_add_u32 %s, %s, %s" % (AM, incm, AM))
     # pif[T-1,:] -> th.pi_end, by the lane that owns step T-1 (only its wave takes this path)
@@ -198,16 +188,6 @@ step_body(0, "0", "4")
 emit("s_cbranch_scc1 .Lhmcg_rep_loop_%=")
 emit("s_branch .Lhmcg_rep_done_%=")
 # ---- rare: some lane's total is not > 0 (every pdf of the step underflowed against its prefix): the uniform law, flagged ----
-for b in (("p", "1", "0") if EPS_FAST else ()):
-    emit(".Lhmcg_rep_fail%s_%%=:" % b)
-    for s in range(K):
-        emit("v_cmp_lt_f64 %s, s[18:19], %s" % (MASK(s), AV(s)))   # eps() < pif[t,s]
-    emit("v_cndmask_b32 %s, %s, %s, %s" % (FAIL, NIB(0), ZERO, MASK(0)))
-    for s in range(1, K):
-        emit("v_cndmask_b32 %s, %s, %s, %s" % (T1, NIB(s), ZERO, MASK(s)))
-        emit("v_or_b32 %s, %s, %s" % (FAIL, FAIL, T1))
-    emit("v_bfi_b32 %s, %s, %s, %s" % (MOK, FAIL, IU, MOK))  # (fail & uniform) | (~fail & idx)
-    emit("s_branch .Lhmcg_rep_merged%s_%%=" % b)
 for b in ("p", "1", "0"):
     emit(".Lhmcg_rep_rare%s_%%=:" % b)
     emit("s_and_saveexec_b64 %s, vcc" % MASK(0))
