@@ -10,6 +10,9 @@
 // samples.  The chain state between chunks travels through the same checkpoint block (xstate, sumacc) that
 // HMCG_FLAG_RESUME exposes, so a chunked run is bit-identical to a single launch.
 //
+// What a call runs -- argument rules, kernel variant, length buckets, sweep range -- is decided in plan.hpp (plain C++, checked on the
+// CPU); this unit hands it the tables and the diagnostic overrides (plan_call) and launches what comes back.
+//
 // No CPU compute path exists here: without a HIP device every compute entry returns HMCG_E_NODEVICE.
 #include <hip/hip_runtime.h>
 
@@ -25,9 +28,10 @@
 #include <thread>
 #include <vector>
 
+#include "gibbs_device.hpp"
 #include "host_util.hpp"
 #include "moments.hpp"
-#include "variants.hpp"
+#include "plan.hpp"
 
 namespace {
 
@@ -91,8 +95,9 @@ struct Arena {
     }
 };
 
+using namespace hmcg_host;
+using namespace hmcg_hostutil;
 constexpr int RING = 3;            // chunk buffers in flight (device and pinned)
-constexpr int MAXBUCKET = 8;       // length buckets of one call (steps-per-thread classes 1, 2, 3, 4, 6, 8, 16)
 
 struct DeviceCtx {
     std::mutex mu;                 // serialises calls on this device
@@ -212,31 +217,6 @@ void destroy_context(DeviceCtx& c)
     c.device = c.phys = -1;
 }
 
-using namespace hmcg_host;
-using namespace hmcg_hostutil;
-int flavour_of(const Variant& v) { return v.NH > 0 ? H : (v.occ == 2 ? P2 : P1); }
-const VariantGroup* const g_groups[] = { &g_group_k2, &g_group_k3, &g_group_mid, &g_group_k3_l16, &g_group_k4, &g_group_sig, &g_group_smooth, &g_group_sigsmooth };
-
-
-// The variant for (K, longest window, threads per window, path): the fewest steps per thread that cover the
-// window, then the flavour -- `force` (>= 0, diagnostics) or the table's preference for the batch size.
-const Variant* pick_variant(int K, int maxT, int nt_req, bool sig, bool smooth, bool small_batch, int force)
-{
-    const int nt = nt_req > 0 ? nt_req : 256;
-    const Variant* best = nullptr;
-    for (const VariantGroup* g : g_groups)
-    for (int i = 0; i < g->n; ++i) {
-        const Variant& v = g->v[i];
-        if (v.K != K || v.NT != nt || v.L * v.NT < maxT || v.sig != sig || v.smooth != smooth) continue;
-        const int want = force >= 0 ? force : (small_batch ? v.pref_small : v.pref_big);
-        const bool better = !best || v.L < best->L ||
-                            (v.L == best->L && flavour_of(v) == want) ||
-                            (v.L == best->L && flavour_of(*best) != want && flavour_of(v) == P1);
-        if (better) best = &v;
-    }
-    return best;
-}
-
 int validate(const hmcg_config* cfg)
 {
     if (!cfg) { set_err("cfg is NULL"); return HMCG_E_BADARG; }
@@ -259,35 +239,7 @@ int validate(const hmcg_config* cfg)
     return 0;
 }
 
-// What runs: the kernel instantiation for this call's shape, chosen once per call.
-// One length bucket of a call: the windows with t_lo <= T <= t_hi run on variant v (its own launch, beside the others).
-// Both bounds are inclusive: the first bucket reaches INT32_MAX, the last starts AT INT32_MIN, so every T lies in exactly one.
-struct Bucket {
-    const Variant* v;
-    int t_lo, t_hi;
-};
-struct Plan {
-    const Variant* v = nullptr;    // register-resident kernel (with buckets: the longest bucket's variant)
-    int nb = 0;                    // > 1: length-bucketed dispatch, longest bucket first
-    Bucket b[MAXBUCKET];
-    const BigVariant* bv = nullptr;
-    int bigL = 0;
-    bool stream = false;           // the LDS-resident kernel's HBM-streaming form (window too long for the CU's LDS)
-    size_t dyn = 0;
-    bool use_sig = false, use_smooth = false;
-    bool needs_pif() const { return bv != nullptr && use_smooth; }   // the LDS-resident smoothing kernel streams pif through pif_final
-    int NT() const { return v ? v->NT : bv->NT; }
-    int L() const { return v ? v->L : bigL; }
-    int NH() const { return v ? v->NH : 0; }
-    // LDS-resident kernel: per-step pdfs handed from the product phase to the replay, [W][L][ceil(K/2)][NT][2] doubles
-    size_t scratch_bytes(int W, int K) const { return bv ? sizeof(double) * (size_t)W * (size_t)bigL * (size_t)(2 * hmcg::big_scratch_pairs(K)) * (size_t)bv->NT : 0; }
-    // streaming form: per window the observations, uniforms, state maps and states of its NT * L steps
-    size_t slab_bytes() const { return stream ? hmcg::stream_slab_bytes((size_t)bv->NT * (size_t)bigL) : 0; }
-    size_t stream_bytes(int W) const { return slab_bytes() * (size_t)W; }
-    const void* fptr() const { return v ? reinterpret_cast<const void*>(v->fn) : reinterpret_cast<const void*>(bv->fn); }
-};
-
-// Static LDS of a kernel instantiation, asked of the runtime once per function (make_plan and fill_timing sit on the call path).
+// Static LDS of a kernel instantiation, asked of the runtime once per function (plan_call and fill_timing sit on the call path).
 size_t static_lds_bytes(const void* fn, size_t fallback)
 {
     static std::mutex mu;
@@ -300,157 +252,44 @@ size_t static_lds_bytes(const void* fn, size_t fallback)
     return fa.sharedSizeBytes;
 }
 
-// The steps-per-thread classes compiled for a path at 256 threads per window, ascending.
-int length_classes(int K, bool sig, bool smooth, int* Ls)
+// What runs: make_plan (plan.hpp) on the library's own tables.  The ONE place that reads the diagnostic switches of the kernel
+// choice, and where the stamps build says that it is one.
+int plan_call(const hmcg_config* cfg, const hmcg_extras* ex, int W, int cu_count, int minT, const HostLengths* hl, Plan* plan)
 {
-    int n = 0;
-    for (const VariantGroup* g : g_groups)
-        for (int i = 0; i < g->n; ++i) {
-            const Variant& v = g->v[i];
-            if (v.K != K || v.NT != 256 || v.sig != sig || v.smooth != smooth) continue;
-            bool seen = false;
-            for (int j = 0; j < n; ++j) seen |= Ls[j] == v.L;
-            if (!seen && n < 16) Ls[n++] = v.L;
-        }
-    std::sort(Ls, Ls + n);
-    return n;
-}
-
-int flavour_code(const char* f) { return !strcmp(f, "h") ? H : (!strcmp(f, "p2") ? P2 : P1); }
-
-// The window lengths of a call as the host entries know them (rows idx[0..n) of T; idx == nullptr: rows 0..n-1).
-struct HostLengths {
-    const int32_t* T = nullptr;
-    const int32_t* idx = nullptr;
-    int n = 0;
-    int at(int i) const { return T[idx ? (size_t)idx[i] : (size_t)i]; }
-};
-
-// Argument checks common to both entries + kernel choice.  W is the number of windows THIS device runs; minT the shortest
-// of them when the caller knows it (0: unknown -- one launch sized for the longest window); hl (host entries) the lengths
-// themselves: classes no window falls in are not launched.
-int make_plan(const hmcg_config* cfg, const hmcg_extras* ex, int W, int cu_count, int minT, const HostLengths* hl, Plan* plan)
-{
-    if (ex && ex->struct_size != (int32_t)sizeof(hmcg_extras)) { set_err("hmcg_extras.struct_size mismatch"); return HMCG_E_BADARG; }
-    const bool resume = (cfg->flags & HMCG_FLAG_RESUME) != 0;
-    if (resume && !(ex && ex->xstate)) { set_err("HMCG_FLAG_RESUME needs extras.xstate"); return HMCG_E_BADARG; }
-    const int maxT = cfg->max_T > 0 ? cfg->max_T : cfg->ldY;
-    const bool use_sig = ex && (ex->sig_range != nullptr);
-    const int n_samples = cfg->n_samples > 1 ? cfg->n_samples : 1;
-    if (!use_sig && (n_samples > 1 || (ex && (ex->sigma_signal || ex->sigvals)))) {
-        set_err("n_samples / sigma_signal / sigvals need extras.sig_range");
-        return HMCG_E_BADARG;
-    }
-    if (!use_sig && (cfg->blend_mask != 0 || (ex && ex->end_pos))) {
-        set_err("blend_mask / end_pos need extras.sig_range");
-        return HMCG_E_BADARG;
-    }
-    if (cfg->blend_mask < 0 || (cfg->H < 31 && (cfg->blend_mask >> cfg->H) != 0)) { set_err("blend_mask has bits beyond H"); return HMCG_E_BADARG; }
-    if (ex && ex->sigvals && ex->nsave_ld < 1) { set_err("sigvals needs nsave_ld >= 1"); return HMCG_E_BADARG; }
-    if (!use_sig && ex && ex->sample_summary) { set_err("sample_summary needs extras.sig_range (without the signal path it is `summary`)"); return HMCG_E_BADARG; }
-    if (ex && ex->corr) {
-        if (use_sig || n_samples > 1 || cfg->H < 1 || cfg->nrun < 2) {
-            set_err("extras.corr: base runs only (no signal path), H >= 1 (the forecast column) and nrun >= 2");
-            return HMCG_E_BADARG;
-        }
-        if (resume || cfg->sweep_base != 0 || (cfg->sweep_count > 0 && cfg->sweep_count < cfg->burnin + cfg->nrun)) {
-            set_err("extras.corr needs the whole run in one call (no RESUME / sweep_base / sweep_count)");
-            return HMCG_E_BADARG;
-        }
-    }
-    const bool use_smooth = ex && (ex->pi_smooth_mean != nullptr || ex->pi_filter_mean != nullptr || ex->pi_smooth_draws != nullptr);
-    if (cfg->sweep_base > n_samples * (cfg->burnin + cfg->nrun)) { set_err("sweep_base beyond the run"); return HMCG_E_BADARG; }
-    // Flavour: helper waves pay off while every window has a CU to itself; with more windows than CUs the capped
-    // plain variant lets two windows share a CU instead (a helped block takes the whole register file).
-    // HMCG_FLAVOUR=p1|p2|h overrides the table (diagnostics, tools/variant_sweep.py).
-    const bool small_batch = W <= cu_count;
-    const char* fenv = diag_env("HMCG_FLAVOUR");
-    const int force = fenv ? flavour_code(fenv) : -1;
-    Plan pl;
-    pl.use_sig = use_sig; pl.use_smooth = use_smooth;
-    // HMCG_FORCE_BIG=1 (diagnostics): the LDS-resident kernel also where a register-resident variant exists
-    if (cfg->K < 5 && !diag_env("HMCG_FORCE_BIG")) pl.v = pick_variant(cfg->K, maxT, cfg->threads_per_window, use_sig, use_smooth, small_batch, force);
-#ifndef HMCG_STAMPS
-    // Length-bucketed dispatch: a batch of ragged windows (the reference's production run: 460 expanding windows of 120..579
-    // months, code/run_hmm.jl:79-109) is cut by the steps-per-thread class each window needs; every class gets its own launch
-    // on its own stream, all of them over the whole grid -- the blocks of the other classes' windows leave at once
-    // (the class bounds in the header of KernelParams::order).  A window then runs on the variant its own length selects, whatever else the call holds:
-    // its result equals that of a call with this window alone, bit for bit.  (HMCG_NO_BUCKETS=1, diagnostics: one launch
-    // sized for the longest window, as before round 4.)
-    if (pl.v && pl.v->NT == 256 && cfg->threads_per_window == 0 && minT > 0 && minT < maxT && !diag_env("HMCG_NO_BUCKETS")) {
-        int Ls[16];
-        const int nL = length_classes(cfg->K, use_sig, use_smooth, Ls);
-        int lo = 0, hi = 0;
-        while (lo < nL && 256 * Ls[lo] < minT) ++lo;
-        while (hi < nL && 256 * Ls[hi] < maxT) ++hi;
-        if (hi < nL && lo < hi) {
-            // classes that are launched, longest first: all of them on the device entry (it does not see T); on the host
-            // entries only those a window falls in (the longest one always: it reports, and flags T > max_T)
-            int keep[16], nk = 0;
-            for (int c = hi; c >= lo; --c) {
-                bool any = !hl || c == hi;
-                const int c_lo = c == 0 ? 0 : 256 * Ls[c - 1], c_hi = 256 * Ls[c];
-                for (int i = 0; hl && i < hl->n && !any; ++i) any = hl->at(i) > c_lo && hl->at(i) <= c_hi;
-                if (any) keep[nk++] = c;
-            }
-            nk = std::min(nk, MAXBUCKET);          // (more classes than slots: the last slot's class takes every shorter window too)
-            const char* bf = diag_env("HMCG_BUCKET_FLAVOURS");          // "h,p2,p2": longest bucket first (diagnostics)
-            for (int j = 0; j < nk; ++j) {
-                int f = force;
-                if (bf && *bf) {
-                    char tok[8] = "";
-                    size_t n = strcspn(bf, ",");
-                    memcpy(tok, bf, std::min(n, sizeof tok - 1));
-                    f = flavour_code(tok);
-                    bf += n + (bf[n] == ',' ? 1 : 0);
-                }
-                // bucket j: windows longer than the next kept class holds, up to what this class holds (a skipped class is
-                // empty, so every window still runs on the smallest class that covers it)
-                const int t_hi = j == 0 ? INT32_MAX : 256 * Ls[keep[j]], t_lo = j == nk - 1 ? INT32_MIN : 256 * Ls[keep[j + 1]] + 1;
-                pl.b[pl.nb++] = Bucket{pick_variant(cfg->K, 256 * Ls[keep[j]], 0, use_sig, use_smooth, small_batch, f), t_lo, t_hi};
-            }
-            if (pl.nb == 1) pl.nb = 0;             // one class after all: a plain single launch
-            pl.v = pl.b[0].v;
-        }
-    }
+    static const VariantGroup* const groups[] = { &g_group_k2, &g_group_k3, &g_group_mid, &g_group_k3_l16, &g_group_k4, &g_group_sig, &g_group_smooth, &g_group_sigsmooth };
+    const KernelTables tab{groups, (int)(sizeof groups / sizeof groups[0]), g_big};
+    PlanOverrides ov;
+    ov.flavour = diag_env("HMCG_FLAVOUR");
+    ov.bucket_flavours = diag_env("HMCG_BUCKET_FLAVOURS");
+    ov.force_big = diag_env("HMCG_FORCE_BIG") != nullptr;
+    ov.no_buckets = diag_env("HMCG_NO_BUCKETS") != nullptr;
+    ov.force_stream = diag_env("HMCG_FORCE_STREAM") != nullptr;
+#ifdef HMCG_STAMPS
+    ov.stamps = true;
 #endif
-    if (!pl.v) {                                       // large K, or a window too long for the register-resident variants
-        auto big = [&](bool stream) { return &(*g_big[use_sig][use_smooth][stream])[cfg->K - BIG_KMIN]; };
-        if (cfg->K >= BIG_KMIN && cfg->K < BIG_KMIN + BIG_NK) {
-            pl.bv = big(false);
-            pl.bigL = (maxT + pl.bv->NT - 1) / pl.bv->NT;
-            pl.dyn = (size_t)pl.bv->NT * pl.bigL * (8 + 8 + 4 + 1) + 16;
-            // dynamic + static LDS of the instantiation must fit the CU's 160 KiB
-            const size_t stat = static_lds_bytes(reinterpret_cast<const void*>(pl.bv->fn), 48 * 1024);
-            if (cfg->threads_per_window != 0 && cfg->threads_per_window != pl.bv->NT) pl.bv = nullptr;
-            else if (pl.dyn + stat > 160 * 1024 || diag_env("HMCG_FORCE_STREAM")) {
-                // too long for the LDS: the same kernel with its per-step arrays in an HBM scratch (HMCG_FORCE_STREAM: tests)
-                pl.bv = big(true);
-                pl.stream = true;
-                pl.dyn = 16;
-            }
-        }
-    }
-    if (!pl.v && !pl.bv) {
-        set_err("no kernel for K=%d max_T=%d threads_per_window=%d", cfg->K, maxT, cfg->threads_per_window);
-        return HMCG_E_UNSUPPORTED;
-    }
-    *plan = pl;
-    return 0;
+    const auto static_lds = [](const BigVariant& bv) { return static_lds_bytes(reinterpret_cast<const void*>(bv.fn), 48 * 1024); };
+    char msg[160];
+    const int rc = make_plan(tab, *cfg, ex, W, cu_count, minT, hl, ov, static_lds, plan, msg, sizeof msg);
+    if (rc) set_err("%s", msg);
+    return rc;
 }
+
+// The LDS-resident kernel's device scratch: per-step pdfs handed from the product phase to the replay, [W][L][ceil(K/2)][NT][2] doubles
+size_t scratch_bytes(const Plan& pl, int W, int K) { return pl.bv ? sizeof(double) * (size_t)W * (size_t)pl.bigL * (size_t)(2 * hmcg::big_scratch_pairs(K)) * (size_t)pl.bv->NT : 0; }
+// streaming form: per window the observations, uniforms, state maps and states of its NT * L steps
+size_t slab_bytes(const Plan& pl) { return pl.stream ? hmcg::stream_slab_bytes((size_t)pl.bv->NT * (size_t)pl.bigL) : 0; }
+size_t stream_bytes(const Plan& pl, int W) { return slab_bytes(pl) * (size_t)W; }
 
 // Kernel parameters common to every launch of a call; per-launch fields (sweep range, resume, output window) are
 // filled by the caller.  All pointers are device pointers.
 hmcg::KernelParams base_params(const hmcg_config* cfg, int W, const double* dY, const int32_t* dT, const double* dyreal,
-                               int32_t* dstatus, const hmcg_extras* dex, bool use_sig)
+                               int32_t* dstatus, const hmcg_extras* dex, const Plan& pl)
 {
     hmcg::KernelParams p{};
-    const int n_samples = cfg->n_samples > 1 ? cfg->n_samples : 1;
     p.Y = dY; p.T = dT; p.yreal = dyreal;
     p.ldY = cfg->ldY; p.W = W; p.H = cfg->H;
-    p.per_sample = cfg->burnin + cfg->nrun;
-    p.burnin_s = cfg->burnin; p.nrun_s = cfg->nrun; p.n_samples = n_samples; p.nd = n_samples * cfg->nrun;
-    if (p.per_sample < 1) p.per_sample = 1;
+    p.per_sample = pl.sched.per_sample;
+    p.burnin_s = cfg->burnin; p.nrun_s = cfg->nrun; p.n_samples = pl.sched.n_samples; p.nd = pl.sched.nd;
     p.kappa = cfg->kappa;
     for (int h = 0; h < HMCG_MAXH; ++h) p.horizons[h] = h < cfg->H ? cfg->horizons[h] : 0;
     p.seed_lo = (uint32_t)cfg->seed; p.seed_hi = (uint32_t)(cfg->seed >> 32); p.window_base = cfg->window_base;
@@ -463,7 +302,7 @@ hmcg::KernelParams base_params(const hmcg_config* cfg, int W, const double* dY, 
         p.sigvals = dex->sigvals; p.nsave_ld = dex->nsave_ld;
         p.x_init = dex->x_init; p.x_final = dex->x_final; p.pif_final = dex->pif_final; p.xstate = dex->xstate;
         p.sumacc = dex->sumacc; p.window_ids = dex->window_ids;
-        if (use_sig) { p.end_pos = dex->end_pos; p.blend_mask = cfg->blend_mask; p.sample_summary = dex->sample_summary; }
+        if (pl.use_sig) { p.end_pos = dex->end_pos; p.blend_mask = cfg->blend_mask; p.sample_summary = dex->sample_summary; }
     }
     return p;
 }
@@ -631,7 +470,7 @@ int launch_device(DeviceCtx& c, const hmcg_config* cfg, const double* dY, const 
 {
     if (!dY || !dT || !dstatus) { set_err("Y, T and status are required"); return HMCG_E_BADARG; }
     Plan pl;
-    int rc = make_plan(cfg, ex, cfg->W, c.cu_count, cfg->min_T, nullptr, &pl);
+    int rc = plan_call(cfg, ex, cfg->W, c.cu_count, cfg->min_T, nullptr, &pl);
     if (rc) return rc;
     if (pl.needs_pif() && !(ex && ex->pif_final)) {
         set_err("pi_smooth_mean / pi_filter_mean for K >= 5 or windows beyond the register-resident kernels need extras.pif_final "
@@ -643,13 +482,9 @@ int launch_device(DeviceCtx& c, const hmcg_config* cfg, const double* dY, const 
         return HMCG_E_BADARG;
     }
     const bool resume = (cfg->flags & HMCG_FLAG_RESUME) != 0;
-    hmcg::KernelParams p = base_params(cfg, cfg->W, dY, dT, dyreal, dstatus, ex, pl.use_sig);
-    const int total_sweeps = p.n_samples * (cfg->burnin + cfg->nrun);
-    p.sweep_begin = cfg->sweep_base;
-    p.sweep_end = total_sweeps;
-    if (cfg->sweep_count > 0 && cfg->sweep_base + cfg->sweep_count < p.sweep_end) p.sweep_end = cfg->sweep_base + cfg->sweep_count;
+    hmcg::KernelParams p = base_params(cfg, cfg->W, dY, dT, dyreal, dstatus, ex, pl);
+    p.sweep_begin = pl.sched.sweep_begin; p.sweep_end = pl.sched.sweep_end; p.final_launch = pl.sched.final_launch;
     p.resume = resume ? 1 : 0;
-    p.final_launch = (p.sweep_end == total_sweeps) ? 1 : 0;
     p.mu = dmu; p.sig2 = dsig2; p.A = dA; p.pi_end = dpi_end; p.fcast = dfcast; p.summary = dsummary;
     p.nd_ld = p.nd; p.draw_off = 0;
 
@@ -666,11 +501,11 @@ int launch_device(DeviceCtx& c, const hmcg_config* cfg, const double* dY, const 
     }
     if (pl.bv) {
         HIP_TRY(hipFuncSetAttribute(pl.fptr(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.dyn));
-        const size_t fbytes = (pl.scratch_bytes(cfg->W, cfg->K) + 255) & ~(size_t)255;
-        const size_t sbytes = fbytes + pl.stream_bytes(cfg->W);
+        const size_t fbytes = (scratch_bytes(pl, cfg->W, cfg->K) + 255) & ~(size_t)255;
+        const size_t sbytes = fbytes + stream_bytes(pl, cfg->W);
         if ((rc = grow_shared(c, c.scr, sbytes))) return rc;
         p.fscr = reinterpret_cast<double*>(c.scr.base);
-        if (pl.stream) { p.sscr = reinterpret_cast<uint8_t*>(c.scr.base + fbytes); p.stream_stride = (int64_t)pl.slab_bytes(); }
+        if (pl.stream) { p.sscr = reinterpret_cast<uint8_t*>(c.scr.base + fbytes); p.stream_stride = (int64_t)slab_bytes(pl); }
     }
     if (timing) HIP_TRY(hipEventRecord(c.ev0, stream));
 #ifdef HMCG_STAMPS
@@ -731,7 +566,6 @@ struct HostCall {
     size_t ncols = 0;
     bool stream_draws = false, copy_out = false, want_corr = false;
     long long nd_total = 0;        // kept draws per window over the whole run
-    int total_sweeps = 0, se = 0;
     std::vector<Chunk> chunks;
 
     BufTable bt{};
@@ -767,13 +601,13 @@ struct HostCall {
             if (t >= 2 && (minT == 0 || t < minT)) minT = t;
         }
         const HostLengths hl{h.T, idx, n};
-        int rc = make_plan(cfg, h.ex, n, c.cu_count, minT, h.T ? &hl : nullptr, &pl);
+        int rc = plan_call(cfg, h.ex, n, c.cu_count, minT, h.T ? &hl : nullptr, &pl);
         if (rc) return rc;
         if (!h.Y || !h.T) { set_err("Y and T are required"); return HMCG_E_BADARG; }
         const hmcg_extras* ex = h.ex;
         const size_t K = (size_t)cfg->K, ld = (size_t)cfg->ldY, H = (size_t)cfg->H, N = (size_t)n;
-        const int n_samples = cfg->n_samples > 1 ? cfg->n_samples : 1;
-        nd_total = (long long)n_samples * cfg->nrun;
+        const SweepSchedule& sch = pl.sched;
+        nd_total = sch.nd;
         // (the sixth group, extras.pi_smooth_draws, is K * ldY columns wide: samples.pib[Nrun, N, D] of every window)
         const Col all[6] = { {h.mu, K, 0}, {h.sig2, K, 0}, {h.A, K * K, 0}, {h.pi_end, K, 0}, {h.fcast, 2 * H, 0},
                              {ex ? ex->pi_smooth_draws : nullptr, K * ld, 0} };
@@ -786,11 +620,6 @@ struct HostCall {
         }
         stream_draws = ncols > 0;
 
-        total_sweeps = n_samples * (cfg->burnin + cfg->nrun);
-        const int sb = cfg->sweep_base;
-        se = total_sweeps;
-        if (cfg->sweep_count > 0 && sb + cfg->sweep_count < se) se = sb + cfg->sweep_count;
-        const int per = std::max(1, cfg->burnin + cfg->nrun);
         // chunk capacity: the ring of RING chunk buffers stays within ~1 GiB of device memory (and as much pinned memory)
         long long cap = nd_total > 0 ? nd_total : 1;
         if (stream_draws) {
@@ -799,7 +628,7 @@ struct HostCall {
         }
         if (const char* cenv = diag_env("HMCG_CHUNK_DRAWS")) { const long long v = atoll(cenv); if (v > 0) cap = std::min(cap, v); }
         const bool one_chunk_env = diag_env("HMCG_NO_CHUNKS") != nullptr;           // diagnostics: one launch, as the device entry
-        chunks = plan_chunks(sb, se, per, cfg->burnin, cfg->nrun, one_chunk_env ? (1LL << 40) : cap, stream_draws && !one_chunk_env,
+        chunks = plan_chunks(sch.sweep_begin, sch.sweep_end, sch.per_sample, cfg->burnin, cfg->nrun, one_chunk_env ? (1LL << 40) : cap, stream_draws && !one_chunk_env,
                              diag_env("HMCG_CHUNK_FLOOR_DIV"), diag_env("HMCG_CHUNK_KEEP"));
         return 0;
     }
@@ -810,7 +639,7 @@ struct HostCall {
     int lay_out()
     {
         const hmcg_extras* ex = h.ex;
-        const bool need_ckpt = chunks.size() > 1 || (cfg->flags & HMCG_FLAG_RESUME) || (ex && (ex->xstate || ex->sumacc)) || se < total_sweeps;
+        const bool need_ckpt = chunks.size() > 1 || (cfg->flags & HMCG_FLAG_RESUME) || (ex && (ex->xstate || ex->sumacc)) || !pl.sched.final_launch;
         bt = host_buffers(*cfg, h, n, need_ckpt, pl.needs_pif(), hmcg_host::moments_stride(cfg->K));
         long long chunk_max = 0;
         for (const Chunk& ch : chunks) chunk_max = std::max(chunk_max, ch.d1 - ch.d0);
@@ -818,8 +647,8 @@ struct HostCall {
         const int nring = stream_draws ? (int)std::min<size_t>(RING, chunks.size()) : 0;
         for (int r = 0; r < nring; ++r) o_dchunk[r] = bt.dev.add(chunk_bytes);
         const size_t o_dord = pl.nb > 1 ? bt.dev.add(bucket_list_bytes(n)) : 0;
-        const size_t o_dfs = pl.bv ? bt.dev.add(pl.scratch_bytes(n, cfg->K)) : 0;
-        const size_t o_dstr = pl.stream ? bt.dev.add(pl.stream_bytes(n)) : 0;
+        const size_t o_dfs = pl.bv ? bt.dev.add(scratch_bytes(pl, n, cfg->K)) : 0;
+        const size_t o_dstr = pl.stream ? bt.dev.add(stream_bytes(pl, n)) : 0;
         o_pst0 = bt.pin.add(4 * (size_t)n);      // status words as they stand after the first launch: which windows were skipped
         for (int r = 0; r < nring; ++r) o_pchunk[r] = bt.pin.add(chunk_bytes);
         if (c.dev.ensure(bt.dev.total) || c.pin.ensure(bt.pin.total)) {
@@ -830,10 +659,10 @@ struct HostCall {
         P = c.pin.base;
         DevSlots ds = device_slots(bt, D);
         if (ds.ex.sigvals) ds.ex.nsave_ld = ex->nsave_ld;
-        base = base_params(cfg, n, ds.Y, ds.T, ds.yreal, ds.status, &ds.ex, pl.use_sig);
+        base = base_params(cfg, n, ds.Y, ds.T, ds.yreal, ds.status, &ds.ex, pl);
         base.summary = ds.summary;
         if (pl.bv) base.fscr = reinterpret_cast<double*>(D + o_dfs);
-        if (pl.stream) { base.sscr = reinterpret_cast<uint8_t*>(D + o_dstr); base.stream_stride = (int64_t)pl.slab_bytes(); }
+        if (pl.stream) { base.sscr = reinterpret_cast<uint8_t*>(D + o_dstr); base.stream_stride = (int64_t)slab_bytes(pl); }
         if (pl.nb > 1) dord = reinterpret_cast<int32_t*>(D + o_dord);
         dmom = ds.mom;
         dcorr = ds.ex.corr;
@@ -925,7 +754,7 @@ struct HostCall {
         hmcg::KernelParams p = base;
         p.sweep_begin = ch.s0; p.sweep_end = ch.s1;
         p.resume = (bt.resume || cidx > 0) ? 1 : 0;
-        p.final_launch = (ch.s1 == total_sweeps) ? 1 : 0;
+        p.final_launch = (ch.s1 == pl.sched.total_sweeps) ? 1 : 0;
         const size_t ndc = (size_t)(ch.d1 - ch.d0), N = (size_t)n;
         p.nd_ld = (int32_t)std::max<size_t>(ndc, 1); p.draw_off = (int32_t)ch.d0;
         // The LAST chunk's draws (1/32 of the run, 1.3 MB at the headline shape) are written by the kernel straight into the

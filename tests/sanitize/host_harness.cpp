@@ -5,6 +5,9 @@
 //   * hmcg_hostutil::partition_windows, plan_chunks -- invariants on random shapes;
 //   * hmcg_hostutil::host_buffers, pack_rows, unpack_rows -- the table of a host-entry call's per-window arrays on random
 //     configurations: the arena layouts' invariants, and pack + unpack against the caller's rows;
+//   * hmcg_host::make_plan, sweep_schedule (csrc/plan.hpp) -- which kernel a call runs and how a ragged batch is cut into length
+//     buckets, on tables built here, against a brute-force restatement: every int32_t length in exactly one bucket, the class
+//     and flavour of every launch, the LDS-resident fallback and its LDS fit, every argument rule's message, the sweep range;
 //   * hmcg_csv.cpp -- hmcg_format_float, hmcg_write_table_csv and hmcg_save_results_csv with its thread pool.
 // Exits 0 when every check holds; sanitizer reports make it exit non-zero by themselves.
 #include <cmath>
@@ -16,9 +19,11 @@
 #include <sys/stat.h>
 
 #include "../../hmc.jl_amd/csrc/host_util.hpp"
+#include "../../hmc.jl_amd/csrc/plan.hpp"
 #include "../../include/hmcg.h"
 
 using namespace hmcg_hostutil;
+using namespace hmcg_host;
 
 #define CHECK(c) do { if (!(c)) { fprintf(stderr, "CHECK failed: %s (%s:%d)\n", #c, __FILE__, __LINE__); return 1; } } while (0)
 
@@ -247,6 +252,297 @@ static int buffer_checks()
     return 0;
 }
 
+// ---- plan.hpp: make_plan on tables of the harness's own (null kernel pointers), against a brute-force restatement ----
+static BigVariant g_forms[2][2][2][BIG_NK];       // [sig][smooth][stream][K - BIG_KMIN]
+static const BigForm* const g_fake_big[2][2][2] = { { { &g_forms[0][0][0], &g_forms[0][0][1] }, { &g_forms[0][1][0], &g_forms[0][1][1] } },
+                                                    { { &g_forms[1][0][0], &g_forms[1][0][1] }, { &g_forms[1][1][0], &g_forms[1][1][1] } } };
+
+// one steps-per-thread class at 256 threads in the flavours of `mask` (1: P1, 2: P2, 4: H), as HMCG_V3 lays them out
+static void add_class(std::vector<Variant>& out, int K, int L, bool sig, bool smooth, int pref_small, int pref_big, int mask = 7)
+{
+    if (mask & 1) out.push_back({K, L, 256, nullptr, sig, smooth, 0, 1, pref_small, pref_big});
+    if (mask & 2) out.push_back({K, L, 256, nullptr, sig, smooth, 0, 2, pref_small, pref_big});
+    if (mask & 4) out.push_back({K, L, 256, nullptr, sig, smooth, 4, 2, pref_small, pref_big});
+}
+
+struct FakeTable {
+    std::vector<Variant> rows[2];                  // two groups
+    VariantGroup grp[2];
+    const VariantGroup* groups[2];
+    KernelTables tab()
+    {
+        for (int g = 0; g < 2; ++g) { grp[g] = VariantGroup{rows[g].data(), (int)rows[g].size()}; groups[g] = &grp[g]; }
+        return KernelTables{groups, 2, g_fake_big};
+    }
+};
+
+static const char* const BADARG_SIG = "n_samples / sigma_signal / sigvals need extras.sig_range";
+
+static int plan_rule_checks(const KernelTables& tab)
+{
+    char on;
+    const auto lds = [](const BigVariant&) { return (size_t)0; };
+    hmcg_config good{};
+    good.struct_size = (int32_t)sizeof good; good.W = 4; good.K = 3; good.ldY = 300; good.max_T = 300; good.burnin = 5; good.nrun = 40; good.H = 2;
+    hmcg_extras ex0{};
+    ex0.struct_size = (int32_t)sizeof ex0;
+    // the config and extras of a rule's smallest violation, and the message that goes with HMCG_E_BADARG
+    struct Rule { const char* msg; std::function<void(hmcg_config&, hmcg_extras&)> breakit; };
+    const Rule rules[] = {
+        {"hmcg_extras.struct_size mismatch", [&](hmcg_config&, hmcg_extras& e) { e.struct_size = 8; }},
+        {"HMCG_FLAG_RESUME needs extras.xstate", [&](hmcg_config& c, hmcg_extras&) { c.flags = HMCG_FLAG_RESUME; }},
+        {BADARG_SIG, [&](hmcg_config& c, hmcg_extras&) { c.n_samples = 2; }},
+        {BADARG_SIG, [&](hmcg_config&, hmcg_extras& e) { e.sigma_signal = (const double*)&on; }},
+        {BADARG_SIG, [&](hmcg_config&, hmcg_extras& e) { e.sigvals = (double*)&on; e.nsave_ld = 1; }},
+        {"blend_mask / end_pos need extras.sig_range", [&](hmcg_config& c, hmcg_extras&) { c.blend_mask = 1; }},
+        {"blend_mask / end_pos need extras.sig_range", [&](hmcg_config&, hmcg_extras& e) { e.end_pos = (const int32_t*)&on; }},
+        {"blend_mask has bits beyond H", [&](hmcg_config& c, hmcg_extras& e) { e.sig_range = (const int32_t*)&on; c.blend_mask = 4; }},
+        {"blend_mask has bits beyond H", [&](hmcg_config& c, hmcg_extras& e) { e.sig_range = (const int32_t*)&on; c.blend_mask = -1; }},
+        {"sigvals needs nsave_ld >= 1", [&](hmcg_config&, hmcg_extras& e) { e.sig_range = (const int32_t*)&on; e.sigvals = (double*)&on; }},
+        {"sample_summary needs extras.sig_range (without the signal path it is `summary`)", [&](hmcg_config&, hmcg_extras& e) { e.sample_summary = (double*)&on; }},
+        {"extras.corr: base runs only (no signal path), H >= 1 (the forecast column) and nrun >= 2", [&](hmcg_config&, hmcg_extras& e) { e.corr = (double*)&on; e.sig_range = (const int32_t*)&on; }},
+        {"extras.corr: base runs only (no signal path), H >= 1 (the forecast column) and nrun >= 2", [&](hmcg_config& c, hmcg_extras& e) { e.corr = (double*)&on; c.H = 0; }},
+        {"extras.corr: base runs only (no signal path), H >= 1 (the forecast column) and nrun >= 2", [&](hmcg_config& c, hmcg_extras& e) { e.corr = (double*)&on; c.nrun = 1; }},
+        {"extras.corr needs the whole run in one call (no RESUME / sweep_base / sweep_count)", [&](hmcg_config& c, hmcg_extras& e) { e.corr = (double*)&on; c.flags = HMCG_FLAG_RESUME; e.xstate = (uint8_t*)&on; }},
+        {"extras.corr needs the whole run in one call (no RESUME / sweep_base / sweep_count)", [&](hmcg_config& c, hmcg_extras& e) { e.corr = (double*)&on; c.sweep_base = 1; }},
+        {"extras.corr needs the whole run in one call (no RESUME / sweep_base / sweep_count)", [&](hmcg_config& c, hmcg_extras& e) { e.corr = (double*)&on; c.sweep_count = 44; }},
+        {"sweep_base beyond the run", [&](hmcg_config& c, hmcg_extras&) { c.sweep_base = 46; }},
+    };
+    Plan untouched, pl;
+    char err[200] = "";
+    CHECK(make_plan(tab, good, nullptr, 4, 256, 0, nullptr, PlanOverrides{}, lds, &pl, err, sizeof err) == 0 && err[0] == 0 && pl.v);
+    CHECK(make_plan(tab, good, &ex0, 4, 256, 0, nullptr, PlanOverrides{}, lds, &pl, err, sizeof err) == 0 && err[0] == 0 && pl.v);
+    for (const Rule& r : rules) {
+        hmcg_config cfg = good;
+        hmcg_extras ex = ex0;
+        r.breakit(cfg, ex);
+        pl = untouched;
+        err[0] = 0;
+        CHECK(make_plan(tab, cfg, &ex, 4, 256, 0, nullptr, PlanOverrides{}, lds, &pl, err, sizeof err) == HMCG_E_BADARG);
+        CHECK(strcmp(err, r.msg) == 0);
+        CHECK(pl.v == nullptr && pl.bv == nullptr);              // no plan comes back with an error
+    }
+    // (the rules that need no extras hold without them too; sweep_base AT the end of the run is a legal empty call)
+    hmcg_config cfg = good;
+    cfg.n_samples = 2;
+    CHECK(make_plan(tab, cfg, nullptr, 4, 256, 0, nullptr, PlanOverrides{}, lds, &pl, err, sizeof err) == HMCG_E_BADARG && strcmp(err, BADARG_SIG) == 0);
+    cfg = good;
+    cfg.sweep_base = 45;
+    CHECK(make_plan(tab, cfg, nullptr, 4, 256, 0, nullptr, PlanOverrides{}, lds, &pl, err, sizeof err) == 0 && pl.sched.sweep_begin == 45 && pl.sched.sweep_end == 45);
+    return 0;
+}
+
+static int schedule_checks()
+{
+    std::mt19937_64 g(17);
+    const int edge[] = {0, 1, 2, 3, 1000, 0x3fffffff, 0x7ffffffe, 0x7fffffff};
+    auto pick = [&](long long most) {         // in [0, most], the small and the extreme values often
+        const long long v = (g() & 1) ? (long long)edge[g() % 8] : (long long)(g() % (unsigned long long)(most + 1));
+        return (int)std::min(v, most);
+    };
+    for (int rep = 0; rep < 20000; ++rep) {
+        hmcg_config cfg{};
+        cfg.n_samples = pick(rep % 3 ? 6 : 0x7fffffff);
+        const long long ns = std::max(1, cfg.n_samples), per_most = 0x7fffffffLL / ns;    // validate(): n_samples * (burnin + nrun) <= 2^31 - 1
+        cfg.burnin = pick(per_most);
+        cfg.nrun = pick(per_most - cfg.burnin);
+        cfg.sweep_base = pick(0x7fffffff);
+        cfg.sweep_count = pick(0x7fffffff);
+        const SweepSchedule s = sweep_schedule(cfg);
+        const long long total = ns * ((long long)cfg.burnin + cfg.nrun), stop = (long long)cfg.sweep_base + cfg.sweep_count;
+        const long long end = cfg.sweep_count > 0 && stop < total ? stop : total;
+        CHECK(s.n_samples == ns && s.per_sample == std::max(1LL, (long long)cfg.burnin + cfg.nrun) && s.total_sweeps == total);
+        CHECK(s.nd == ns * cfg.nrun && s.sweep_begin == cfg.sweep_base && s.sweep_end == end && s.final_launch == (end == total ? 1 : 0));
+    }
+    return 0;
+}
+
+static int plan_checks()
+{
+    for (int s = 0; s < 2; ++s) for (int m = 0; m < 2; ++m) for (int t = 0; t < 2; ++t)
+        for (int k = 0; k < BIG_NK; ++k) g_forms[s][m][t][k] = BigVariant{BIG_KMIN + k, 256, nullptr};
+    // A: the shape of the shipped K = 3 base path (eight classes in three flavours, rows at other block sizes), and a few more paths
+    // B: gaps -- classes far apart, classes that lack flavours.  C: more classes than a call has bucket slots
+    FakeTable tb[3];
+    {
+        const int LA[] = {1, 2, 4, 8, 3, 6, 12, 16}, prefA[][2] = {{H, P2}, {H, P1}, {H, P2}, {H, P2}, {H, P2}, {P2, P2}, {P1, P2}, {P1, H}};
+        for (int i = 0; i < 8; ++i) add_class(tb[0].rows[i < 4 ? 0 : 1], 3, LA[i], false, false, prefA[i][0], prefA[i][1]);
+        tb[0].rows[0].push_back({3, 2, 512, nullptr, false, false, 0, 1, P1, P1});
+        tb[0].rows[0].push_back({3, 8, 128, nullptr, false, false, 0, 2, P2, P2});
+        for (int L : {1, 2, 4}) add_class(tb[0].rows[1], 4, L, false, false, H, P2);
+        for (int L : {1, 2, 4, 8}) add_class(tb[0].rows[1], 3, L, true, false, P2, H);
+        for (int L : {1, 2, 4}) add_class(tb[0].rows[0], 3, L, false, true, H, H);
+        for (int L : {2, 4}) add_class(tb[0].rows[0], 2, L, true, true, P1, P2);
+        add_class(tb[1].rows[0], 3, 16, false, false, P1, P2, 4);          // H only
+        add_class(tb[1].rows[0], 3, 1, false, false, H, P2);
+        add_class(tb[1].rows[1], 3, 5, false, false, P1, H, 6);            // no P1
+        add_class(tb[1].rows[1], 3, 9, false, false, H, P1, 3);            // no H
+        tb[1].rows[0].push_back({3, 3, 256, nullptr, false, false, 0, 2, H, H});      // no H, and P2 ahead of P1
+        tb[1].rows[0].push_back({3, 3, 256, nullptr, false, false, 0, 1, H, H});
+        add_class(tb[1].rows[1], 2, 7, false, false, H, P2, 2);
+        add_class(tb[1].rows[1], 2, 2, false, false, P2, P2);
+        const int LC[] = {1, 2, 3, 4, 5, 6, 7, 8, 10, 12, 14, 16};
+        for (int i = 0; i < 12; ++i) add_class(tb[2].rows[i % 2], 3, LC[i], false, false, i % 3, (i + 1) % 3);
+        for (int L : {1, 2, 3, 4, 5, 6, 7, 8, 9, 10}) add_class(tb[2].rows[1], 4, L, false, true, H, P2);
+    }
+    if (plan_rule_checks(tb[0].tab())) return 1;
+    if (schedule_checks()) return 1;
+
+    std::mt19937 g(19);
+    auto coin = [&]() { return (g() & 1) != 0; };
+    auto one_in = [&](unsigned n) { return g() % n == 0; };
+    char on;
+    int seen_buckets = 0, seen_trunc = 0, seen_big = 0, seen_stream = 0, seen_unsupported = 0, seen_skipped_class = 0;
+    for (int rep = 0; rep < 6000; ++rep) {
+        FakeTable& ft = tb[rep % 3];
+        const KernelTables tab = ft.tab();
+        hmcg_config cfg{};
+        cfg.struct_size = (int32_t)sizeof cfg;
+        cfg.K = one_in(4) ? 2 + (int)(g() % 7) : (coin() ? 3 : 4);
+        cfg.burnin = 3; cfg.nrun = 10; cfg.H = 1;
+        const int maxT = one_in(5) ? 2 + (int)(g() % 9000) : 2 + (int)(g() % 4200);
+        cfg.ldY = maxT + (int)(g() % 3);
+        cfg.max_T = cfg.ldY == maxT && coin() ? 0 : maxT;                 // (0: ldY stands in)
+        cfg.threads_per_window = one_in(6) ? (int)(g() % 4) * 128 + 128 : 0;
+        hmcg_extras ex{};
+        ex.struct_size = (int32_t)sizeof ex;
+        const bool sig = one_in(4), smooth = one_in(4);
+        if (sig) ex.sig_range = (const int32_t*)&on;
+        if (smooth) (coin() ? ex.pi_smooth_mean : (coin() ? ex.pi_filter_mean : ex.pi_smooth_draws)) = (double*)&on;
+        const int W = 1 + (int)(g() % 600), cu_count = 1 + (int)(g() % 512);
+        // the windows: a few lengths of a ragged batch or every length of the range, and invalid ones among them
+        std::vector<int32_t> T((size_t)W);
+        const int span = coin() ? maxT : std::max(1, maxT / (1 + (int)(g() % 6))), few = one_in(3) ? 1 + (int)(g() % 3) : 0;
+        int32_t some[3];
+        for (int32_t& t : some) t = maxT - (int32_t)(g() % (unsigned)span);
+        const int32_t bad[] = {INT32_MIN, INT32_MIN + 1, -7, 0, 1, maxT + 1, cfg.ldY + 300, INT32_MAX - 1, INT32_MAX};
+        for (int32_t& t : T) t = one_in(9) ? bad[g() % 9] : (few ? some[g() % (unsigned)few] : maxT - (int32_t)(g() % (unsigned)span));
+        std::vector<int32_t> perm((size_t)W);
+        std::iota(perm.begin(), perm.end(), 0);
+        std::shuffle(perm.begin(), perm.end(), g);
+        const int n = 1 + (int)(g() % (unsigned)W);
+        const bool host_entry = coin(), rows = host_entry && coin();       // host entry: lengths known; rows: a device's share of them
+        const HostLengths hl{T.data(), rows ? perm.data() : nullptr, rows ? n : W};
+        int minT = 0;
+        if (host_entry) { for (int i = 0; i < hl.n; ++i) if (hl.at(i) >= 2 && (minT == 0 || hl.at(i) < minT)) minT = hl.at(i); }   // as HostCall::plan
+        else minT = one_in(4) ? 0 : (one_in(8) ? maxT : 1 + (int)(g() % (unsigned)(maxT + 3)));                                     // the caller's hint
+        PlanOverrides ov;
+        const char* const fl_names[] = {"p1", "p2", "h"};
+        const int force = one_in(4) ? (int)(g() % 3) : -1;
+        if (force >= 0) ov.flavour = fl_names[force];
+        const char* const bf_texts[] = {"h", "p2,h", "p1,p1,h,p2,p2,h,h,p1,p2,p2"};
+        const int bf_codes[] = {H, -1, -1, -1, -1, -1, -1, -1, -1, -1, P2, H, -1, -1, -1, -1, -1, -1, -1, -1, P1, P1, H, P2, P2, H, H, P1, P2, P2};
+        const int bf = one_in(4) ? (int)(g() % 3) : -1;
+        if (bf >= 0) ov.bucket_flavours = bf_texts[bf];
+        ov.force_big = one_in(12); ov.no_buckets = one_in(12); ov.force_stream = one_in(12); ov.stamps = one_in(12);
+        // static LDS of the fake kernel: at, one above and around the largest that still fits
+        const size_t dyn_want = (size_t)256 * (size_t)((maxT + 255) / 256) * 21 + 16, fit = 160 * 1024;
+        const size_t stat = coin() ? (size_t)(g() % 60000) : (dyn_want <= fit ? fit - dyn_want + (coin() ? 1 : 0) : 0);
+        int lds_calls = 0;
+        const auto lds = [&](const BigVariant&) { ++lds_calls; return stat; };
+
+        Plan pl;
+        char err[200] = "";
+        const int rc = make_plan(tab, cfg, &ex, hl.n, cu_count, minT, host_entry ? &hl : nullptr, ov, lds, &pl, err, sizeof err);
+        const bool small_batch = hl.n <= cu_count;
+
+        // ---- the restatement ----
+        const int nt = cfg.threads_per_window > 0 ? cfg.threads_per_window : 256;
+        std::vector<const Variant*> path;                       // the rows of this (K, block size, path), table order
+        for (int gi = 0; gi < 2; ++gi) for (const Variant& v : ft.rows[gi]) if (v.K == cfg.K && v.NT == nt && v.sig == sig && v.smooth == smooth) path.push_back(&v);
+        std::vector<int> classes;
+        for (const Variant* v : path) classes.push_back(v->L);
+        std::sort(classes.begin(), classes.end());
+        classes.erase(std::unique(classes.begin(), classes.end()), classes.end());
+        auto cover = [&](long long t) { for (int L : classes) if ((long long)nt * L >= t) return L; return 0; };     // 0: none
+        // the row of class L the tie rule names: the wanted flavour, else P1, else the first
+        auto row_of = [&](int L, int forced) {
+            const Variant* first = nullptr; const Variant* p1 = nullptr;
+            for (const Variant* v : path) {
+                if (v->L != L) continue;
+                if (flavour_of(*v) == (forced >= 0 ? forced : (small_batch ? v->pref_small : v->pref_big))) return v;
+                if (!first) first = v;
+                if (!p1 && flavour_of(*v) == P1) p1 = v;
+            }
+            return p1 ? p1 : first;
+        };
+        const int Lhi = cfg.K < 5 && !ov.force_big ? cover(maxT) : 0;
+        CHECK(pl.sched.total_sweeps == 13 || rc != 0);
+        if (Lhi == 0) {
+            // the LDS-resident kernel: K >= 5, forced, or no register-resident row covers the longest window
+            if (cfg.threads_per_window != 0 && cfg.threads_per_window != 256) {
+                char want[200];
+                snprintf(want, sizeof want, "no kernel for K=%d max_T=%d threads_per_window=%d", cfg.K, maxT, cfg.threads_per_window);
+                CHECK(rc == HMCG_E_UNSUPPORTED && strcmp(err, want) == 0 && !pl.v && !pl.bv);
+                ++seen_unsupported;
+                continue;
+            }
+            const int bigL = (maxT + 255) / 256;
+            const bool streams = dyn_want + stat > fit || ov.force_stream;
+            CHECK(rc == 0 && err[0] == 0 && pl.v == nullptr && pl.nb == 0 && lds_calls == 1);
+            CHECK(pl.bv == &g_forms[sig][smooth][streams][cfg.K - BIG_KMIN] && pl.bigL == bigL && pl.stream == streams && pl.dyn == (streams ? 16 : dyn_want));
+            CHECK(pl.use_sig == sig && pl.use_smooth == smooth && pl.needs_pif() == smooth && pl.NT() == 256 && pl.L() == bigL && pl.NH() == 0);
+            ++seen_big; seen_stream += streams;
+            continue;
+        }
+        CHECK(rc == 0 && err[0] == 0 && pl.bv == nullptr && !pl.stream && pl.dyn == 0 && lds_calls == 0 && pl.use_sig == sig && pl.use_smooth == smooth && !pl.needs_pif());
+        const int Llo = minT > 0 ? cover(minT) : 0;
+        const bool cut = nt == 256 && cfg.threads_per_window == 0 && minT > 0 && minT < maxT && !ov.no_buckets && !ov.stamps && Llo < Lhi;
+        std::vector<int> kept;                                   // the classes launched, longest first
+        bool truncated = false;
+        if (cut) {
+            for (auto it = classes.rbegin(); it != classes.rend(); ++it) {
+                if (*it > Lhi || *it < Llo) continue;
+                bool any = !host_entry || *it == Lhi;
+                for (int i = 0; host_entry && i < hl.n && !any; ++i) any = hl.at(i) >= 1 && cover(hl.at(i)) == *it;
+                if (any) kept.push_back(*it); else ++seen_skipped_class;
+            }
+            truncated = (int)kept.size() > MAXBUCKET;
+            kept.resize(std::min<size_t>(kept.size(), MAXBUCKET));
+        }
+        if (kept.size() <= 1) {
+            // one launch, sized for the longest window (threads_per_window, no or equal minT, an override, or one class after all)
+            CHECK(pl.nb == 0 && pl.v == row_of(Lhi, cut && bf >= 0 && bf_codes[10 * bf] >= 0 ? bf_codes[10 * bf] : force));
+            CHECK(pl.NT() == nt && pl.L() == Lhi && pl.NH() == pl.v->NH && (long long)nt * Lhi >= maxT);
+            continue;
+        }
+        ++seen_buckets; seen_trunc += truncated;
+        const int nb = (int)kept.size();
+        CHECK(pl.nb == nb && pl.v == pl.b[0].v);
+        for (int j = 0; j < nb; ++j) {
+            const int tok = bf >= 0 ? bf_codes[10 * bf + j] : -1;                     // per-bucket flavours: longest bucket first
+            CHECK(pl.b[j].v == row_of(kept[(size_t)j], tok >= 0 ? tok : force) && pl.b[j].v->NT == 256);
+        }
+        // longest first, no gap, no overlap, and the two ends of int32_t
+        CHECK(pl.b[0].t_hi == INT32_MAX && pl.b[nb - 1].t_lo == INT32_MIN);
+        for (int j = 0; j < nb; ++j) CHECK(pl.b[j].t_lo <= pl.b[j].t_hi && (j == 0 || (pl.b[j].t_hi < pl.b[j - 1].t_lo && pl.b[j].t_hi + 1 == pl.b[j - 1].t_lo)));
+        // where a length goes (the test of bucket_lists_kernel): exactly one bucket; a coverable one to the smallest kept class that covers it
+        std::vector<int32_t> probe(T);
+        probe.insert(probe.end(), std::begin(bad), std::end(bad));
+        for (int L : classes) for (int d = -1; d <= 1; ++d) probe.push_back(256 * L + d);
+        for (int i = 0; i < 40; ++i) probe.push_back((int32_t)g());
+        for (int i = 0; i < 40; ++i) probe.push_back(2 + (int32_t)(g() % (unsigned)maxT));
+        for (int32_t t : probe) {
+            int hits = 0, at = -1;
+            for (int j = 0; j < nb; ++j) if (t >= pl.b[j].t_lo && t <= pl.b[j].t_hi) { ++hits; at = j; }
+            CHECK(hits == 1);
+            int want = t > 256 * Lhi ? 0 : nb - 1;
+            for (int j = 0; j < nb && t >= 1 && t <= 256 * Lhi; ++j) if (256 * kept[(size_t)j] >= t) want = j;        // (kept descends: the last that covers)
+            CHECK(at == want);
+            if (t >= 1 && t <= 256 * Lhi) CHECK(256 * pl.b[at].v->L >= t);             // also with more classes than slots
+        }
+        // the host entries' own windows run on the class their length selects among ALL classes (theirs is kept), slots permitting
+        for (int i = 0; host_entry && !truncated && i < hl.n; ++i) {
+            const int32_t t = hl.at(i);
+            if (t < 2 || t > maxT) continue;
+            for (int j = 0; j < nb; ++j) if (t >= pl.b[j].t_lo && t <= pl.b[j].t_hi) CHECK(pl.b[j].v->L == cover(t));
+        }
+    }
+    // every branch above was taken
+    CHECK(seen_buckets > 500 && seen_trunc > 10 && seen_big > 200 && seen_stream > 50 && seen_stream < seen_big && seen_unsupported > 10 && seen_skipped_class > 50);
+    return 0;
+}
+
 static int csv_checks(const char* dir)
 {
     char buf[64];
@@ -292,6 +588,7 @@ int main(int argc, char** argv)
     if (partition_checks()) return 1;
     if (chunk_checks()) return 1;
     if (buffer_checks()) return 1;
+    if (plan_checks()) return 1;
     if (csv_checks(argv[1])) return 1;
     printf("host harness ok\n");
     return 0;

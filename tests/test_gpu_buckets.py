@@ -1,4 +1,4 @@
-"""Length-bucketed dispatch of ragged batches (csrc/hmcg.hip, make_plan / launch_kernel).
+"""Length-bucketed dispatch of ragged batches (csrc/plan.hpp make_plan, csrc/hmcg.hip launch_kernel).
 
 The reference's production run is 460 expanding windows of 120..579 months (code/run_hmm.jl:79-109; one SLURM task per
 window, slurmscripts/base_estimation.sh:5).  Until round 3 one launch ran them all on the steps-per-thread variant of the

@@ -1,7 +1,9 @@
 """Sanitizer runs of everything in the library that needs no GPU (GPU AddressSanitizer is not available
 on this pool, so this is the CPU side only):
   * tests/sanitize/host_harness.cpp = hmc.jl_amd/csrc/host_util.hpp (ScatterPool, partition_windows, plan_chunks, the host
-    entry's table of per-window buffers with its layouts and pack / unpack: the very header the library compiles) + csrc/hmcg_csv.cpp (format_float, the table writers and their thread pool) under
+    entry's table of per-window buffers with its layouts and pack / unpack) + csrc/plan.hpp (make_plan: the argument rules, the
+    kernel variant, the length buckets, the LDS-resident fallback, the sweep range -- on kernel tables built in the harness): the
+    very headers the library compiles; + csrc/hmcg_csv.cpp (format_float, the table writers and their thread pool) under
     AddressSanitizer + UBSan and under ThreadSanitizer;
   * the oracle's C restatement under AddressSanitizer + UBSan (tests/sanitize/oracle_harness.c)."""
 import os
