@@ -281,6 +281,7 @@ def estimate_batch_host(Y, T, K, burnin, nrun, horizons=(12,), yreal=None, seed=
     out["steps_per_thread"] = tm.steps_per_thread
     out["lds_bytes"] = tm.lds_bytes
     out["helper_waves"] = tm.helper_waves
+    out["occupancy"] = tm.occupancy
     out["launches"] = tm.launches
     out["buckets"] = tm.buckets
     out["streaming"] = bool(tm.streaming)

@@ -394,12 +394,18 @@ def test_signal_run_resumed_with_every_running_sum(hmclib):
     assert np.array_equal(a["mu"][:, :, :d], one["mu"][:, :, :d]) and np.array_equal(b["mu"][:, :, d:], one["mu"][:, :, d:])
 
 
+# (K, L, NT) of the kernel rows with a thread count of their own (csrc/variants_k3.hip), each selected by threads_per_window=NT
+# at T = 1000; tests/test_variant_coverage.py holds this list to the tables
+THREADS_PER_WINDOW_CASES = [(3, 8, 128), (3, 2, 512)]
+
+
 def test_threads_per_window_variants_agree(hmclib, oracle):
     """The 128- and 512-thread decompositions scan in a different association order; they must
     still match the oracle (and hence each other) within tolerance with identical state paths."""
-    Y, Tw, fut = synth.generate_panel(3, 1000, 3)
-    for tpw in (128, 512):
-        check_against_oracle(oracle, Y, Tw, 3, 2, 20, (12,), fut[:, 11:12], threads_per_window=tpw)
+    for K, L, tpw in THREADS_PER_WINDOW_CASES:
+        Y, Tw, fut = synth.generate_panel(3, 1000, K)
+        g = check_against_oracle(oracle, Y, Tw, K, 2, 20, (12,), fut[:, 11:12], threads_per_window=tpw)
+        assert g["threads_per_window"] == tpw and g["steps_per_thread"] == L and g["buckets"] == 1
 
 
 @pytest.mark.parametrize("K", [2, 3, 4])

@@ -64,6 +64,9 @@ def test_every_variant_against_oracle(hmclib, oracle, monkeypatch, K, L, path, f
                                      want_smooth=(path == "smooth"), want_filter_mean=(path == "smooth"))
     assert g["steps_per_thread"] == L and g["threads_per_window"] == 256, (g["steps_per_thread"], L)
     assert g["helper_waves"] == (4 if flavour == "h" else 0)
+    assert g["occupancy"] == {"p1": 1, "p2": 2, "h": 2}[flavour]          # the OCC argument of the three HMCG_V3 expansions
+    classes = sorted({l for (k, l, p) in ROWS if (k, p) == (K, path)})
+    assert g["buckets"] == (1 if min(l for l in classes if 256 * l >= lens[1]) == L else 2)     # 2: the second window falls a class lower
     for w in range(2):
         T = int(Tw[w])
         if path == "sig":
@@ -155,6 +158,7 @@ def test_smoothed_and_filtered_means_on_the_signal_path(hmclib, oracle, K, L):
     g = _lib.estimate_batch_host(Y, Tw, K, burnin, nrun, (12,), fut[:, 11:12], want_state=True, sig_range=sig, save_range=sig,
                                  sigma_signal=ssig, kappa=0.6, n_samples=ns, alpha=2.0, nu=2.0, want_smooth=True, want_filter_mean=True)
     assert g["steps_per_thread"] == L and g["helper_waves"] == 0
+    assert g["occupancy"] == 1                                              # every sigsmooth row is the plain flavour, OCC 1
     for w in range(2):
         T = int(Tw[w])
         o = oracle.estimate_signals(Y[w, :T], K, burnin, nrun, ns, sig=tuple(sig[w]), kappa=0.6, alpha=2.0, nu=2.0,

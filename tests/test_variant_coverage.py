@@ -1,0 +1,118 @@
+"""The per-instantiation contract, checked without a GPU: every kernel instantiation the variant tables compile --
+gibbs_sweeps_kernel<K, L, NT, SIG, SM, NH, OCC> (the three flavours of each HMCG_V3 row, the lone HMCG_V rows) and
+gibbs_sweeps_kernel_big<K, 256, SM, ST, SIG> (8 forms x K = 2..8) -- is named by an oracle-parity case of the GPU suite, and no
+case names a kernel that is not compiled.  The tables are parsed from csrc/variants.hpp and csrc/variants_*.hip and held
+against the kernel symbols of the built libhmcgibbs.so, so that a regex which silently drops a row fails here; the cases are
+the parametrize lists of the GPU tests themselves (importing those modules needs no GPU)."""
+import os
+import re
+import shutil
+import subprocess
+
+import test_gpu_big_variants as big
+import test_gpu_parity as parity
+import test_gpu_variants as reg
+from hmc_jl_amd import _lib
+
+FLAVOUR = {"p1": (0, 1), "p2": (0, 2), "h": (4, 2)}                      # (NH, OCC) of the three HMCG_V3 expansions
+PATH = {"base": (False, False), "sig": (True, False), "smooth": (False, True)}
+
+
+def fmt_reg(r):
+    return "gibbs_sweeps_kernel<K=%d, L=%d, NT=%d, SIG=%d, SM=%d, NH=%d, OCC=%d>" % r
+
+
+def fmt_big(b):
+    sig, sm, st, K = b
+    return "gibbs_sweeps_kernel_big<K=%d, 256, SM=%d, ST=%d, SIG=%d> (form %d%d%d)" % (K, sm, st, sig, sig, sm, st)
+
+
+def cases_of(test):
+    """The argument tuples of a test function's pytest.mark.parametrize: what the suite actually runs."""
+    marks = [m for m in getattr(test, "pytestmark", []) if m.name == "parametrize"]
+    assert len(marks) == 1, test.__name__
+    return list(marks[0].args[1])
+
+
+def library_kernels():
+    """The instantiations in the built library, from its kernel symbols (Itanium names: the template arguments are the
+    Li<int>E / Lb<0|1>E fields, as tools/isa_lint.py reads them)."""
+    nm = shutil.which("nm") or shutil.which("llvm-nm") or shutil.which("llvm-nm", path="/opt/rocm/llvm/bin")
+    assert nm, "no nm / llvm-nm to list the symbols of libhmcgibbs.so"
+    assert os.path.exists(_lib.SO_PATH), "libhmcgibbs.so is not built"
+    names = set(re.findall(r"\b(_ZN4hmcg\d+gibbs_sweeps_kernel(?:_big)?I\w+)", subprocess.run([nm, "-D", "--defined-only", _lib.SO_PATH], check=True, capture_output=True, text=True).stdout))
+    regs, bigs = [], []
+    for name in sorted(names):
+        m = re.match(r"_ZN4hmcg\d+gibbs_sweeps_kernel(_big)?I((?:L[ib]\d+E)+)EEvNS_12KernelParamsE", name)
+        assert m, "kernel symbol of an unknown shape: " + name
+        a = [int(x) for x in re.findall(r"L[ib](\d+)E", m.group(2))]
+        if m.group(1):
+            K, nt, sm, st, sig = a
+            assert nt == 256, name
+            bigs.append((bool(sig), bool(sm), bool(st), K))
+        else:
+            K, L, nt, sig, sm, nh, occ = a
+            regs.append((K, L, nt, bool(sig), bool(sm), nh, occ))
+    return regs, bigs
+
+
+def test_parsed_tables_are_the_kernels_of_the_built_library():
+    """129 register-resident and 56 LDS-resident instantiations today; whatever the numbers, the source parse and the
+    library's symbols name the same kernels, none twice."""
+    rows, bigs = big.register_rows(), big.big_instantiations()
+    assert len(set(rows)) == len(rows) and len(set(bigs)) == len(bigs)
+    lib_rows, lib_bigs = library_kernels()
+    assert len(lib_rows) + len(lib_bigs) == len(rows) + len(bigs), (len(lib_rows), len(lib_bigs), len(rows), len(bigs))
+    assert sorted(lib_rows) == sorted(rows), [fmt_reg(r) for r in set(lib_rows) ^ set(rows)]
+    assert sorted(lib_bigs) == sorted(bigs), [fmt_big(b) for b in set(lib_bigs) ^ set(bigs)]
+    assert len(bigs) == 56 and len(rows) >= 129
+
+
+def covered_register_rows():
+    """Instantiation -> the case that names it, over the register-resident case lists of the GPU suite."""
+    named = {}
+    for (K, L, path, fl) in cases_of(reg.test_every_variant_against_oracle):
+        named[(K, L, 256) + PATH[path] + FLAVOUR[fl]] = "test_every_variant_against_oracle[K%d-L%d-%s-%s]" % (K, L, path, fl)
+    for (K, L) in cases_of(reg.test_smoothed_and_filtered_means_on_the_signal_path):
+        named[(K, L, 256, True, True, 0, 1)] = "test_smoothed_and_filtered_means_on_the_signal_path[K%d-L%d]" % (K, L)
+    rows = big.register_rows()
+    for (K, L, nt) in parity.THREADS_PER_WINDOW_CASES:
+        # a thread count of its own: the one base-path row of that (K, L, NT) is what threads_per_window=NT selects
+        mine = [r for r in rows if r[:5] == (K, L, nt, False, False)]
+        assert len(mine) <= 1, "several flavours at NT=%d: test_threads_per_window_variants_agree cannot tell them apart" % nt
+        named[mine[0] if mine else (K, L, nt, False, False, -1, -1)] = "test_threads_per_window_variants_agree (K=%d L=%d NT=%d)" % (K, L, nt)
+    return named
+
+
+def test_every_register_resident_instantiation_has_an_oracle_case():
+    rows, named = set(big.register_rows()), covered_register_rows()
+    missing = sorted(rows - set(named))
+    assert not missing, "compiled, but no oracle-parity case names it: " + "; ".join(fmt_reg(r) for r in missing)
+    extra = sorted(set(named) - rows)
+    assert not extra, "a case names a kernel that is not compiled: " + "; ".join("%s -> %s" % (named[r], fmt_reg(r)) for r in extra)
+
+
+def test_every_lds_resident_instantiation_has_an_oracle_case():
+    bigs = set(big.big_instantiations())
+    cases = cases_of(big.test_every_big_instantiation_against_oracle)
+    assert len(set(cases)) == len(cases)
+    missing = sorted(bigs - set(cases))
+    assert not missing, "compiled, but no oracle-parity case names it: " + "; ".join(fmt_big(b) for b in missing)
+    extra = sorted(set(cases) - bigs)
+    assert not extra, "a case names a kernel that is not compiled: " + "; ".join(fmt_big(b) for b in extra)
+    # the coverage case must take the production route to its kernel: beyond the ladder (LDS forms) / beyond the LDS (streaming)
+    for (sig, sm, st, K) in cases:
+        top = big.coverage_lengths(sig, sm, st, K)[0]
+        assert top > big.ladder_ceiling(K, sig, sm) and top % 256 != 0, fmt_big((sig, sm, st, K))
+        assert (big.dyn_bytes((top + 255) // 256) > big.LDS_LIMIT) == st, fmt_big((sig, sm, st, K))
+
+
+def test_depth_cases_stay_beyond_the_ladder():
+    """The fixed depth cases of the base form only name depths the production dispatch hands to the LDS-resident kernel, and
+    every K has its deepest ones."""
+    cases = cases_of(big.test_base_form_depth_edges)
+    for (K, L) in cases:
+        assert 256 * L - 1 > big.ladder_ceiling(K, False, False), (K, L)
+    for K in big.big_form_ks():
+        assert {L for (k, L) in cases if k == K} >= {L for L in (8, 9, 16, 17) if 256 * L - 1 > big.ladder_ceiling(K, False, False)}, K
+        assert (K, 17) in cases
