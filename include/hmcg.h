@@ -66,7 +66,9 @@ extern "C" {
 #define HMCG_E_NOMEM    (-4)
 
 /* status[w] bits */
-#define HMCG_ST_BAD_INVGAMMA   1 /* a<=0 or b<=0 in the InvGamma update: old variance kept (src/Hmc.jl:319-329) */
+#define HMCG_ST_BAD_INVGAMMA   1 /* a<=0 or b<=0 in the InvGamma update: old variance kept (src/Hmc.jl:319-329).  Kept for the
+                                    reference's branch; no call can raise it: the entry reads alpha <= 0 as 1, so a >= alpha > 0,
+                                    and beta >= 1 plus non-negative sums of squares keeps b > 0.  No test provokes it. */
 #define HMCG_ST_EMIS_UNDERFLOW 2 /* all K emission pdfs underflowed at some step: that observation was treated as missing (f=1); or a zero
                                     normaliser was replaced by the uniform law (reference would produce NaN and throw, src/Hmc.jl:435) */
 #define HMCG_ST_NONFINITE      4 /* non-finite observation: window skipped, outputs untouched */

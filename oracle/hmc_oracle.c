@@ -63,6 +63,37 @@
 
 enum { SITE_SIG2 = 0, SITE_MU = 1, SITE_RHO = 2, SITE_A = 3, SITE_X = 4, SITE_NOISE = 5 };
 
+/* ------------------------------------------------- branch counters ------- */
+
+/* How often a chain took each data-dependent branch of the sampler: what tests/test_branch_coverage.py holds the GPU
+ * suite's case lists to.  Kept per chain (chain_t.bc; hmco_estimate_batch runs chains under OpenMP), never read by the
+ * sampler itself: the numerics are those of a build without them.  Order = oracle.py's BRANCH_NAMES. */
+enum {
+    BC_SWEEPS = 0,        /* gibbs_sweep calls */
+    BC_PERM,              /* ... whose sortperm(mu) is not the identity */
+    BC_NONINVOL,          /* ... whose sortperm(mu) is not its own inverse (a 3-cycle or longer) */
+    BC_KEPT,              /* kept sweeps (it >= burnin) */
+    BC_KEPT_PERM,         /* ... with a non-identity order */
+    BC_KEPT_NONINVOL,     /* ... with an order that is not its own inverse */
+    BC_ORDERS,            /* distinct orders seen (at most HMCO_MAXORDERS are told apart) */
+    BC_GAMMA_1,           /* Marsaglia-Tsang draws (shape != 1) accepted at the first attempt */
+    BC_GAMMA_2,           /* ... at the second */
+    BC_GAMMA_3,           /* ... at the third or later, all sites */
+    BC_GAMMA_3_SIG2,      /* ... of them at site SIG2 */
+    BC_GAMMA_3_A,         /* ... of them at site A */
+    BC_V_REJECT,          /* attempts thrown away on v = 1 + c x <= 0 */
+    BC_SHAPE_EQ1,         /* shape == 1 draws (exponential) */
+    BC_SHAPE_LT1,         /* shape < 1 draws (the U^(1/shape) boost) */
+    BC_EMPTY,             /* state updates with Ni + Mi == 0 */
+    BC_SIG_ONLY,          /* signal path: states with Ni == 0 < Mi */
+    BC_REAL_ONLY,         /* signal path: states with Mi == 0 < Ni */
+    BC_UNDERFLOW,         /* filter steps whose K emission pdfs all underflowed */
+    BC_X_UNIFORM,         /* update_X steps that fell back to the uniform law (total <= eps) */
+    BC_CAT_GUARD,         /* categorical draws that stopped on the i < n-1 guard with cp <= u */
+    BC_N
+};
+#define HMCO_MAXORDERS 64
+
 /* ------------------------------------------------------------------ RNG -- */
 
 static void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1)
@@ -118,10 +149,13 @@ static double rng_normal(const rng_t *g, uint32_t site, uint32_t elem, uint32_t 
 }
 
 /* Gamma(shape, 1).  Stand-in for rand(Gamma) of Distributions 0.21.8. */
-static double rng_gamma(const rng_t *g, uint32_t site, uint32_t elem, double shape, int *status)
+static double rng_gamma(const rng_t *g, uint32_t site, uint32_t elem, double shape, int *status, int64_t *bc)
 {
     uint32_t r[4];
+    int64_t none[BC_N] = { 0 };           /* a caller that keeps no counters */
+    if (!bc) bc = none;
     if (shape == 1.0) {
+        bc[BC_SHAPE_EQ1] += 1;
         rng_block(g, site, elem, 0, r);
         return -log(1.0 - u53(r[0], r[1]));
     }
@@ -136,12 +170,16 @@ static double rng_gamma(const rng_t *g, uint32_t site, uint32_t elem, double sha
         rng_block(g, site, elem, 2u * (uint32_t)j + 1u, r);
         double u = u53(r[0], r[1]);
         double v = 1.0 + c * x;
-        if (v <= 0.0) continue;
+        if (v <= 0.0) { bc[BC_V_REJECT] += 1; continue; }
         v = v * v * v;
         if (log(1.0 - u) < 0.5 * x * x + d - d * v + d * log(v)) { out = d * v; break; }
     }
     if (j == HMCO_GAMMA_MAX_ATTEMPTS) *status |= ST_GAMMA_CAP;
+    bc[j == 0 ? BC_GAMMA_1 : (j == 1 ? BC_GAMMA_2 : BC_GAMMA_3)] += 1;
+    if (j >= 2 && site == SITE_SIG2) bc[BC_GAMMA_3_SIG2] += 1;
+    if (j >= 2 && site == SITE_A) bc[BC_GAMMA_3_A] += 1;
     if (shape < 1.0) {
+        bc[BC_SHAPE_LT1] += 1;
         rng_block(g, site, elem, 0xFFFFFFFFu, r);
         out *= pow(1.0 - u53(r[0], r[1]), 1.0 / shape);
     }
@@ -157,11 +195,12 @@ static double rng_uniform_x(const rng_t *g, uint32_t t)
 
 /* Categorical draw: Distributions 0.21.8 DiscreteNonParametric rand (call sites
  * src/Hmc.jl:464,481).  Returns a 0-based state. */
-static int categorical(const double *p, int n, double u)
+static int categorical(const double *p, int n, double u, int64_t *bc)
 {
     double cp = p[0];
     int i = 0;
     while (cp <= u && i < n - 1) { ++i; cp += p[i]; }
+    if (cp <= u) bc[BC_CAT_GUARD] += 1;
     return i;
 }
 
@@ -209,6 +248,8 @@ typedef struct {
      * empty for the live estimatemodel caller.  kappa = hp.kappa (relative noise of a signal). */
     int sig_b, sig_e;
     double kappa;
+    int64_t bc[BC_N];                    /* branch counters of this chain */
+    uint64_t orders[HMCO_MAXORDERS];     /* the distinct orders seen, four bits per label */
 } chain_t;
 
 #define PIF(c, t, s) ((c)->pif[(size_t)(t) * (c)->K + (s)])
@@ -306,6 +347,9 @@ static void update_mu_sigma(chain_t *c, const rng_t *g)
     }
     double Neff[HMCO_MAXK];
     for (int i = 0; i < K; ++i) {
+        if (Ni[i] + Mi[i] == 0) c->bc[BC_EMPTY] += 1;
+        if (c->sig_b < c->sig_e && Ni[i] == 0 && Mi[i] > 0) c->bc[BC_SIG_ONLY] += 1;
+        if (c->sig_b < c->sig_e && Mi[i] == 0 && Ni[i] > 0) c->bc[BC_REAL_ONLY] += 1;
         double Meff = (double)Mi[i] / (1.0 + kap);                                    /* :302 */
         Neff[i] = (double)Ni[i] + Meff;                                               /* :303 */
         double a = c->alpha + 0.5 * (double)Ni[i] + 0.5 * (double)Mi[i];              /* :313 */
@@ -314,7 +358,7 @@ static void update_mu_sigma(chain_t *c, const rng_t *g)
                  + 0.5 * Neff[i] * c->nu / (Neff[i] + c->nu) * (dm * dm);             /* :314 */
         if (a > 0.0 && b > 0.0) {
             /* InverseGamma(a,b) = 1/Gamma(a, scale 1/b)  (:320) */
-            double gdraw = rng_gamma(g, SITE_SIG2, (uint32_t)i, a, &c->status);
+            double gdraw = rng_gamma(g, SITE_SIG2, (uint32_t)i, a, &c->status, c->bc);
             c->sig2[i] = 1.0 / (gdraw * (1.0 / b));
         } else {
             c->status |= ST_BAD_INVGAMMA;                                             /* :321-329 keeps old */
@@ -334,7 +378,7 @@ static void update_beta(chain_t *c) { for (int i = 0; i < c->K; ++i) c->beta[i] 
 static void update_rho(chain_t *c, const rng_t *g)
 {
     double s = 0.0;
-    for (int i = 0; i < c->K; ++i) { c->rho[i] = rng_gamma(g, SITE_RHO, (uint32_t)i, 1.0, &c->status); s += c->rho[i]; }
+    for (int i = 0; i < c->K; ++i) { c->rho[i] = rng_gamma(g, SITE_RHO, (uint32_t)i, 1.0, &c->status, NULL); s += c->rho[i]; }
     double inv = 1.0 / s;
     for (int i = 0; i < c->K; ++i) c->rho[i] *= inv;
 }
@@ -349,7 +393,7 @@ static void update_A(chain_t *c, const rng_t *g)
     for (int i = 0; i < K; ++i) {
         double s = 0.0;
         for (int j = 0; j < K; ++j) {
-            c->A[i][j] = rng_gamma(g, SITE_A, (uint32_t)(i * K + j), (double)Trans[i][j], &c->status);
+            c->A[i][j] = rng_gamma(g, SITE_A, (uint32_t)(i * K + j), (double)Trans[i][j], &c->status, c->bc);
             s += c->A[i][j];
         }
         double inv = 1.0 / s;
@@ -382,6 +426,7 @@ static void forward_update(chain_t *c)
             /* every pdf underflowed: the observation carries no usable likelihood; it is treated as
              * missing (f = 1: the step becomes the prediction pi[t-1,:]*A) and the window is flagged */
             c->status |= ST_EMIS_UNDERFLOW;
+            c->bc[BC_UNDERFLOW] += 1;
             for (int s = 0; s < K; ++s) f[s] = 1.0;
         }
         double total = 0.0;
@@ -423,19 +468,37 @@ static void update_X(chain_t *c, const rng_t *g, const int *order)
     const int K = c->K, T = c->T;
     double p[HMCO_MAXK];
     for (int s = 0; s < K; ++s) p[s] = PIF(c, T - 1, order[s]);
-    c->X[T - 1] = categorical(p, K, rng_uniform_x(g, (uint32_t)(T - 1)));             /* :464 */
+    c->X[T - 1] = categorical(p, K, rng_uniform_x(g, (uint32_t)(T - 1)), c->bc);             /* :464 */
     for (int k = T - 2; k >= 0; --k) {
         int k2 = k + 1, s = c->X[k2];
         double total = 0.0;
         for (int r = 0; r < K; ++r) { p[r] = PF(c, k2, r, s); total += p[r]; }        /* :468-471 */
         if (total > 2.220446049250313e-16) for (int j = 0; j < K; ++j) p[j] /= total; /* :472-475 */
-        else for (int j = 0; j < K; ++j) p[j] = 1.0 / K;                              /* :476-480 */
-        c->X[k] = categorical(p, K, rng_uniform_x(g, (uint32_t)k));                   /* :481 */
+        else { c->bc[BC_X_UNIFORM] += 1; for (int j = 0; j < K; ++j) p[j] = 1.0 / K; }  /* :476-480 */
+        c->X[k] = categorical(p, K, rng_uniform_x(g, (uint32_t)k), c->bc);            /* :481 */
     }
 }
 
-/* gibbssweep (src/Hmc.jl:486-515).  `order` receives sortperm(mu). */
-static void gibbs_sweep(chain_t *c, const rng_t *g, int *order, int do_smoother)
+/* Branch counters of one sweep's sortperm(mu): identity or not, its own inverse or not (order and inverse(order) are the
+ * same permutation for any product of disjoint swaps, so only a longer cycle tells the two apart), seen before or not. */
+static void count_order(chain_t *c, const int *order, int kept)
+{
+    int perm = 0, noninvol = 0;
+    uint64_t code = 0;
+    for (int i = 0; i < c->K; ++i) {
+        if (order[i] != i) perm = 1;
+        if (order[order[i]] != i) noninvol = 1;
+        code |= (uint64_t)order[i] << (4 * i);
+    }
+    c->bc[BC_SWEEPS] += 1; c->bc[BC_PERM] += perm; c->bc[BC_NONINVOL] += noninvol;
+    if (kept) { c->bc[BC_KEPT] += 1; c->bc[BC_KEPT_PERM] += perm; c->bc[BC_KEPT_NONINVOL] += noninvol; }
+    int n = (int)c->bc[BC_ORDERS], i = 0;
+    while (i < n && c->orders[i] != code) ++i;
+    if (i == n && n < HMCO_MAXORDERS) { c->orders[n] = code; c->bc[BC_ORDERS] += 1; }
+}
+
+/* gibbssweep (src/Hmc.jl:486-515).  `order` receives sortperm(mu).  kept: a sweep past the burn-in (counters only). */
+static void gibbs_sweep(chain_t *c, const rng_t *g, int *order, int do_smoother, int kept)
 {
     const int K = c->K, T = c->T;
     update_mu_sigma(c, g);
@@ -452,6 +515,7 @@ static void gibbs_sweep(chain_t *c, const rng_t *g, int *order, int do_smoother)
         while (j >= 0 && c->mu[order[j]] > c->mu[o]) { order[j + 1] = order[j]; --j; }
         order[j + 1] = o;
     }
+    count_order(c, order, kept);
     double tv[HMCO_MAXK], tA[HMCO_MAXK][HMCO_MAXK];
     for (int i = 0; i < K; ++i) tv[i] = c->mu[order[i]];
     memcpy(c->mu, tv, sizeof(double) * (size_t)K);                                    /* :502 */
@@ -534,15 +598,15 @@ double hmco_forecast(int K, const double *mu, const double *A_rowmajor, const do
  * :148-159); xi is always the mean of the REAL window.
  * flags bit0: faithful-cost mode; bit1: run the backward smoother every sweep.
  * Returns 0, or -1 on bad arguments. */
-int hmco_estimate_window_ex(const double *Y, int T, int K, int burnin, int nrun,
-                            const int *horizons, int H, const double *yreal,
-                            uint64_t seed, uint32_t window_id, int flags, const int *x_init,
-                            int sig_b, int sig_e, double kappa, double alpha, double nu,
-                            int n_samples, double sigma_signal, int save_b, int save_e,
-                            int end_pos, int blend_mask,
-                            double *mu, double *sig2, double *A, double *pi_end, double *fcast,
-                            double *pi_smooth, double *summary, double *sigvals,
-                            int *x_final, double *pif_final, double *pi_filter_mean, int *status)
+static int estimate_window_impl(const double *Y, int T, int K, int burnin, int nrun,
+                                const int *horizons, int H, const double *yreal,
+                                uint64_t seed, uint32_t window_id, int flags, const int *x_init,
+                                int sig_b, int sig_e, double kappa, double alpha, double nu,
+                                int n_samples, double sigma_signal, int save_b, int save_e,
+                                int end_pos, int blend_mask,
+                                double *mu, double *sig2, double *A, double *pi_end, double *fcast,
+                                double *pi_smooth, double *summary, double *sigvals,
+                                int *x_final, double *pif_final, double *pi_filter_mean, int *status, int64_t *branches)
 {
     /* pi_filter_mean [T][K]: mean over the kept draws of the label-sorted FILTERED probabilities pif[t,:] (:512) --
      * what data/output/official_insample/forecats_insample.csv holds in s1..s3 (an older API's "pib").
@@ -589,7 +653,7 @@ int hmco_estimate_window_ex(const double *Y, int T, int K, int burnin, int nrun,
         if (sigvals) for (int t = save_b; t < save_e; ++t) sigvals[(size_t)smp * (save_e - save_b) + (t - save_b)] = Yfake[t];
         for (int it = 0; it < burnin + nrun; ++it) {
             g.sweep = (uint32_t)(smp * (burnin + nrun) + it);
-            gibbs_sweep(&c, &g, order, smoother);
+            gibbs_sweep(&c, &g, order, smoother, it >= burnin);
             if (it < burnin) continue;
             const int d = smp * nrun + (it - burnin);
             double pe[HMCO_MAXK], arow[HMCO_MAXK * HMCO_MAXK];
@@ -635,9 +699,45 @@ int hmco_estimate_window_ex(const double *Y, int T, int K, int burnin, int nrun,
     if (x_final) for (int t = 0; t < T; ++t) x_final[t] = c.X[t];
     if (pif_final) memcpy(pif_final, c.pif, sizeof(double) * (size_t)T * K);
     if (status) *status = c.status;
+    if (branches) memcpy(branches, c.bc, sizeof c.bc);
     free(c.pif); free(c.pib); free(c.Pf); free(c.Pb); free(c.X); free(c.obs_index); free(Yfake);
     return 0;
 }
+
+int hmco_estimate_window_ex(const double *Y, int T, int K, int burnin, int nrun,
+                            const int *horizons, int H, const double *yreal,
+                            uint64_t seed, uint32_t window_id, int flags, const int *x_init,
+                            int sig_b, int sig_e, double kappa, double alpha, double nu,
+                            int n_samples, double sigma_signal, int save_b, int save_e,
+                            int end_pos, int blend_mask,
+                            double *mu, double *sig2, double *A, double *pi_end, double *fcast,
+                            double *pi_smooth, double *summary, double *sigvals,
+                            int *x_final, double *pif_final, double *pi_filter_mean, int *status)
+{
+    return estimate_window_impl(Y, T, K, burnin, nrun, horizons, H, yreal, seed, window_id, flags, x_init,
+                                sig_b, sig_e, kappa, alpha, nu, n_samples, sigma_signal, save_b, save_e, end_pos, blend_mask,
+                                mu, sig2, A, pi_end, fcast, pi_smooth, summary, sigvals, x_final, pif_final, pi_filter_mean,
+                                status, NULL);
+}
+
+/* The same run, and branches[hmco_branch_count()]: the chain's branch counters (BC_* above). */
+int hmco_estimate_window_branches(const double *Y, int T, int K, int burnin, int nrun,
+                                  const int *horizons, int H, const double *yreal,
+                                  uint64_t seed, uint32_t window_id, int flags, const int *x_init,
+                                  int sig_b, int sig_e, double kappa, double alpha, double nu,
+                                  int n_samples, double sigma_signal, int save_b, int save_e,
+                                  int end_pos, int blend_mask,
+                                  double *mu, double *sig2, double *A, double *pi_end, double *fcast,
+                                  double *pi_smooth, double *summary, double *sigvals,
+                                  int *x_final, double *pif_final, double *pi_filter_mean, int *status, int64_t *branches)
+{
+    return estimate_window_impl(Y, T, K, burnin, nrun, horizons, H, yreal, seed, window_id, flags, x_init,
+                                sig_b, sig_e, kappa, alpha, nu, n_samples, sigma_signal, save_b, save_e, end_pos, blend_mask,
+                                mu, sig2, A, pi_end, fcast, pi_smooth, summary, sigvals, x_final, pif_final, pi_filter_mean,
+                                status, branches);
+}
+
+int hmco_branch_count(void) { return BC_N; }
 
 int hmco_estimate_window(const double *Y, int T, int K, int burnin, int nrun,
                          const int *horizons, int H, const double *yreal,
@@ -741,7 +841,7 @@ double hmco_gamma(uint64_t seed, uint32_t window, uint32_t sweep, uint32_t site,
 {
     rng_t g = { seed, window, sweep };
     int st = 0;
-    return rng_gamma(&g, site, elem, shape, &st);
+    return rng_gamma(&g, site, elem, shape, &st, NULL);
 }
 double hmco_normal(uint64_t seed, uint32_t window, uint32_t sweep, uint32_t site, uint32_t elem)
 {

@@ -18,6 +18,14 @@ _LIB = None
 
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
+_lp = C.POINTER(C.c_int64)
+
+# out["branches"] of estimate_window / estimate_signals: how often the chain took each data-dependent branch of the
+# sampler (the BC_* counters of hmc_oracle.c, in their order)
+BRANCH_NAMES = ("sweeps", "perm_sweeps", "noninvol_sweeps", "kept_sweeps", "kept_perm_sweeps", "kept_noninvol_sweeps",
+                "distinct_orders", "gamma_1", "gamma_2", "gamma_3plus", "gamma_3plus_sig2", "gamma_3plus_A", "v_rejects",
+                "shape_eq1", "shape_lt1", "empty_states", "sig_only_states", "real_only_states", "underflow_steps",
+                "x_uniform_fallbacks", "cat_guard_stops")
 
 
 def build(force=False):
@@ -37,6 +45,9 @@ def lib():
         L = C.CDLL(so)
         L.hmco_estimate_window.restype = C.c_int
         L.hmco_estimate_window_ex.restype = C.c_int
+        L.hmco_estimate_window_branches.restype = C.c_int
+        L.hmco_branch_count.restype = C.c_int
+        assert L.hmco_branch_count() == len(BRANCH_NAMES), "BRANCH_NAMES is not hmc_oracle.c's BC_* list"
         L.hmco_estimate_batch.restype = C.c_int
         L.hmco_forward_filter.restype = C.c_int
         L.hmco_backward_smoother.restype = None
@@ -60,7 +71,8 @@ def estimate_window(Y, K, burnin, nrun, horizons=(12,), yreal=None, seed=1234, w
 
     Returns a dict of Julia-layout arrays converted to numpy (draw index first):
     mu (nrun,K), sig2 (nrun,K), A (nrun,K,K), pi_end (nrun,K), fcast (nrun,2H),
-    summary (3K+K^2+2H), x_final (T,) 0-based, pif_final (T,K) unsorted, status.
+    summary (3K+K^2+2H), x_final (T,) 0-based, pif_final (T,K) unsorted, status, and branches: {name: count} over
+    BRANCH_NAMES.  alpha = nu = 1 here; estimate_signals with an empty `sig` is the same base-path run at another alpha.
     """
     Y = np.ascontiguousarray(Y, dtype=np.float64)
     T = Y.shape[0]
@@ -75,14 +87,19 @@ def estimate_window(Y, K, burnin, nrun, horizons=(12,), yreal=None, seed=1234, w
     xi = None if x_init is None else np.ascontiguousarray(x_init, dtype=np.int32)
     st = C.c_int(0)
     flags = (1 if faithful_cost else 0) | (2 if smoother else 0)
-    rc = lib().hmco_estimate_window(_p(Y), C.c_int(T), C.c_int(K), C.c_int(burnin), C.c_int(nrun),
-                                    _p(hz, _ip), C.c_int(H), _p(yr), C.c_uint64(seed), C.c_uint32(window_id),
-                                    C.c_int(flags), _p(xi, _ip), _p(mu), _p(sig2), _p(A), _p(pe), _p(fc),
-                                    _p(sm), _p(summ), _p(xf, _ip), _p(pf), C.byref(st))
+    bc = np.zeros(len(BRANCH_NAMES), dtype=np.int64)
+    # hmco_estimate_window's own argument list (no signal set, alpha = nu = 1, one sample), through the entry that counts
+    rc = lib().hmco_estimate_window_branches(_p(Y), C.c_int(T), C.c_int(K), C.c_int(burnin), C.c_int(nrun),
+                                             _p(hz, _ip), C.c_int(H), _p(yr), C.c_uint64(seed), C.c_uint32(window_id),
+                                             C.c_int(flags), _p(xi, _ip), C.c_int(T), C.c_int(T), C.c_double(1.0),
+                                             C.c_double(1.0), C.c_double(1.0), C.c_int(1), C.c_double(0.0), C.c_int(0), C.c_int(0),
+                                             C.c_int(-1), C.c_int(0), _p(mu), _p(sig2), _p(A), _p(pe), _p(fc),
+                                             _p(sm), _p(summ), None, _p(xf, _ip), _p(pf), None, C.byref(st), _p(bc, _lp))
     if rc != 0:
         raise ValueError("hmco_estimate_window rc=%d" % rc)
     out = dict(mu=mu.T.copy(), sig2=sig2.T.copy(), A=A.transpose(2, 1, 0).copy(), pi_end=pe.T.copy(),
-               fcast=fc.T.copy(), summary=summ, x_final=xf, pif_final=pf, status=st.value)
+               fcast=fc.T.copy(), summary=summ, x_final=xf, pif_final=pf, status=st.value,
+               branches=dict(zip(BRANCH_NAMES, (int(v) for v in bc))))
     if want_smooth:
         out["pi_smooth"] = sm.transpose(2, 1, 0).copy()  # (nrun, T, K)
     return out
@@ -95,7 +112,9 @@ def estimate_signals(Y, K, burnin, nrun, n_samples=1, sig=(0, 0), kappa=1.0, alp
     sigma_signal=0 it is the base estimatemodel run on a window that has a signal set.
     sig/save are 0-based half-open position ranges.  end_pos (0-based) selects the position whose smoothed
     probabilities are reported as pi_end (:900; default the last step), blend_mask the horizons reported through
-    forecastsignal (:908-909).  Returns draws as (n_samples*nrun, ...) arrays plus sigvals (n_samples, nsave)."""
+    forecastsignal (:908-909).  Returns draws as (n_samples*nrun, ...) arrays plus sigvals (n_samples, nsave), and
+    branches: {name: count} over BRANCH_NAMES.  With the default empty `sig` this is estimate_window's base-path run at
+    the alpha / nu passed here."""
     Y = np.ascontiguousarray(Y, dtype=np.float64)
     T = Y.shape[0]
     H = len(horizons)
@@ -112,17 +131,19 @@ def estimate_signals(Y, K, burnin, nrun, n_samples=1, sig=(0, 0), kappa=1.0, alp
     sm = np.empty((K, T, nd)) if want_smooth else None
     xi = None if x_init is None else np.ascontiguousarray(x_init, dtype=np.int32)
     st = C.c_int(0)
-    rc = lib().hmco_estimate_window_ex(_p(Y), C.c_int(T), C.c_int(K), C.c_int(burnin), C.c_int(nrun),
-                                       _p(hz, _ip), C.c_int(H), _p(yr), C.c_uint64(seed), C.c_uint32(window_id),
-                                       C.c_int(0), _p(xi, _ip), C.c_int(sig[0]), C.c_int(sig[1]), C.c_double(kappa),
-                                       C.c_double(alpha), C.c_double(nu), C.c_int(n_samples), C.c_double(sigma_signal),
-                                       C.c_int(save[0]), C.c_int(save[1]), C.c_int(end_pos), C.c_int(blend_mask),
-                                       _p(mu), _p(sig2), _p(A), _p(pe), _p(fc),
-                                       _p(sm), _p(summ), _p(sv), _p(xf, _ip), _p(pf), _p(fm), C.byref(st))
+    bc = np.zeros(len(BRANCH_NAMES), dtype=np.int64)
+    rc = lib().hmco_estimate_window_branches(_p(Y), C.c_int(T), C.c_int(K), C.c_int(burnin), C.c_int(nrun),
+                                             _p(hz, _ip), C.c_int(H), _p(yr), C.c_uint64(seed), C.c_uint32(window_id),
+                                             C.c_int(0), _p(xi, _ip), C.c_int(sig[0]), C.c_int(sig[1]), C.c_double(kappa),
+                                             C.c_double(alpha), C.c_double(nu), C.c_int(n_samples), C.c_double(sigma_signal),
+                                             C.c_int(save[0]), C.c_int(save[1]), C.c_int(end_pos), C.c_int(blend_mask),
+                                             _p(mu), _p(sig2), _p(A), _p(pe), _p(fc),
+                                             _p(sm), _p(summ), _p(sv), _p(xf, _ip), _p(pf), _p(fm), C.byref(st), _p(bc, _lp))
     if rc != 0:
         raise ValueError("hmco_estimate_window_ex rc=%d" % rc)
     out = dict(mu=mu.T.copy(), sig2=sig2.T.copy(), A=A.transpose(2, 1, 0).copy(), pi_end=pe.T.copy(),
-               fcast=fc.T.copy(), summary=summ, sigvals=sv[:, :nsave], x_final=xf, pif_final=pf, status=st.value)
+               fcast=fc.T.copy(), summary=summ, sigvals=sv[:, :nsave], x_final=xf, pif_final=pf, status=st.value,
+               branches=dict(zip(BRANCH_NAMES, (int(v) for v in bc))))
     # runaggregate's (date, signalid) rows of this run (src/Hmc.jl:1053-1075): per noise sample, means of the rounded draws
     ss = np.empty((n_samples, 3 * K + K * K + 2 * H))
     lib().hmco_sample_summary(_p(mu), _p(sig2), _p(A), _p(pe), _p(fc), C.c_int(K), C.c_int(H), C.c_int(n_samples), C.c_int(nrun), _p(ss))
