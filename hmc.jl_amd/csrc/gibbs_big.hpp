@@ -265,6 +265,22 @@ __global__ __launch_bounds__(NT) void gibbs_sweeps_kernel_big(const KernelParams
             for (int k = 0; k < K; ++k) if (tid == k) sh.pivot[k] = mu0[k];
         }
     }
+    if constexpr (SM) {
+        // the running smoothed / filtered sums live in the caller's arrays (every thread its own steps): a fresh chain starts
+        // them at zero whatever those hold, as the register-resident kernel's sm_acc / fm_acc do; a RESUME call reads them back
+        if (!p.resume) {
+            for (int l = 0; l < L; ++l) {
+                const int t = t0 + l;
+                if (t < T) {
+#pragma unroll
+                    for (int q = 0; q < K; ++q) {
+                        if (p.pi_smooth_mean) p.pi_smooth_mean[((size_t)w * p.ldY + t) * K + q] = 0.0;
+                        if (p.pi_filter_mean) p.pi_filter_mean[((size_t)w * p.ldY + t) * K + q] = 0.0;
+                    }
+                }
+            }
+        }
+    }
     if (tid < 8) xs[cap + tid] = 0;
     __syncthreads();
     int x_end = xs[T - 1];

@@ -150,7 +150,12 @@ typedef struct hmcg_extras {
                                    P(X_t | Y_1:T, theta) in sorted labels = the draw-average of the reference's
                                    samples.pib[:, t, :] (backwardupdate_P!, src/Hmc.jl:442-457, sorted :513).  Every K and every
                                    supported T (the LDS-resident kernel needs extras.pif_final on the device entry); about
-                                   half as many draws per second as without.  NULL: only pib[end,:] is produced */
+                                   half as many draws per second as without.  NULL: only pib[end,:] is produced.
+                                   Buffer contents: a call without HMCG_FLAG_RESUME does not depend on what pi_smooth_mean /
+                                   pi_filter_mean hold on entry (the chain's running sums start at zero on every kernel; steps
+                                   t >= T[w] and skipped windows are left untouched).  A call that stops short (sweep_count)
+                                   leaves the raw running sums in them; the RESUME call that continues it reads them back
+                                   from the same buffers and the call that ends the run turns them into means */
     double* pi_filter_mean;     /* [W][ldY][K] optional: the same draw average for the FILTERED probabilities pif[t,:] in
                                    sorted labels (what the reference's older API returned as "pib" and averaged per date in
                                    data/output/official_insample/forecats_insample.csv, columns s1..s3).  Runs on the same

@@ -157,11 +157,12 @@ def signal_ranges(Tw):
     return sig, save
 
 
-def check_smoothing_against_oracle(oracle, Y, Tw, K, burnin, nrun, yreal, sig=None, ssig=None, n_samples=1):
+def check_smoothing_against_oracle(oracle, Y, Tw, K, burnin, nrun, yreal, sig=None, ssig=None, n_samples=1,
+                                   run=_lib.estimate_batch_host, **more):
     """extras.pi_smooth_mean / pi_filter_mean against the mean of the oracle's literal Pb recursion and its running filtered
     mean, with every other output; sig: on the signal path (as test_smoothed_means_on_the_signal_path_lds_resident_kernel)."""
     kw = dict(sig_range=sig, save_range=sig, sigma_signal=ssig, kappa=0.6, n_samples=n_samples, alpha=2.0, nu=2.0) if sig is not None else {}
-    g = _lib.estimate_batch_host(Y, Tw, K, burnin, nrun, (12,), yreal, want_state=True, want_smooth=True, want_filter_mean=True, **kw)
+    g = run(Y, Tw, K, burnin, nrun, (12,), yreal, want_state=True, want_smooth=True, want_filter_mean=True, **kw, **more)
     for w in range(Y.shape[0]):
         T = int(Tw[w])
         if sig is not None:
@@ -183,6 +184,8 @@ def check_smoothing_against_oracle(oracle, Y, Tw, K, burnin, nrun, yreal, sig=No
         assert np.max(np.abs(g["pi_smooth_mean"][w, :T] - o["pi_smooth"].mean(axis=0))) < TOL, w
         assert np.max(np.abs(g["pi_filter_mean"][w, :T] - fmean)) < TOL, w
         assert np.max(np.abs(g["pi_smooth_mean"][w, :T].sum(axis=1) - 1)) < 1e-12
+        if "pi_smooth_draws" in g:                               # asked for through `more`: samples.pib[Nrun, N, D] itself
+            assert np.max(np.abs(np.transpose(g["pi_smooth_draws"][w, :, :T, :], (2, 1, 0)) - o["pi_smooth"])) < TOL, w
     return g
 
 

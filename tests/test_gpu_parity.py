@@ -19,9 +19,10 @@ def close(g, o, tol=TOL):
     return float(np.max(np.abs(g - o) / (1.0 + np.abs(o)))) if g.size else 0.0
 
 
-def check_against_oracle(oracle, Y, Tw, K, burnin, nrun, horizons=(12,), yreal=None, window_ids=None, seed=1234, **kw):
-    g = _lib.estimate_batch_host(Y, Tw, K, burnin, nrun, horizons, yreal, seed=seed, want_state=True,
-                                 window_ids=window_ids, **kw)
+def check_against_oracle(oracle, Y, Tw, K, burnin, nrun, horizons=(12,), yreal=None, window_ids=None, seed=1234,
+                         run=_lib.estimate_batch_host, **kw):
+    """run: the entry under test with estimate_batch_host's interface (tests/device_entry.py has the device entry's)."""
+    g = run(Y, Tw, K, burnin, nrun, horizons, yreal, seed=seed, want_state=True, window_ids=window_ids, **kw)
     W = Y.shape[0]
     for w in range(W):
         wid = w if window_ids is None else int(window_ids[w])
@@ -93,10 +94,11 @@ def test_cfg4_shape_8_states_T5000(hmclib, oracle):
         assert np.max(np.abs(gt["pif_final"][w] - o["pif_final"])) < TOL
 
 
-def check_signals_against_oracle(oracle, Y, Tw, K, burnin, nrun, n_samples, sig, save, kappa, alpha, nu, ssig, yreal):
+def check_signals_against_oracle(oracle, Y, Tw, K, burnin, nrun, n_samples, sig, save, kappa, alpha, nu, ssig, yreal,
+                                 run=_lib.estimate_batch_host):
     W = Y.shape[0]
-    g = _lib.estimate_batch_host(Y, Tw, K, burnin, nrun, (12,), yreal, want_state=True, sig_range=sig, save_range=save,
-                                 sigma_signal=ssig, kappa=kappa, n_samples=n_samples, alpha=alpha, nu=nu, want_sample_summary=True)
+    g = run(Y, Tw, K, burnin, nrun, (12,), yreal, want_state=True, sig_range=sig, save_range=save,
+            sigma_signal=ssig, kappa=kappa, n_samples=n_samples, alpha=alpha, nu=nu, want_sample_summary=True)
     for w in range(W):
         o = oracle.estimate_signals(Y[w, :Tw[w]], K, burnin, nrun, n_samples, sig=tuple(sig[w]), kappa=kappa, alpha=alpha,
                                     nu=nu, sigma_signal=float(ssig[w]), save=tuple(save[w]), yreal=yreal[w], window_id=w)
@@ -109,6 +111,40 @@ def check_signals_against_oracle(oracle, Y, Tw, K, burnin, nrun, n_samples, sig,
         assert close(g["sigvals"][w][:, :ns], o["sigvals"]) < TOL
         assert close(g["pif_final"][w, :Tw[w]], o["pif_final"]) < TOL
         assert close(g["sample_summary"][w], o["sample_summary"]) < TOL          # runaggregate's (date, signalid) rows
+    return g
+
+
+def check_tail_signals_against_oracle(oracle, Y, Tw, K, burnin, nrun, n_samples, sig, save, ssig, end_pos, horizons, yreal, sigLen,
+                                      want_sample_summary=False, run=_lib.estimate_batch_host):
+    """Signals past the end date (end_pos, blend_mask = 1; kappa = 0.6, alpha = nu = 2) against the oracle, window by window."""
+    more = dict(want_sample_summary=True) if want_sample_summary else {}
+    g = run(Y, Tw, K, burnin, nrun, horizons, yreal, want_state=True, sig_range=sig, save_range=save,
+            sigma_signal=ssig, kappa=0.6, n_samples=n_samples, alpha=2.0, nu=2.0, end_pos=end_pos, blend_mask=1, **more)
+    for w in range(Y.shape[0]):
+        o = oracle.estimate_signals(Y[w, :Tw[w]], K, burnin, nrun, n_samples, sig=tuple(sig[w]), kappa=0.6, alpha=2.0, nu=2.0,
+                                    sigma_signal=float(ssig[w]), save=tuple(save[w]), horizons=horizons, yreal=yreal[w],
+                                    window_id=w, end_pos=int(end_pos[w]), blend_mask=1)
+        assert g["status"][w] == o["status"] == 0
+        assert np.array_equal(g["x_final"][w, :Tw[w]], o["x_final"])
+        for k, go in (("mu", g["mu"][w].T), ("sig2", g["sig2"][w].T), ("pi_end", g["pi_end"][w].T), ("fcast", g["fcast"][w].T)):
+            assert close(go, o[k]) < TOL, (w, k)
+        assert close(g["summary"][w], o["summary"]) < TOL
+        if want_sample_summary:
+            assert close(g["sample_summary"][w], o["sample_summary"]) < TOL
+        assert close(g["sigvals"][w][:, :sigLen], o["sigvals"]) < TOL
+        assert np.max(np.abs(g["pi_end"][w].sum(axis=0) - 1)) < 1e-12
+    return g
+
+
+def check_teacher_forced_against_oracle(oracle, Y, Tw, K, x_init, run=_lib.estimate_batch_host):
+    """One sweep from given states (full-length windows): the redrawn states exact, the filtered-probability path and the
+    parameter draws within TOL."""
+    g = run(Y, Tw, K, 0, 1, (), None, x_init=x_init, want_state=True)
+    for w in range(Y.shape[0]):
+        o = oracle.estimate_window(Y[w], K, 0, 1, (), None, window_id=w, x_init=x_init[w])
+        assert np.array_equal(g["x_final"][w], o["x_final"])
+        assert np.max(np.abs(g["pif_final"][w] - o["pif_final"])) < TOL
+        assert close(g["mu"][w].T, o["mu"]) < TOL and close(np.transpose(g["A"][w], (2, 1, 0)), o["A"]) < TOL
     return g
 
 
@@ -151,19 +187,7 @@ def test_signal_path_signals_past_the_end_date(hmclib, oracle, K, T, sigLen):
     ssig = np.array([0.4, 1.3, 0.05])
     horizons = (0, 12)                           # device horizons: slot 0 is the blend (h == sigLen), slot 1 is h = sigLen + 12
     yreal = np.stack([fut[:, 0], fut[:, 11]], axis=1)
-    g = _lib.estimate_batch_host(Y, Tw, K, 4, 10, horizons, yreal, want_state=True, sig_range=sig, save_range=save,
-                                 sigma_signal=ssig, kappa=0.6, n_samples=3, alpha=2.0, nu=2.0, end_pos=end_pos, blend_mask=1)
-    for w in range(W):
-        o = oracle.estimate_signals(Y[w, :Tw[w]], K, 4, 10, 3, sig=tuple(sig[w]), kappa=0.6, alpha=2.0, nu=2.0,
-                                    sigma_signal=float(ssig[w]), save=tuple(save[w]), horizons=horizons, yreal=yreal[w],
-                                    window_id=w, end_pos=int(end_pos[w]), blend_mask=1)
-        assert g["status"][w] == o["status"] == 0
-        assert np.array_equal(g["x_final"][w, :Tw[w]], o["x_final"])
-        for k, go in (("mu", g["mu"][w].T), ("sig2", g["sig2"][w].T), ("pi_end", g["pi_end"][w].T), ("fcast", g["fcast"][w].T)):
-            assert close(go, o[k]) < TOL, (w, k)
-        assert close(g["summary"][w], o["summary"]) < TOL
-        assert close(g["sigvals"][w][:, :sigLen], o["sigvals"]) < TOL
-        assert np.max(np.abs(g["pi_end"][w].sum(axis=0) - 1)) < 1e-12
+    check_tail_signals_against_oracle(oracle, Y, Tw, K, 4, 10, 3, sig, save, ssig, end_pos, horizons, yreal, sigLen)
     # end_pos at the last step is the plain path, bit for bit
     a = _lib.estimate_batch_host(Y, Tw, K, 4, 10, (12,), yreal[:, 1:], sig_range=sig, sigma_signal=ssig, kappa=0.6, n_samples=2,
                                  end_pos=Tw - 1)
@@ -242,12 +266,7 @@ def test_teacher_forced_single_sweep(hmclib, oracle):
     W, T, K = 6, 1000, 3
     Y, Tw, _ = synth.generate_panel(W, T, K)
     X0 = rng.integers(0, K, size=(W, T)).astype(np.int32)
-    g = _lib.estimate_batch_host(Y, Tw, K, 0, 1, (), None, x_init=X0, want_state=True)
-    for w in range(W):
-        o = oracle.estimate_window(Y[w], K, 0, 1, (), None, window_id=w, x_init=X0[w])
-        assert np.array_equal(g["x_final"][w], o["x_final"])
-        assert np.max(np.abs(g["pif_final"][w] - o["pif_final"])) < TOL
-        assert close(g["mu"][w].T, o["mu"]) < TOL and close(np.transpose(g["A"][w], (2, 1, 0)), o["A"]) < TOL
+    check_teacher_forced_against_oracle(oracle, Y, Tw, K, X0)
 
 
 def test_real_data_expanding_windows(hmclib, oracle, inflation):
@@ -616,17 +635,7 @@ def test_signals_past_the_end_date_on_the_lds_resident_kernel(hmclib, oracle, mo
     yreal = np.stack([fut[:, 0], fut[:, 11]], axis=1)
     kw = dict(sig_range=sig, save_range=sig, sigma_signal=ssig, kappa=0.6, n_samples=3, alpha=2.0, nu=2.0, end_pos=end_pos, blend_mask=1,
               want_sample_summary=True)
-    g = _lib.estimate_batch_host(Y, Tw, K, 4, 10, horizons, yreal, want_state=True, **kw)
-    for w in range(W):
-        o = oracle.estimate_signals(Y[w, :Tw[w]], K, 4, 10, 3, sig=tuple(sig[w]), kappa=0.6, alpha=2.0, nu=2.0, sigma_signal=float(ssig[w]),
-                                    save=tuple(sig[w]), horizons=horizons, yreal=yreal[w], window_id=w, end_pos=int(end_pos[w]), blend_mask=1)
-        assert g["status"][w] == o["status"] == 0
-        assert np.array_equal(g["x_final"][w, :Tw[w]], o["x_final"])
-        for k, go in (("mu", g["mu"][w].T), ("sig2", g["sig2"][w].T), ("pi_end", g["pi_end"][w].T), ("fcast", g["fcast"][w].T)):
-            assert close(go, o[k]) < TOL, (w, k)
-        assert close(g["summary"][w], o["summary"]) < TOL and close(g["sample_summary"][w], o["sample_summary"]) < TOL
-        assert close(g["sigvals"][w][:, :sigLen], o["sigvals"]) < TOL
-        assert np.max(np.abs(g["pi_end"][w].sum(axis=0) - 1)) < 1e-12
+    g = check_tail_signals_against_oracle(oracle, Y, Tw, K, 4, 10, 3, sig, sig, ssig, end_pos, horizons, yreal, sigLen, want_sample_summary=True)
     monkeypatch.setenv("HMCG_FORCE_STREAM", "1")
     monkeypatch.setenv("HMCG_CHUNK_DRAWS", "7")
     s = _lib.estimate_batch_host(Y, Tw, K, 4, 10, horizons, yreal, want_state=True, **kw)

@@ -3,13 +3,18 @@ gibbs_sweeps_kernel<K, L, NT, SIG, SM, NH, OCC> (the three flavours of each HMCG
 gibbs_sweeps_kernel_big<K, 256, SM, ST, SIG> (8 forms x K = 2..8) -- is named by an oracle-parity case of the GPU suite, and no
 case names a kernel that is not compiled.  The tables are parsed from csrc/variants.hpp and csrc/variants_*.hip and held
 against the kernel symbols of the built libhmcgibbs.so, so that a regex which silently drops a row fails here; the cases are
-the parametrize lists of the GPU tests themselves (importing those modules needs no GPU)."""
+the parametrize lists of the GPU tests themselves (importing those modules needs no GPU).
+
+The device entry's contract is held the same way: every pointer member of hmcg_extras (parsed from include/hmcg.h) is passed by
+some case of tests/test_gpu_device_entry.py, and its split-chain table covers every kernel form."""
 import os
 import re
 import shutil
 import subprocess
 
+import device_entry
 import test_gpu_big_variants as big
+import test_gpu_device_entry as dev
 import test_gpu_parity as parity
 import test_gpu_variants as reg
 from hmc_jl_amd import _lib
@@ -116,3 +121,95 @@ def test_depth_cases_stay_beyond_the_ladder():
     for K in big.big_form_ks():
         assert {L for (k, L) in cases if k == K} >= {L for L in (8, 9, 16, 17) if 256 * L - 1 > big.ladder_ceiling(K, False, False)}, K
         assert (K, 17) in cases
+
+
+# ---- the device entry (tests/test_gpu_device_entry.py) ----
+HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "hmcg.h")
+
+
+def extras_pointer_members():
+    """The pointer members of `struct hmcg_extras`, in declaration order."""
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    body = re.search(r"typedef\s+struct\s+hmcg_extras\s*\{(.*?)\}\s*hmcg_extras\s*;", text, flags=re.S)
+    assert body, "struct hmcg_extras not found in include/hmcg.h"
+    members = [d.strip() for d in body.group(1).split(";") if d.strip()]
+    ptrs = [re.search(r"(\w+)$", d).group(1) for d in members if "*" in d]
+    assert len(members) == len(_lib.Extras._fields_), "include/hmcg.h and _lib.Extras disagree on the members of hmcg_extras"
+    return ptrs
+
+
+def test_extras_parse_matches_the_ctypes_binding():
+    import ctypes
+    ptrs = extras_pointer_members()
+    assert ptrs == [n for n, t in _lib.Extras._fields_ if t is ctypes.c_void_p]
+    assert len(ptrs) >= 16 and len(set(ptrs)) == len(ptrs)
+    # what the runner reports as passed is read from the struct it builds: a bare call passes none, a full one every member
+    import numpy as np
+    Y, T = np.zeros((2, 8)), np.array([8, 8])
+    assert device_entry.extras_passed(Y, T, 3, 1, 2) == set()
+    sig = np.array([[4, 8], [4, 8]])
+    full = dict(x_init=np.zeros((2, 8)), want_state=True, window_ids=[0, 1], sig_range=sig, save_range=sig, sigma_signal=[1.0, 1.0],
+                end_pos=[7, 7], want_sample_summary=True, want_smooth=True, want_filter_mean=True, want_smooth_draws=True, want_corr=True)
+    assert device_entry.extras_passed(Y, T, 3, 1, 2, **full) == set(ptrs)
+    assert "pif_final" not in device_entry.extras_passed(Y, T, 3, 1, 2, want_smooth=True, pass_pif=False)
+
+
+def test_every_extras_pointer_is_passed_on_the_device_entry():
+    """The runner builds each case's hmcg_extras with the code it runs on the GPU (over placeholder addresses) and the members
+    it sets are read from the struct.  A new member of hmcg_extras without a device-entry case fails here."""
+    cases = cases_of(dev.test_device_entry_against_oracle)
+    assert cases == dev.PARITY_CASES and cases_of(dev.test_fresh_call_ignores_buffer_contents) == dev.PARITY_CASES
+    passed = {}
+    for c in cases:
+        args, kw = dev.call_of(c)
+        got = device_entry.extras_passed(*args, **kw, **dev.device_kw(c))
+        assert got == dev.case_extras(c), c["id"]
+        for f in got:
+            passed.setdefault(f, c["id"])
+    missing = [f for f in extras_pointer_members() if f not in passed]
+    assert not missing, "no device-entry case passes extras." + ", extras.".join(missing)
+
+
+def test_device_entry_parity_cases_cover_every_family_and_path():
+    have = {(c["kernel"], c["path"]) for c in dev.PARITY_CASES}
+    want = {(k, "base") for k in ("register", "lds", "stream")} | {(k, p) for k in ("register", "lds") for p in ("sig", "tail", "smooth", "teacher")}
+    want.add(("stream", "smooth"))
+    assert want <= have, sorted(want - have)
+    assert any(c["bucketed"] for c in dev.PARITY_CASES) and any(c["kernel"] == "register" and not c["bucketed"] and len(set(c["lens"])) > 1 for c in dev.PARITY_CASES)
+    for c in dev.PARITY_CASES:
+        sig, smooth = c["path"] in ("sig", "tail"), c["path"] == "smooth"
+        top = max(c["lens"])
+        if c["kernel"] == "register":
+            assert top <= big.ladder_ceiling(c["K"], sig, smooth), c["id"]
+        else:                                                  # the production route to the LDS-resident kernel and its streaming form
+            assert top > big.ladder_ceiling(c["K"], sig, smooth), c["id"]
+            assert (big.dyn_bytes((top + 255) // 256) > big.LDS_LIMIT) == (c["kernel"] == "stream"), c["id"]
+
+
+def test_split_chain_table_covers_every_kernel_form():
+    cases = cases_of(dev.test_split_chain_equals_one_launch)
+    assert cases == dev.SPLIT_CASES
+    forms = {c["form"] for c in cases}
+    assert forms >= {"register", "lds", "streaming", "sig", "sm", "sig+sm"}, sorted(forms)
+    carried = set()
+    for c in cases:
+        args, kw = dev.call_of(c)
+        sig, smooth = "sig_range" in kw, "want_smooth" in kw
+        assert (c["form"] in ("sig", "sig+sm")) == sig and (c["form"] in ("sm", "sig+sm")) == smooth, c["id"]
+        if c["kernel"] == "register":
+            assert max(c["lens"]) <= big.ladder_ceiling(c["K"], sig, smooth), c["id"]
+        else:
+            assert max(c["lens"]) > big.ladder_ceiling(c["K"], sig, smooth) or ("HMCG_FORCE_BIG", "1") in c["env"], c["id"]
+        burnin, nrun = c["sweeps"]
+        per = burnin + nrun
+        # the cuts the issue of this table asks for: inside burn-in, exactly at burnin, after a kept draw, a three-piece run;
+        # on the signal path inside a sample before / after its first kept draw, at a sample boundary, inside a later sample
+        cuts = {s for sp in c["splits"] for s in sp}
+        assert any(0 < s < burnin for s in cuts) and any(len(sp) == 2 for sp in c["splits"]) or sig, c["id"]
+        if sig:
+            assert any(s < burnin for s in cuts) and any(burnin < s < per for s in cuts) and any(s % per == 0 for s in cuts) and any(s > per and s % per > burnin for s in cuts), c["id"]
+        else:
+            assert burnin in cuts and any(s > burnin for s in cuts), c["id"]
+        carried |= device_entry.extras_passed(*args, **kw) & set(device_entry.CARRIED)
+    assert carried == set(device_entry.CARRIED) - {"status"}, sorted(carried)
+    assert {v for c in cases for k, v in c["env"] if k == "HMCG_FLAVOUR"} == set(FLAVOUR)
