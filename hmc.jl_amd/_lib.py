@@ -4,6 +4,7 @@ The library is the product: hand-written HIP kernels for gfx950.  There is no
 CPU fallback anywhere in this package -- if the shared object is missing or no
 GPU is usable, the compute entry points raise.
 """
+import collections
 import ctypes as C
 import os
 import subprocess
@@ -153,6 +154,143 @@ def _np_ptr(a):
     return None if a is None else C.c_void_p(a.ctypes.data)
 
 
+# ---- one table of a call's buffers (the Python twin of host_buffers in csrc/host_util.hpp) ----
+Row = collections.namedtuple("Row", "name pos dtype shape io request carried nan")
+_f64, _i32 = np.float64, np.int32
+# name | position among the data pointers of hmcg_estimate_batch (None: the hmcg_extras member of that name) | dtype |
+# shape, in the symbols of call_dims | in / out | the request that makes an output present (None: always; want_*: that keyword
+# of build_call; draws, save_range, pif, checkpoint: see there); an input is present when it is given | a RESUME call reads
+# it back | NaN in a skipped window (estimate_batch_host)
+BUFFERS = tuple(Row(n, pos, dt, tuple(shape.split()), io, req, carried, nan) for n, pos, dt, shape, io, req, carried, nan in (
+    ("Y",               0,    _f64,      "W ldY",      "in",  None,                  False, False),
+    ("T",               1,    _i32,      "W",          "in",  None,                  False, False),
+    ("yreal",           2,    _f64,      "W H",        "in",  None,                  False, False),
+    ("mu",              3,    _f64,      "W K nd",     "out", "draws",               False, True),
+    ("sig2",            4,    _f64,      "W K nd",     "out", "draws",               False, True),
+    ("A",               5,    _f64,      "W K K nd",   "out", "draws",               False, True),
+    ("pi_end",          6,    _f64,      "W K nd",     "out", "draws",               False, True),
+    ("fcast",           7,    _f64,      "W 2H nd",    "out", "draws",               False, True),
+    ("summary",         8,    _f64,      "W NS",       "out", None,                  False, True),
+    ("status",          9,    _i32,      "W",          "out", None,                  True,  False),
+    ("x_init",          None, _i32,      "W ldY",      "in",  None,                  False, False),
+    ("window_ids",      None, np.uint32, "W",          "in",  None,                  False, False),
+    ("sig_range",       None, _i32,      "W 2",        "in",  None,                  False, False),    # the signal Monte-Carlo path (estimatesignals!)
+    ("save_range",      None, _i32,      "W 2",        "in",  None,                  False, False),
+    ("sigma_signal",    None, _f64,      "W",          "in",  None,                  False, False),
+    ("end_pos",         None, _i32,      "W",          "in",  None,                  False, False),    # signals past the end date (sigLen > 0)
+    ("sigvals",         None, _f64,      "W ns nsave", "out", "save_range",          False, True),
+    ("sample_summary",  None, _f64,      "W ns NS",    "out", "want_sample_summary", True,  True),
+    ("pi_smooth_draws", None, _f64,      "W K ldY nd", "out", "want_smooth_draws",   False, True),     # samples.pib[Nrun, N, D] of every window, draw index fastest
+    ("pi_smooth_mean",  None, _f64,      "W ldY K",    "out", "want_smooth",         True,  True),
+    ("pi_filter_mean",  None, _f64,      "W ldY K",    "out", "want_filter_mean",    True,  True),
+    ("corr",            None, _f64,      "W NC NC",    "out", "want_corr",           False, True),
+    ("x_final",         None, _i32,      "W ldY",      "out", "want_state",          False, False),
+    ("pif_final",       None, _f64,      "W ldY K",    "out", "pif",                 False, True),
+    ("xstate",          None, np.uint8,  "W ldY",      "out", "checkpoint",          True,  False),
+    ("sumacc",          None, _f64,      "W NS+K",     "out", "checkpoint",          True,  False)))
+DRAW_KEYS = tuple(r.name for r in BUFFERS if r.request == "draws")
+CARRIED = tuple(r.name for r in BUFFERS if r.carried)              # what a RESUME call reads back from the caller's buffers
+NAN_FILLED = tuple(r.name for r in BUFFERS if r.nan)                # every float output but sumacc, the checkpoint block
+ENTRY_OUTPUTS = tuple(r.name for r in BUFFERS if r.pos is not None and r.io == "out")
+
+
+def call_dims(W, ldY, K, nrun, H, n_samples=0, save_range=None):
+    """The dimension symbols of the BUFFERS shapes.  nd: kept draws per window (sample-major on the signal path); nsave:
+    hmcg_extras.nsave_ld, the longest save_range (an int32 (W, 2) array; None: no sigvals, 0)."""
+    NS, NC, ns = 3 * K + K * K + 2 * H, 3 * K + K * K + 1, max(int(n_samples), 1)
+    nsave = 0 if save_range is None else int(max(1, (save_range[:, 1] - save_range[:, 0]).max()))
+    return {"W": W, "ldY": ldY, "K": K, "H": H, "2H": 2 * H, "NS": NS, "NS+K": NS + K, "NC": NC, "ns": ns, "nd": ns * nrun,
+            "nsave": nsave, "2": 2}
+
+
+def call_shapes(dims):
+    return {r.name: tuple(dims[s] for s in r.shape) for r in BUFFERS}
+
+
+def build_call(store, Y, T, K, burnin, nrun, horizons=(12,), yreal=None, want_draws=True, resume=False, pif_with_smoothing=False,
+               max_T=None, **kw):
+    """One walk over BUFFERS for every runner: uploads the inputs that are given and allocates the outputs that are asked for
+    through `store`, and returns (hmcg_config, the ten data pointers of the C entry -- None: NULL --, hmcg_extras).
+    kw: the hmcg_extras inputs of BUFFERS by name, the want_* requests of its outputs, and make_config's keywords.
+    store.upload(name, array, dtype) and store.alloc(name, shape, dtype) return the buffer's address; the store keeps the
+    buffer and decides what it holds at first (zeros or a sentinel, an earlier call's buffer, what a RESUME call carries).
+    The signal-path inputs (save_range, sigma_signal, end_pos) are ignored without sig_range.  xstate / sumacc are passed with
+    want_state or resume; resume also sets HMCG_FLAG_RESUME.  Where the runners differ on purpose:
+      want_draws: True, False or the names of the draw arrays to keep; the others are passed as NULL (the host runner's;
+        the device runner always passes all five);
+      pif_with_smoothing: pif_final is passed with any smoothing output too, not with want_state alone (the device runner's:
+        the LDS-resident kernel needs it there);
+      max_T, and min_T in kw: hmcg_config's (the device runner's; the host runner leaves min(max T, ldY) and 0)."""
+    given = dict(Y=np.ascontiguousarray(Y, dtype=np.float64), T=T, yreal=yreal)
+    W, ldY = given["Y"].shape
+    given.update((r.name, kw.pop(r.name, None)) for r in BUFFERS if r.io == "in" and r.pos is None)
+    if given["sig_range"] is None:
+        given.update(save_range=None, sigma_signal=None, end_pos=None)
+    if given["save_range"] is not None:
+        given["save_range"] = np.ascontiguousarray(given["save_range"], dtype=np.int32).reshape(W, 2)
+    asked = {r.request: kw.pop(r.request, False) for r in BUFFERS if str(r.request).startswith("want_")}
+    smoothing = asked["want_smooth"] or asked["want_filter_mean"] or asked["want_smooth_draws"]
+    asked.update({None: True, "save_range": given["save_range"] is not None, "checkpoint": asked["want_state"] or resume,
+                  "pif": asked["want_state"] or (pif_with_smoothing and smoothing)})
+    keep = DRAW_KEYS if want_draws is True else tuple(want_draws or ())
+    shapes = call_shapes(call_dims(W, ldY, K, nrun, len(horizons), kw.get("n_samples", 0), given["save_range"]))
+    ex = Extras()
+    ex.struct_size, ex.nsave_ld = C.sizeof(Extras), shapes["sigvals"][2]
+    args = [None] * sum(r.pos is not None for r in BUFFERS)
+    for r in BUFFERS:
+        if r.io == "in" and given[r.name] is not None:
+            given[r.name] = np.ascontiguousarray(given[r.name], dtype=r.dtype).reshape(shapes[r.name])
+            addr = store.upload(r.name, given[r.name], r.dtype)
+        elif r.io == "out" and (r.name in keep if r.request == "draws" else asked[r.request]):
+            addr = store.alloc(r.name, shapes[r.name], r.dtype)
+        else:
+            continue
+        if r.pos is None:
+            setattr(ex, r.name, addr)
+        else:
+            args[r.pos] = addr
+    if max_T is None:
+        max_T = min(int(given["T"].max()), ldY)
+    return make_config(W, K, ldY, max_T, burnin, nrun, horizons, flags=FLAG_RESUME if resume else 0, **kw), args, ex
+
+
+def timing_result(tms):
+    """The timing keys of a result dict from a call's hmcg_timing records, one per device (None: an untimed call -- the
+    same keys, every value None)."""
+    tm = tms[0] if tms else Timing()
+    out = {k: getattr(tm, k) for k in ("kernel_ms", "threads_per_window", "steps_per_thread", "lds_bytes", "helper_waves",
+                                       "occupancy", "launches", "buckets")}
+    out["streaming"] = bool(tm.streaming)
+    out["call_ms"] = max(t.call_ms for t in tms or [tm])
+    out["per_device"] = [dict(device=t.device, windows=t.windows, kernel_ms=t.kernel_ms, call_ms=t.call_ms, launches=t.launches)
+                         for t in tms or []]
+    return out if tms else dict.fromkeys(out)
+
+
+class NumpyStore:
+    """build_call's store over host arrays.  Every output starts as zeros, but: the outputs that are arguments of the C entry
+    (the draws, summary, status) reuse the array of that name in `prev` -- an earlier result -- where shape, dtype and
+    contiguity match, as they stand except status, which is zeroed; an output named in `carry` (a RESUME call) is a copy of it."""
+
+    def __init__(self, prev=None, carry=None):
+        self.prev, self.carry, self.inp, self.out = prev or {}, carry or {}, {}, {}
+
+    def upload(self, name, a, dtype):
+        self.inp[name] = a                   # kept alive until the call is done
+        return a.ctypes.data
+
+    def alloc(self, name, shape, dtype):
+        a = self.prev.get(name) if name in ENTRY_OUTPUTS else None
+        if name in self.carry:
+            a = np.ascontiguousarray(self.carry[name], dtype=dtype).reshape(shape).copy()
+        elif not (isinstance(a, np.ndarray) and a.shape == shape and a.dtype == dtype and a.flags.c_contiguous):
+            a = np.zeros(shape, dtype=dtype)
+        elif name == "status":
+            a[:] = 0
+        self.out[name] = a
+        return a.ctypes.data
+
+
 def estimate_batch_host(Y, T, K, burnin, nrun, horizons=(12,), yreal=None, seed=1234, window_base=0, device=0,
                         threads_per_window=0, x_init=None, want_state=False, want_draws=True, alpha=0.0, nu=0.0,
                         resume_state=None, sweep_base=0, window_ids=None, sweep_count=0,
@@ -170,124 +308,39 @@ def estimate_batch_host(Y, T, K, burnin, nrun, horizons=(12,), yreal=None, seed=
     want_draws=False (the draws then never leave the device).
     want_sample_summary (signal path): out["sample_summary"] (W, n_samples, NS) -- per noise sample the mean over its kept
     draws of the 5-digit-rounded outputs (extras.sample_summary: the rows runaggregate makes per (date, signalid));
-    resume_sample_summary carries the buffer of a call that stopped inside a sample into its RESUME call."""
+    resume_sample_summary carries the buffer of a call that stopped inside a sample into its RESUME call.
+    resume_state: the result of the call this one continues; its status, xstate and sumacc are carried (the running smoothed /
+    filtered sums are not: a host RESUME call starts them at zero)."""
     L = load()
-    Y = np.ascontiguousarray(Y, dtype=np.float64)
-    W, ldY = Y.shape
-    T = np.ascontiguousarray(T, dtype=np.int32)
-    H = len(horizons)
-    NS = 3 * K + K * K + 2 * H
-    yr = None if yreal is None else np.ascontiguousarray(yreal, dtype=np.float64).reshape(W, H)
-    prev = out if out is not None else {}
-    out = {}
-    nd = max(int(n_samples), 1) * nrun          # kept draws per window (sample-major on the signal path)
-    shapes = dict(mu=(W, K, nd), sig2=(W, K, nd), A=(W, K, K, nd), pi_end=(W, K, nd), fcast=(W, 2 * H, nd))
-    keep = tuple(shapes) if want_draws is True else (tuple(want_draws) if want_draws else ())   # True, False or names
-
-    def buf(name, shape, dtype=np.float64):
-        a = prev.get(name)
-        return a if isinstance(a, np.ndarray) and a.shape == tuple(shape) and a.dtype == dtype and a.flags.c_contiguous else np.zeros(shape, dtype=dtype)
-    for name in keep:
-        out[name] = buf(name, shapes[name])
-    out["summary"] = buf("summary", (W, NS))
-    out["status"] = buf("status", (W,), np.int32)
-    if resume_state is None:
-        out["status"][:] = 0
-    ex = Extras()
-    ex.struct_size = C.sizeof(Extras)
-    flags = 0
-    if x_init is not None:
-        xi = np.ascontiguousarray(x_init, dtype=np.int32).reshape(W, ldY)
-        ex.x_init = xi.ctypes.data
-    if window_ids is not None:
-        wid = np.ascontiguousarray(window_ids, dtype=np.uint32).reshape(W)
-        ex.window_ids = wid.ctypes.data
-    if sig_range is not None:                      # signal Monte-Carlo path (estimatesignals!)
-        sr = np.ascontiguousarray(sig_range, dtype=np.int32).reshape(W, 2)
-        ex.sig_range = sr.ctypes.data
-        if save_range is not None:
-            svr = np.ascontiguousarray(save_range, dtype=np.int32).reshape(W, 2)
-            ex.save_range = svr.ctypes.data
-            nsave = int(max(1, (svr[:, 1] - svr[:, 0]).max()))
-            out["sigvals"] = np.zeros((W, max(int(n_samples), 1), nsave))
-            ex.sigvals = out["sigvals"].ctypes.data
-            ex.nsave_ld = nsave
-        if sigma_signal is not None:
-            ssg = np.ascontiguousarray(sigma_signal, dtype=np.float64).reshape(W)
-            ex.sigma_signal = ssg.ctypes.data
-        if end_pos is not None:                    # signals past the end date (sigLen > 0)
-            epos = np.ascontiguousarray(end_pos, dtype=np.int32).reshape(W)
-            ex.end_pos = epos.ctypes.data
-    if want_sample_summary:
-        out["sample_summary"] = (np.zeros((W, max(int(n_samples), 1), NS)) if resume_sample_summary is None else
-                                 np.ascontiguousarray(resume_sample_summary, dtype=np.float64).reshape(W, max(int(n_samples), 1), NS).copy())
-        ex.sample_summary = out["sample_summary"].ctypes.data
-    if want_smooth_draws:                      # samples.pib[Nrun, N, D] of every window: (W, K, ldY, nd), draw index fastest
-        out["pi_smooth_draws"] = np.zeros((W, K, ldY, nd))
-        ex.pi_smooth_draws = out["pi_smooth_draws"].ctypes.data
-    if want_smooth:
-        out["pi_smooth_mean"] = np.zeros((W, ldY, K))
-        ex.pi_smooth_mean = out["pi_smooth_mean"].ctypes.data
-    if want_filter_mean:
-        out["pi_filter_mean"] = np.zeros((W, ldY, K))
-        ex.pi_filter_mean = out["pi_filter_mean"].ctypes.data
-    if want_corr:
-        NC = 3 * K + K * K + 1
-        out["corr"] = np.zeros((W, NC, NC))
-        ex.corr = out["corr"].ctypes.data
-    if want_state:
-        out["x_final"] = np.zeros((W, ldY), dtype=np.int32)
-        out["pif_final"] = np.zeros((W, ldY, K))
-        out["xstate"] = np.zeros((W, ldY), dtype=np.uint8)
-        out["sumacc"] = np.zeros((W, NS + K))
-        ex.x_final = out["x_final"].ctypes.data
-        ex.pif_final = out["pif_final"].ctypes.data
-        ex.xstate = out["xstate"].ctypes.data
-        ex.sumacc = out["sumacc"].ctypes.data
-    if resume_state is not None:
-        flags |= FLAG_RESUME
-        out["xstate"] = np.ascontiguousarray(resume_state["xstate"], dtype=np.uint8).copy()
-        out["sumacc"] = np.ascontiguousarray(resume_state["sumacc"], dtype=np.float64).copy()
-        out["status"] = np.ascontiguousarray(resume_state["status"], dtype=np.int32).copy()
-        ex.xstate = out["xstate"].ctypes.data
-        ex.sumacc = out["sumacc"].ctypes.data
-    cfg = make_config(W, K, ldY, min(int(T.max()), ldY), burnin, nrun, horizons, seed, window_base, device, flags,
-                      threads_per_window, sweep_base, alpha, nu, sweep_count, kappa, n_samples, blend_mask)
+    carry = {} if resume_state is None else {k: resume_state[k] for k in ("status", "xstate", "sumacc")}
+    if resume_sample_summary is not None:
+        carry["sample_summary"] = resume_sample_summary
+    store = NumpyStore(out, carry)
+    cfg, args, ex = build_call(
+        store, Y, T, K, burnin, nrun, horizons, yreal, want_draws, resume_state is not None, seed=seed, window_base=window_base,
+        device=device, threads_per_window=threads_per_window, alpha=alpha, nu=nu, kappa=kappa, n_samples=n_samples,
+        blend_mask=blend_mask, sweep_base=sweep_base, sweep_count=sweep_count, x_init=x_init, window_ids=window_ids,
+        sig_range=sig_range, save_range=save_range, sigma_signal=sigma_signal, end_pos=end_pos, want_state=want_state,
+        want_sample_summary=want_sample_summary, want_smooth=want_smooth, want_filter_mean=want_filter_mean,
+        want_smooth_draws=want_smooth_draws, want_corr=want_corr)
+    args = [None if p is None else C.c_void_p(p) for p in args]
     if devices is None:
-        tm = Timing()
-        rc = L.hmcg_estimate_batch(C.byref(cfg), _np_ptr(Y), _np_ptr(T), _np_ptr(yr),
-                                   _np_ptr(out.get("mu")), _np_ptr(out.get("sig2")), _np_ptr(out.get("A")),
-                                   _np_ptr(out.get("pi_end")), _np_ptr(out.get("fcast")), _np_ptr(out["summary"]),
-                                   _np_ptr(out["status"]), C.byref(ex), C.byref(tm))
-        tms = [tm]
+        tms = (Timing * 1)()
+        rc = L.hmcg_estimate_batch(C.byref(cfg), *args, C.byref(ex), C.byref(tms[0]))
     else:
         devs = (C.c_int32 * len(devices))(*[int(d) for d in devices])
         tms = (Timing * len(devices))()
-        rc = L.hmcg_estimate_batch_multi(C.byref(cfg), C.c_int32(len(devices)), devs, _np_ptr(Y), _np_ptr(T), _np_ptr(yr),
-                                         _np_ptr(out.get("mu")), _np_ptr(out.get("sig2")), _np_ptr(out.get("A")),
-                                         _np_ptr(out.get("pi_end")), _np_ptr(out.get("fcast")), _np_ptr(out["summary"]),
-                                         _np_ptr(out["status"]), C.byref(ex), tms)
-        tm = tms[0]
+        rc = L.hmcg_estimate_batch_multi(C.byref(cfg), C.c_int32(len(devices)), devs, *args, C.byref(ex), tms)
     _check(rc)
+    out = store.out
     # a skipped window (non-finite data, bad T, bad ranges) was not computed: its outputs read NaN, never a
     # plausible-looking zero (the reference would have thrown, src/Hmc.jl:435)
     skipped = (out["status"] & ST_SKIPPED) != 0
     if skipped.any() and nan_fill:
-        for name in keep + ("summary", "sigvals", "pi_smooth_mean", "pi_filter_mean", "pif_final", "corr", "sample_summary", "pi_smooth_draws"):
+        for name in NAN_FILLED:
             if name in out:
                 out[name][skipped] = np.nan
-    out["kernel_ms"] = tm.kernel_ms
-    out["threads_per_window"] = tm.threads_per_window
-    out["steps_per_thread"] = tm.steps_per_thread
-    out["lds_bytes"] = tm.lds_bytes
-    out["helper_waves"] = tm.helper_waves
-    out["occupancy"] = tm.occupancy
-    out["launches"] = tm.launches
-    out["buckets"] = tm.buckets
-    out["streaming"] = bool(tm.streaming)
-    out["call_ms"] = max(t.call_ms for t in tms)
-    out["per_device"] = [dict(device=t.device, windows=t.windows, kernel_ms=t.kernel_ms, call_ms=t.call_ms, launches=t.launches)
-                         for t in tms]
+    out.update(timing_result(list(tms)))
     return out
 
 

@@ -8,6 +8,11 @@ import numpy as np
 from . import _lib
 
 
+def panel_shapes(W, ldY, K, nrun, H):
+    """The shapes of a DevicePanel's buffers by name: those of the call table (_lib.BUFFERS) for one chain per window."""
+    return _lib.call_shapes(_lib.call_dims(W, ldY, K, nrun, H))
+
+
 class DevicePanel:
     """A window panel resident in HBM plus its output buffers.
 
@@ -27,7 +32,8 @@ class DevicePanel:
         self.W, self.ldY = Y.shape
         self.K, self.nrun, self.horizons = int(K), int(nrun), tuple(horizons)
         H = len(self.horizons)
-        self.NS = 3 * K + K * K + 2 * H
+        shape = panel_shapes(self.W, self.ldY, K, nrun, H)
+        self.NS = shape["summary"][1]
         self.max_T = int(np.max(T))
         Tv = np.asarray(T)[np.asarray(T) >= 2]
         self.min_T = int(Tv.min()) if Tv.size else 0      # hint for the length-bucketed dispatch (hmcg_config.min_T)
@@ -38,18 +44,12 @@ class DevicePanel:
             np.ascontiguousarray(yreal, dtype=np.float64).reshape(self.W, H)).to(self.dev)
         self.window_ids = None if window_ids is None else torch.from_numpy(
             np.ascontiguousarray(window_ids, dtype=np.int64).astype(np.int32)).to(self.dev)
-        W = self.W
-        if keep_draws:
-            self.mu = torch.zeros((W, K, nrun), **f64); self.sig2 = torch.zeros((W, K, nrun), **f64)
-            self.A = torch.zeros((W, K, K, nrun), **f64); self.pi_end = torch.zeros((W, K, nrun), **f64)
-            self.fcast = torch.zeros((W, 2 * H, nrun), **f64)
-        else:
-            self.mu = self.sig2 = self.A = self.pi_end = self.fcast = None
-        self.summary = torch.zeros((W, self.NS), **f64)
-        self.status = torch.zeros(W, dtype=torch.int32, device=self.dev)
-        # extras.corr: (W, NC, NC) correlations between the per-draw outputs (calccorr), needs the draws on the device
-        NC = 3 * K + K * K + 1
-        self.corr = torch.zeros((W, NC, NC), **f64) if corr else None
+        for name in _lib.DRAW_KEYS:
+            setattr(self, name, torch.zeros(shape[name], **f64) if keep_draws else None)
+        self.summary = torch.zeros(shape["summary"], **f64)
+        self.status = torch.zeros(shape["status"], dtype=torch.int32, device=self.dev)
+        # extras.corr: correlations between the per-draw outputs (calccorr), needs the draws on the device
+        self.corr = torch.zeros(shape["corr"], **f64) if corr else None
         self.last_timing = None
         torch.cuda.synchronize(self.dev)   # fills above ran on torch's stream; the library uses its own
 

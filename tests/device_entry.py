@@ -24,14 +24,26 @@ from hmc_jl_amd import _lib
 
 SENTINEL = "sentinel"
 SENTINEL_BYTE = 0x5A
-TIMING_KEYS = ("kernel_ms", "threads_per_window", "steps_per_thread", "lds_bytes", "helper_waves", "occupancy", "launches",
-               "buckets", "streaming", "call_ms")
-DRAW_KEYS = ("mu", "sig2", "A", "pi_end", "fcast")
-# what a RESUME call reads back from the caller's buffers
-CARRIED = ("status", "xstate", "sumacc", "sample_summary", "pi_smooth_mean", "pi_filter_mean")
+TIMING_KEYS = tuple(_lib.timing_result(None))
+DRAW_KEYS, CARRIED = _lib.DRAW_KEYS, _lib.CARRIED
 
 
-class PlaceholderCall:
+class _Store:
+    """What the two stores of _lib.build_call below share: a buffer of an earlier call is used as it stands; a new one takes
+    resume_state's contents where a RESUME call reads it back (CARRIED)."""
+    prefill, resume_state = SENTINEL, None
+
+    def alloc(self, name, shape, dtype):
+        t = self.buf.get(name)
+        if t is None:
+            t = self.buf[name] = self.new(shape, dtype)
+            if self.resume_state is not None and name in CARRIED:
+                self.fill(t, np.ascontiguousarray(self.resume_state[name], dtype=dtype).reshape(shape))
+        assert tuple(t.shape) == tuple(shape), (name, tuple(t.shape), shape)
+        return t.data_ptr()
+
+
+class PlaceholderCall(_Store):
     """The buffer interface of DeviceCall over made-up non-null addresses: what extras_passed() builds a call on."""
 
     def __init__(self):
@@ -41,10 +53,12 @@ class PlaceholderCall:
         self.next += 0x1000
         return self.next
 
-    def alloc(self, name, shape, dtype, prefill):
+    def new(self, shape, dtype):
         self.next += 0x1000
-        self.buf[name] = _Placeholder(tuple(shape), self.next)
-        return self.buf[name]
+        return _Placeholder(tuple(shape), self.next)
+
+    def fill(self, t, a):
+        pass
 
 
 class _Placeholder:
@@ -54,11 +68,8 @@ class _Placeholder:
     def data_ptr(self):
         return self.ptr
 
-    def copy_(self, other):
-        pass
 
-
-class DeviceCall:
+class DeviceCall(_Store):
     """One call's device buffers: filled by prepare_call; enqueue() is the library call; collect() copies everything back."""
 
     def __init__(self, device=0):
@@ -88,26 +99,22 @@ class DeviceCall:
         self.inp[name] = t
         return t.data_ptr()
 
-    def alloc(self, name, shape, dtype, prefill):
+    def new(self, shape, dtype):
         torch = self.torch
         assert dtype in (np.float64, np.int32, np.uint8)
         tdt = {np.float64: torch.float64, np.int32: torch.int32, np.uint8: torch.uint8}[dtype]
-        if prefill is None:
-            t = torch.zeros(shape, dtype=tdt, device=self.dev)
-        elif dtype is np.float64:
-            t = torch.full(shape, float("nan"), dtype=tdt, device=self.dev)
-        else:
-            t = torch.full(shape, SENTINEL_BYTE * (0x01010101 if dtype is np.int32 else 1), dtype=tdt, device=self.dev)
-        self.buf[name] = t
-        return t
+        if self.prefill is None:
+            return torch.zeros(shape, dtype=tdt, device=self.dev)
+        if dtype is np.float64:
+            return torch.full(shape, float("nan"), dtype=tdt, device=self.dev)
+        return torch.full(shape, SENTINEL_BYTE * (0x01010101 if dtype is np.int32 else 1), dtype=tdt, device=self.dev)
+
+    def fill(self, t, a):
+        t.copy_(self.torch.from_numpy(a))
 
     def collect(self):
         out = {k: t.cpu().numpy() for k, t in self.buf.items()}
-        tm = self.timing
-        for k in TIMING_KEYS:
-            out[k] = None if tm is None else getattr(tm, k)
-        if tm is not None:
-            out["streaming"] = bool(tm.streaming)
+        out.update(_lib.timing_result(None if self.timing is None else [self.timing]))
         out["_call"] = self
         return out
 
@@ -119,87 +126,13 @@ def sentinel_like(a):
     return np.frombuffer(bytes([SENTINEL_BYTE]) * a.nbytes, dtype=a.dtype).reshape(a.shape)
 
 
-def _build(c, Y, T, K, burnin, nrun, horizons=(12,), yreal=None, seed=1234, window_base=0, window_ids=None,
-           threads_per_window=0, alpha=0.0, nu=0.0, x_init=None, want_state=False,
-           sig_range=None, save_range=None, sigma_signal=None, kappa=0.0, n_samples=0, end_pos=None, blend_mask=0,
-           want_sample_summary=False, want_smooth=False, want_filter_mean=False, want_smooth_draws=False,
-           want_corr=False, sweep_base=0, sweep_count=0, resume_state=None,
-           min_T=0, max_T=None, prefill=SENTINEL, out=None, pass_pif=True, device=0):
-    """Uploads the inputs and allocates the outputs through c (a DeviceCall, or a PlaceholderCall), builds hmcg_config and
-    hmcg_extras from the addresses and leaves them in c.launch."""
-    Y = np.ascontiguousarray(Y, dtype=np.float64)
-    W, ldY = Y.shape
-    T = np.ascontiguousarray(T, dtype=np.int32)
-    H = len(horizons)
-    NS = 3 * K + K * K + 2 * H
-    ns = max(int(n_samples), 1)
-    nd = ns * nrun
-    prev = None
-    if resume_state is not None and "_call" in resume_state:
-        prev = resume_state["_call"]
-    elif out is not None:
-        prev = out["_call"]
+def _build(c, *args, prefill=SENTINEL, out=None, pass_pif=True, resume_state=None, **kw):
+    """_lib.build_call over c (a DeviceCall, or a PlaceholderCall) with the device runner's options, left in c.launch."""
+    c.prefill, c.resume_state = prefill, resume_state
+    prev = resume_state if resume_state is not None and "_call" in resume_state else out
     if prev is not None:
-        c.buf = prev.buf                     # the same device buffers: nothing is prefilled, nothing reallocated
-
-    def buf(name, shape, dtype=np.float64):
-        t = c.buf.get(name)
-        if t is None:
-            t = c.alloc(name, shape, dtype, prefill)
-            if resume_state is not None and name in CARRIED:
-                import torch
-                t.copy_(torch.from_numpy(np.ascontiguousarray(resume_state[name], dtype=dtype).reshape(shape)))
-        assert tuple(t.shape) == tuple(shape), (name, tuple(t.shape), shape)
-        return t.data_ptr()
-
-    dY, dT = c.upload("Y", Y, np.float64), c.upload("T", T, np.int32)
-    dyreal = 0 if yreal is None else c.upload("yreal", np.asarray(yreal, dtype=np.float64).reshape(W, H), np.float64)
-    shapes = dict(mu=(W, K, nd), sig2=(W, K, nd), A=(W, K, K, nd), pi_end=(W, K, nd), fcast=(W, 2 * H, nd))
-    ptr = {name: buf(name, shapes[name]) for name in DRAW_KEYS}
-    ptr["summary"] = buf("summary", (W, NS))
-    ptr["status"] = buf("status", (W,), np.int32)
-    ex = _lib.Extras()
-    ex.struct_size = C.sizeof(_lib.Extras)
-    flags = 0
-    if x_init is not None:
-        ex.x_init = c.upload("x_init", np.asarray(x_init).reshape(W, ldY), np.int32)
-    if window_ids is not None:
-        ex.window_ids = c.upload("window_ids", np.asarray(window_ids).reshape(W), np.uint32)
-    if sig_range is not None:
-        ex.sig_range = c.upload("sig_range", np.asarray(sig_range).reshape(W, 2), np.int32)
-        if save_range is not None:
-            svr = np.ascontiguousarray(save_range, dtype=np.int32).reshape(W, 2)
-            ex.save_range = c.upload("save_range", svr, np.int32)
-            nsave = int(max(1, (svr[:, 1] - svr[:, 0]).max()))
-            ex.sigvals = buf("sigvals", (W, ns, nsave))
-            ex.nsave_ld = nsave
-        if sigma_signal is not None:
-            ex.sigma_signal = c.upload("sigma_signal", np.asarray(sigma_signal).reshape(W), np.float64)
-        if end_pos is not None:
-            ex.end_pos = c.upload("end_pos", np.asarray(end_pos).reshape(W), np.int32)
-    if want_sample_summary:
-        ex.sample_summary = buf("sample_summary", (W, ns, NS))
-    if want_smooth_draws:
-        ex.pi_smooth_draws = buf("pi_smooth_draws", (W, K, ldY, nd))
-    if want_smooth:
-        ex.pi_smooth_mean = buf("pi_smooth_mean", (W, ldY, K))
-    if want_filter_mean:
-        ex.pi_filter_mean = buf("pi_filter_mean", (W, ldY, K))
-    if want_corr:
-        NC = 3 * K + K * K + 1
-        ex.corr = buf("corr", (W, NC, NC))
-    if want_state or ((want_smooth or want_filter_mean or want_smooth_draws) and pass_pif):
-        ex.pif_final = buf("pif_final", (W, ldY, K))
-    if want_state:
-        ex.x_final = buf("x_final", (W, ldY), np.int32)
-    if want_state or resume_state is not None:
-        ex.xstate = buf("xstate", (W, ldY), np.uint8)
-        ex.sumacc = buf("sumacc", (W, NS + K))
-    if resume_state is not None:
-        flags |= _lib.FLAG_RESUME
-    cfg = _lib.make_config(W, K, ldY, min(int(T.max()), ldY) if max_T is None else max_T, burnin, nrun, horizons, seed, window_base,
-                           device, flags, threads_per_window, sweep_base, alpha, nu, sweep_count, kappa, n_samples, blend_mask, min_T)
-    c.launch = (cfg, (dY, dT, dyreal, ptr["mu"], ptr["sig2"], ptr["A"], ptr["pi_end"], ptr["fcast"], ptr["summary"], ptr["status"]), ex)
+        c.buf = prev["_call"].buf            # the same device buffers: nothing is prefilled, nothing reallocated
+    c.launch = _lib.build_call(c, *args, resume=resume_state is not None, pif_with_smoothing=pass_pif, **kw)
     return c
 
 

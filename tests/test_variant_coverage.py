@@ -18,6 +18,7 @@ import test_gpu_device_entry as dev
 import test_gpu_parity as parity
 import test_gpu_variants as reg
 from hmc_jl_amd import _lib
+from hmcg_header import extras_pointer_members
 
 FLAVOUR = {"p1": (0, 1), "p2": (0, 2), "h": (4, 2)}                      # (NH, OCC) of the three HMCG_V3 expansions
 PATH = {"base": (False, False), "sig": (True, False), "smooth": (False, True)}
@@ -124,20 +125,6 @@ def test_depth_cases_stay_beyond_the_ladder():
 
 
 # ---- the device entry (tests/test_gpu_device_entry.py) ----
-HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "hmcg.h")
-
-
-def extras_pointer_members():
-    """The pointer members of `struct hmcg_extras`, in declaration order."""
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
-    body = re.search(r"typedef\s+struct\s+hmcg_extras\s*\{(.*?)\}\s*hmcg_extras\s*;", text, flags=re.S)
-    assert body, "struct hmcg_extras not found in include/hmcg.h"
-    members = [d.strip() for d in body.group(1).split(";") if d.strip()]
-    ptrs = [re.search(r"(\w+)$", d).group(1) for d in members if "*" in d]
-    assert len(members) == len(_lib.Extras._fields_), "include/hmcg.h and _lib.Extras disagree on the members of hmcg_extras"
-    return ptrs
-
-
 def test_extras_parse_matches_the_ctypes_binding():
     import ctypes
     ptrs = extras_pointer_members()
