@@ -29,6 +29,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 #include "../../include/hmcg.h"
 #include "round5.hpp"
@@ -731,6 +732,14 @@ struct SweepShared {
     double pf_rep[2][K];
     double y_last[2];
 };
+// the helper flavour of the base path (counts first, sums beside wave 0's count-only draws: see the kernel) adds, behind the
+// common part, wave 0's states for the helper wave that takes its sums, and a second buffer of state-draw uniforms for
+// the part of a sweep's uniforms that is generated a sweep ahead
+template <int K, int L, int NT>
+struct SweepSharedSplit : SweepShared<K, L, NT, false> {
+    unsigned xw0[64];             // wave 0's L states of lane j, two bits each (a state is at most 3; padded steps: XPAD)
+    double ux2[NT * L];           // uniforms of the odd sweeps (the even ones': ux)
+};
 
 template <int NW>
 __device__ __forceinline__ double block_sum(double v, double* bred, int wave, int lane)
@@ -843,7 +852,7 @@ __device__ __forceinline__ void sort_order(const double (&mu)[K], int (&order)[K
 // csrc/Makefile `stamps`); the shipped kernel executes none.  Values leave the kernel only
 // through p.dbg, which no other code reads.
 #ifdef HMCG_STAMPS
-#define HMCG_NSTAMP 20
+#define HMCG_NSTAMP 23
 #define HMCG_NSTAMP_ALL (HMCG_NSTAMP + 2)   // + the sweep loop's total in s_memtime ticks and in s_memrealtime (100 MHz) ticks
 #define STAMP(i)                                                          \
     do {                                                                  \
@@ -878,7 +887,20 @@ void gibbs_sweeps_kernel(const KernelParams p)
     constexpr int KK = K * K;
     constexpr int NG = K + KK;           // gamma roles: sig2_i, then A_ij row-major
     static_assert(NG <= 64, "draw roles must fit wave 0");
-    using Sh = SweepShared<K, L, NT, SIG>;
+    // SPLIT (the helper flavour of the base path): the statistics are published in two parts.  The transition counts follow
+    // the apply step at once (barrier Ba = counts ready); then wave 0 draws everything that depends on the counts alone
+    // (shapes, both Marsaglia-Tsang attempts, the A rows, 1/gamma of the sig2 lanes) while waves 1..3 take the pivoted sums
+    // of their own steps and helper wave NW -- wave 0's SIMD partner, the younger wave there, which gets the issue slots the
+    // latency-bound draw chain leaves -- takes those of wave 0's steps; one more barrier (Ba2 = sums ready) and the sig2 /
+    // mu lanes finish.  Six block barriers per sweep, kept by all eight waves; no flags, no waiting loops.
+    // Four steps per thread only (T = 769..1024, the class it was measured on: +2.3 %).  The sums grow with L while wave 0's
+    // count-only chain does not (~2k cycles against ~0.25k L), so from L = 8 on Ba2 would wait for the sums; and the next
+    // sweep's RNG preparation, which leaves the window between Ba and Bb for the shadow of the forward filter (~4.5k cycles
+    // there, co-issued with a VALU-bound wave), would outlast that phase (2.4k .. 3.6k cycles) below L = 4.  The other
+    // classes keep the five-barrier loop.
+    constexpr bool SPLIT = NH > 0 && !SIG && L == 4;
+    static_assert(!SPLIT || (NH == 4 && NT * L <= 1024), "SPLIT deals exactly four uniform trips: three to helpers NW+1..NW+3, one ahead");
+    using Sh = typename std::conditional<SPLIT, SweepSharedSplit<K, L, NT>, SweepShared<K, L, NT, SIG>>::type;
     __shared__ Sh sh;
 
     int w_ = blockIdx.x;
@@ -1110,20 +1132,39 @@ void gibbs_sweeps_kernel(const KernelParams p)
     static_assert(NW > 2 || 3 * K + KK <= 64 - 2 * HMCG_MAXH, "parameter and forecast output lanes share a wave when NW == 2");
     // uniforms for the state draws of sweep `sw` (site 4, index t): block b covers t = 2b, 2b+1.
     // Blocks [b0, b1) are dealt round-robin to the calling wave's lanes.
+    // (SPLIT: the uniforms of sweep sw live in the buffer of its parity)
+    auto ux_of = [&](int sw) __attribute__((always_inline)) -> double* {
+        if constexpr (SPLIT) return (sw & 1) ? sh.ux2 : sh.ux;
+        else return sh.ux;
+    };
     auto job_uniforms = [&](int sw, int b0, int b1) __attribute__((always_inline)) {
         Rng g = rng;
         g.sweep = (uint32_t)sw;
+        double* const ub = ux_of(sw);
         for (int b = b0 + lane; b < b1; b += 128) {       // two independent blocks per trip (ILP across the mul chains)
             const int bb = b + 64;
             uint32_t r[4], q[4];
             g.block(SITE_X, 0, (uint32_t)b, r);
             g.block(SITE_X, 0, (uint32_t)bb, q);
-            sh.ux[2 * b] = u53(r[0], r[1]);
-            if (2 * b + 1 < NT * L) sh.ux[2 * b + 1] = u53(r[2], r[3]);
+            ub[2 * b] = u53(r[0], r[1]);
+            if (2 * b + 1 < NT * L) ub[2 * b + 1] = u53(r[2], r[3]);
             if (bb < b1) {
-                sh.ux[2 * bb] = u53(q[0], q[1]);
-                if (2 * bb + 1 < NT * L) sh.ux[2 * bb + 1] = u53(q[2], q[3]);
+                ub[2 * bb] = u53(q[0], q[1]);
+                if (2 * bb + 1 < NT * L) ub[2 * bb + 1] = u53(q[2], q[3]);
             }
+        }
+    };
+    // half a trip: blocks [b0, b1), b1 - b0 <= 64, one per lane
+    auto job_uniforms_half = [&](int sw, int b0, int b1) __attribute__((always_inline)) {
+        Rng g = rng;
+        g.sweep = (uint32_t)sw;
+        double* const ub = ux_of(sw);
+        const int b = b0 + lane;
+        if (b < b1) {
+            uint32_t r[4];
+            g.block(SITE_X, 0, (uint32_t)b, r);
+            ub[2 * b] = u53(r[0], r[1]);
+            if (2 * b + 1 < NT * L) ub[2 * b + 1] = u53(r[2], r[3]);
         }
     };
 
@@ -1329,6 +1370,145 @@ void gibbs_sweeps_kernel(const KernelParams p)
     constexpr int NPK = Sh::NPK;
     constexpr bool PADCNT = PADMARK && !SIG && NWORD == 1 && NF < FPW;    // counts without `t + 1 < T` predicates
     static_assert(64 * L < 65536, "wave totals fit their fields (10 bits while 64 L < 1024, else 16)");
+    // SPLIT takes the statistics in two parts: the integer counts (all that the gamma and Dirichlet draws need:
+    // publish_counts) and the pivoted sums (which enter the sig2 / mu draws only: publish_sums) -- the two halves of
+    // publish_stats below, statement for statement; every other flavour keeps publish_stats as it was.  The COUNTS half
+    // always describes the calling wave's OWN steps (it reads x, xnext, t0 and wave and ignores xs_, pv, tq0, dw: only
+    // publish_counts calls it).  The SUMS half takes the sums of the steps tq0 + l of the calling wave's lanes (states xs_,
+    // observations in its y[]) about the pivots pv and publishes them as wave dw's: a window's own wave passes its own
+    // (x, pivot, t0, wave); the helper wave stands in for wave 0.
+    auto publish = [&](auto with_counts, auto with_sums, const int (&xs_)[L], const double (&pv)[K], int tq0, int dw) __attribute__((always_inline)) {
+        constexpr bool COUNTS = decltype(with_counts)::value, SUMS = decltype(with_sums)::value;
+        static_assert(COUNTS != SUMS, "one half at a time: publish_stats is the whole");
+        unsigned pk[NPK];
+        if constexpr (COUNTS) {
+        // ---- transition counts C_ij: per-thread PB-bit fields -> 16-bit fields -> one DPP integer sum per word
+        unsigned acc[NWORD];
+#pragma unroll
+        for (int wd = 0; wd < NWORD; ++wd) acc[wd] = 0;
+#pragma unroll
+        for (int l = 0; l < L; ++l) {
+            const int xn = (l + 1 < L) ? x[(l + 1 < L) ? l + 1 : l] : xnext;
+            const int code = PADCNT ? x[l] + K * xn : x[l] * K + xn;
+            const bool pv = (t0 + l + 1) < T;
+            if constexpr (PADCNT) {
+                // field j*K+i for the pair i -> j: a pair whose successor is padded (xn = K; a padded step is never
+                // followed by a real one) has code >= K*K, and all of those land in the spare field K*K
+                acc[0] += 1u << (PB * min(code, KK));
+            } else if constexpr (NWORD == 1) {
+                acc[0] += pv ? (1u << (PB * code)) : 0u;
+            } else {
+#pragma unroll
+                for (int wd = 0; wd < NWORD; ++wd) {
+                    const int rel = code - wd * FPW;
+                    acc[wd] += (pv && rel >= 0 && rel < FPW) ? (1u << (PB * rel)) : 0u;
+                }
+            }
+            if constexpr (SIG) {                       // M_i: signal steps in state i
+                const int t = t0 + l;
+                const bool sv = t >= sb && t < se;
+                const int c2 = KK + x[l];
+#pragma unroll
+                for (int wd = 0; wd < NWORD; ++wd) {
+                    const int rel = c2 - wd * FPW;
+                    acc[wd] += (sv && rel >= 0 && rel < FPW) ? (1u << (PB * rel)) : 0u;
+                }
+            }
+        }
+#pragma unroll
+        for (int d = 0; d < NPK; ++d) {
+            unsigned v = 0;
+#pragma unroll
+            for (int q = 0; q < Sh::FPK; ++q) {
+                const int e = Sh::FPK * d + q;
+                if (e < NF) v |= ((acc[e / FPW] >> (PB * (e % FPW))) & ((1u << PB) - 1u)) << (Sh::FW * q);
+            }
+            pk[d] = v;
+        }
+        wave_sum_words_lane63<NPK>(pk);
+        }
+        if constexpr (SUMS) {
+        // ---- pivoted sums by state: d1_i = sum (y - pivot_i), d2_i = sum (y - pivot_i)^2 over the observation
+        // positions (and, on the signal path, the same two sums over the signal positions)
+        double d1[K], d2[K], s1[SIG ? K : 1], s2[SIG ? K : 1];
+#pragma unroll
+        for (int i = 0; i < K; ++i) { d1[i] = 0.0; d2[i] = 0.0; }
+        if constexpr (SIG) {
+#pragma unroll
+            for (int i = 0; i < K; ++i) { s1[i] = 0.0; s2[i] = 0.0; }
+        }
+#pragma unroll
+        for (int l = 0; l < L; ++l) {
+            double pvt = pv[0];
+#pragma unroll
+            for (int k = 1; k < K; ++k) pvt = (xs_[l] == k) ? pv[k] : pvt;
+            const double dl = y[l] - pvt;
+            const int t = tq0 + l;
+            const bool issig = SIG && t >= sb && t < se;
+            const int xs = PADMARK ? (issig ? -1 : xs_[l]) : ((t < T && !issig) ? xs_[l] : -1);
+#pragma unroll
+            for (int i = 0; i < K; ++i) {
+                const double dm = (xs == i) ? dl : 0.0;
+                d1[i] += dm;
+                d2[i] = fma(dm, dm, d2[i]);
+            }
+            if constexpr (SIG) {
+                const int xg = issig ? xs_[l] : -1;
+#pragma unroll
+                for (int i = 0; i < K; ++i) {
+                    const double dm = (xg == i) ? dl : 0.0;
+                    s1[i] += dm;
+                    s2[i] = fma(dm, dm, s2[i]);
+                }
+            }
+        }
+        if constexpr (SIG) {
+            static_assert(!SIG || K <= 4, "signal path: transposed reduce carries 2 x 4 slots");
+            double v8[8], o0, o1;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { v8[i] = i < K ? s1[i < K ? i : 0] : 0.0; v8[4 + i] = i < K ? s2[i < K ? i : 0] : 0.0; }
+            wave_sum8_transposed(v8, lane, o0, o1);
+            if ((lane & 0x3C) == 12) {
+                const int i0 = lane & 2, i1 = i0 + 1;
+                double* dst = (lane & 1) ? &sh.red_s2[dw][0] : &sh.red_s1[dw][0];
+                if (i0 < K) dst[i0] = o0;
+                if (i1 < K) dst[i1] = o1;
+            }
+        }
+        if constexpr (K <= 4) {
+            double v8[8], o0, o1;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { v8[i] = i < K ? d1[i] : 0.0; v8[4 + i] = i < K ? d2[i] : 0.0; }
+            wave_sum8_transposed(v8, lane, o0, o1);
+            if ((lane & 0x3C) == 12) {                 // lanes 12..15 hold the totals
+                const int i0 = lane & 2, i1 = i0 + 1;  // state index of o0 / o1; lane&1 picks d1 or d2
+                double* dst = (lane & 1) ? &sh.red_d2[dw][0] : &sh.red_d1[dw][0];
+                if (i0 < K) dst[i0] = o0;
+                if (i1 < K) dst[i1] = o1;
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < K; ++i) { d1[i] = wave_sum(d1[i]); d2[i] = wave_sum(d2[i]); }
+            if (lane == 0) {
+#pragma unroll
+                for (int i = 0; i < K; ++i) { sh.red_d1[dw][i] = d1[i]; sh.red_d2[dw][i] = d2[i]; }
+            }
+        }
+        }
+        if constexpr (COUNTS) {
+            if (lane == 63) {
+#pragma unroll
+                for (int d = 0; d < NPK; ++d) sh.red_pk[wave][d] = pk[d];
+            }
+        }
+        if (COUNTS ? tid == 0 : (dw == 0 && lane == 0)) {
+            if constexpr (SUMS) {
+#pragma unroll
+                for (int k = 0; k < K; ++k) sh.pivot[k] = pv[k];
+            }
+            if constexpr (COUNTS) sh.x_end = x_end;
+        }
+    };
     auto publish_stats = [&]() __attribute__((always_inline)) {
         // ---- transition counts C_ij: per-thread PB-bit fields -> 16-bit fields -> one DPP integer sum per word
         unsigned acc[NWORD];
@@ -1375,6 +1555,7 @@ void gibbs_sweeps_kernel(const KernelParams p)
             pk[d] = v;
         }
         wave_sum_words_lane63<NPK>(pk);
+        STAMP(19);
         // ---- pivoted sums by state: d1_i = sum (y - pivot_i), d2_i = sum (y - pivot_i)^2 over the observation
         // positions (and, on the signal path, the same two sums over the signal positions)
         double d1[K], d2[K], s1[SIG ? K : 1], s2[SIG ? K : 1];
@@ -1451,6 +1632,11 @@ void gibbs_sweeps_kernel(const KernelParams p)
             sh.x_end = x_end;
         }
     };
+    auto publish_counts = [&]() __attribute__((always_inline)) { publish(std::true_type(), std::false_type(), x, pivot, t0, wave); };
+    auto publish_sums = [&](const int (&xs_)[L], const double (&pv)[K], int tq0, int dw) __attribute__((always_inline)) {
+        publish(std::false_type(), std::true_type(), xs_, pv, tq0, dw);
+    };
+    (void)publish_counts; (void)publish_sums;
     // a new noise sample (src/Hmc.jl:892): Yfake = Yreal + N(0,1) * sigma_signal on the signal range; the chain
     // state carries over (:889-895) and the statistics are retaken on the new data
     auto regen_y = [&](int smp, bool report) __attribute__((always_inline)) {
@@ -1498,6 +1684,12 @@ void gibbs_sweeps_kernel(const KernelParams p)
         }
         trips = __builtin_amdgcn_readfirstlane(trips);
     }
+    // SPLIT: that deal serves a launch's first sweep only (the prologue took its statistics whole, so the window between Ba
+    // and Bb is as free as it used to be).  On every later sweep waves 1..3 and helper NW spend that window on the sums, so:
+    //   * trips 0..2 stay in the window, on helpers NW+1..NW+3 (the SIMD partners of waves 1..3: they take the issue slots
+    //     the sums leave, then the whole SIMD), half a trip on either side of Ba2 so that no helper is late for it;
+    //   * the fourth trip is generated A SWEEP AHEAD, into the other uniform buffer, by helper NW in the shadow of the
+    //     forward filter (it used to wait there for ~7.6k cycles); Philox is counter-based: same values.
     auto job_uniform_trips = [&](int sw) __attribute__((always_inline)) {
         const int nblk = (T + 1) >> 1;
         for (uint32_t m = trips; m != 0; m &= m - 1) {
@@ -1529,15 +1721,54 @@ void gibbs_sweeps_kernel(const KernelParams p)
     if constexpr (NH > 0) {
         if (helper) {
             // ---- helper waves: the draw-phase jobs, then only the sweep's barriers ----
+            if constexpr (SPLIT) {
+                // helper NW takes the sums of wave 0's steps: lane j stands in for wave 0's lane j
+                if (wave == NW) {
+#pragma unroll
+                    for (int l = 0; l < L; ++l) y[l] = (lane * L + l) < T ? p.Y[(size_t)w * p.ldY + lane * L + l] : 0.0;
+                }
+            }
             for (int sweep = p.sweep_begin; sweep < p.sweep_end; ++sweep) {
                 __syncthreads();                                             // Ba
                 STAMP(0);
-                if (wave == PREP_WAVE && sweep + 1 < p.sweep_end) job_prep(sweep + 1);
-                STAMP(15);
-                job_uniform_trips(sweep);
-                STAMP(1);
-                __syncthreads();                                             // Bb
-                STAMP(2);
+                if constexpr (SPLIT) {
+                    const bool first = sweep == p.sweep_begin;               // the prologue took counts and sums alike
+                    const int nblk = (T + 1) >> 1;
+                    const int hb = (wave - (NW + 1)) * 128;                  // helpers NW+1..: first block of their trip in the window
+                    if (wave == NW && !first) {
+                        const unsigned xw = sh.xw0[lane];
+                        int hx[L];
+                        double hp[K];
+#pragma unroll
+                        for (int l = 0; l < L; ++l) hx[l] = (int)((xw >> (2 * l)) & 3u);
+#pragma unroll
+                        for (int k = 0; k < K; ++k) hp[k] = sh.th[(sweep & 1) ^ 1].mu[k];   // the pivots: last sweep's state means
+                        publish_sums(hx, hp, lane * L, 0);
+                    }
+                    STAMP(13);
+                    if (first) job_uniform_trips(sweep);
+                    else if (hb >= 0) job_uniforms_half(sweep, hb, min(hb + 64, nblk));
+                    STAMP(1);
+                    __syncthreads();                                         // Ba2
+                    STAMP(20);
+                    if (!first && hb >= 0) job_uniforms_half(sweep, hb + 64, min(hb + 128, nblk));
+                    STAMP(21);
+                    __syncthreads();                                         // Bb
+                    STAMP(2);
+                    if (sweep + 1 < p.sweep_end) {
+                        if (wave == PREP_WAVE) job_prep(sweep + 1);
+                        STAMP(15);
+                        if (wave == NW) job_uniforms(sweep + 1, 3 * 128, min(4 * 128, nblk));   // the fourth trip, a sweep ahead
+                        STAMP(22);
+                    }
+                } else {
+                    if (wave == PREP_WAVE && sweep + 1 < p.sweep_end) job_prep(sweep + 1);
+                    STAMP(15);
+                    job_uniform_trips(sweep);
+                    STAMP(1);
+                    __syncthreads();                                         // Bb
+                    STAMP(2);
+                }
                 // the PREVIOUS sweep's per-draw outputs and forecasts (theta[par ^ 1] stays untouched until the next
                 // parameter phase), in the shadow of the primaries' pdf / product / scan phases (~5k cycles) -- not in the
                 // parameter phase, which the forecast job (2.3k cycles) would bound together with wave 0.  (Measured: in
@@ -1560,7 +1791,7 @@ void gibbs_sweeps_kernel(const KernelParams p)
             const int smp = sweep / p.per_sample;
             if (sweep == smp * p.per_sample) { regen_y(smp, true); publish_stats(); }
         }
-        __syncthreads();                                                     // Ba: statistics + rb[par] ready
+        __syncthreads();                                                     // Ba: statistics (SPLIT: the counts) + rb[par] ready
         STAMP(0);
         if (wave == 0) {
             // ---- parameter draws (sites 0,1,3; site 2 = rho comes ready-made from the shadow) ----
@@ -1595,6 +1826,12 @@ void gibbs_sweeps_kernel(const KernelParams p)
             if (is_g) {
                 const int c = is_sig ? rowsum + ((sh.x_end == role) ? 1 : 0) : cT;
                 if (is_sig) {
+                    if constexpr (SPLIT) {
+                        // what the count gives; what the sums add follows Ba2 (same statements as the block below)
+                        Neff = (double)c;
+                        shape = p.alpha + 0.5 * Neff;                                // :313
+                        rnn = rcp_fast(Neff + p.nu);
+                    } else {
                     double d1 = 0.0, d2 = 0.0;
 #pragma unroll
                     for (int ww = 0; ww < NW; ++ww) { d1 += sh.red_d1[ww][role]; d2 += sh.red_d2[ww][role]; }
@@ -1633,6 +1870,7 @@ void gibbs_sweeps_kernel(const KernelParams p)
                         shape = p.alpha + 0.5 * dNi + 0.5 * dMi;                                    // :313
                         rnn = rcp_fast(Neff + p.nu);
                         bpar = beta + 0.5 * S2 + (0.5 * kfac) * Sm2 + 0.5 * Neff * p.nu * rnn * (dm * dm);   // :314
+                    }
                     }
                 } else {
                     shape = (double)(c + 1);                                     // :362-365
@@ -1680,8 +1918,30 @@ void gibbs_sweeps_kernel(const KernelParams p)
             double gs = is_A ? val : 0.0;
             gs += quadperm_f64<0xB1>(gs);
             gs += quadperm_f64<0x4E>(gs);
+            if constexpr (SPLIT) {
+                if (is_sig) val = rcp_fast(val);                                 // sig2 lanes: 1 / Gamma(a, 1), ahead of the barrier
+                // the A rows are complete; the sig2 / mu lanes wait for the sums
+                if (is_A) th.A[qi][qj] = val * rcp_fast(gs);
+                STAMP(1);
+                __syncthreads();                                                 // Ba2: sums ready
+                STAMP(20);
+                if (is_sig) {
+                    const int c = rowsum + ((sh.x_end == role) ? 1 : 0);
+                    double d1 = 0.0, d2 = 0.0;
+#pragma unroll
+                    for (int ww = 0; ww < NW; ++ww) { d1 += sh.red_d1[ww][role]; d2 += sh.red_d2[ww][role]; }
+                    const double piv = sh.pivot[role];
+                    const double beta = (sweep == 0) ? 1.0 : 2.0;                // quirk 2 (:179, :347)
+                    const double rn = c > 0 ? rcp_fast(Neff) : 0.0;
+                    const double ybar = c > 0 ? piv + d1 * rn : 0.0;             // :259-265, :282-288
+                    const double S2 = c > 0 ? fmax(d2 - d1 * d1 * rn, 0.0) : 0.0;  // sum (y-ybar)^2 (:291-294)
+                    Ssum = piv * Neff + d1;                                      // sum of y in the state
+                    const double dm = ybar - xi;
+                    bpar = beta + 0.5 * S2 + 0.5 * Neff * p.nu * rnn * (dm * dm);   // :314
+                }
+            }
             if (is_sig) {
-                const double sig2 = bpar * rcp_fast(val);                        // :320 InverseGamma(a,b) = b / Gamma(a,1)
+                const double sig2 = bpar * (SPLIT ? val : rcp_fast(val));        // :320 InverseGamma(a,b) = b / Gamma(a,1)
                 const double m = (Ssum + p.nu * xi) * rnn;                       // :331
                 const double sdev = sqrt_fast(sig2 * rnn);                       // :332 sqrt(sig2/(Neff+nu))
                 const double mu = m + sdev * rb.z[role];                         // :334
@@ -1689,7 +1949,7 @@ void gibbs_sweeps_kernel(const KernelParams p)
                 th.mu[role] = mu; th.sig2[role] = sig2;
                 th.isd[role] = isd * 0.70710678118654752440; th.coef[role] = INVSQRT2PI * isd;
                 th.rho[role] = rb.rho[role];                                     // :355
-            } else if (is_A) {
+            } else if (!SPLIT && is_A) {
                 th.A[qi][qj] = val * rcp_fast(gs);
             }
         } else {
@@ -1698,9 +1958,18 @@ void gibbs_sweeps_kernel(const KernelParams p)
             // next sweep's RNG preparation (wave 1), and this sweep's (T+1)/2 Philox blocks of state-draw
             // uniforms, dealt to the shadow waves in proportion to what else they carry.
             const int nblk = (T + 1) >> 1;
+            if constexpr (SPLIT) {
+                if (sweep > p.sweep_begin) publish_sums(x, pivot, t0, wave);     // this wave's own steps (first sweep: the prologue's)
+                STAMP(13);
+            }
             if (sweep > p.sweep_begin) job_outputs(sweep - 1);
             STAMP(14);
-            if constexpr (NH > 0) {
+            if constexpr (SPLIT) {
+                if (sweep == p.sweep_begin) job_uniform_trips(sweep);
+                STAMP(1);
+                __syncthreads();                                                 // Ba2: sums ready
+                STAMP(20);
+            } else if constexpr (NH > 0) {
                 job_uniform_trips(sweep);
             } else if (NSH >= 3) {
                 // fixed jobs: wave 1 parameter outputs (~1.0k cycles), wave 2 RNG preparation (~1.5k), last
@@ -1731,7 +2000,7 @@ void gibbs_sweeps_kernel(const KernelParams p)
                 job_uniforms(sweep, shadow_wave * per, min((shadow_wave + 1) * per, nblk));
             }
         }
-        STAMP(1);
+        if constexpr (SPLIT) { STAMP(21); } else { STAMP(1); }
         __syncthreads();                                                     // Bb: theta[par], ux ready
         STAMP(2);
         // ---- everyone: parameters to registers ----
@@ -1746,7 +2015,7 @@ void gibbs_sweeps_kernel(const KernelParams p)
         sort_order<K>(mu, order);
         double ux[L];
 #pragma unroll
-        for (int l = 0; l < L; ++l) ux[l] = sh.ux[t0 + l];
+        for (int l = 0; l < L; ++l) ux[l] = ux_of(sweep)[t0 + l];
         // ---- forward filter (:371-440) as a scan of M_t = A diag(f_t) ----
         double f[L][K];
         unsigned und = 0;                            // bit l: every pdf of step l underflowed
@@ -2228,8 +2497,19 @@ void gibbs_sweeps_kernel(const KernelParams p)
 #pragma unroll
         for (int k = 0; k < K; ++k) pivot[k] = mu[k];
         STAMP(12);
-        publish_stats();
-        STAMP(13);
+        if constexpr (SPLIT) {
+            publish_counts();
+            if (wave == 0) {                         // wave 0's states, for the helper wave that takes its sums after Ba
+                unsigned xw = 0;
+#pragma unroll
+                for (int l = 0; l < L; ++l) xw |= (unsigned)x[l] << (2 * l);
+                sh.xw0[lane] = xw;
+            }
+            STAMP(19);
+        } else {
+            publish_stats();
+            STAMP(13);
+        }
     }
 #ifdef HMCG_STAMPS
     if (lane == 0 && p.dbg) {

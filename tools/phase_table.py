@@ -20,9 +20,9 @@ import subprocess
 import sys
 
 NAMES = ["Ba wait", "param draws | shadow jobs", "Bb wait", "theta+ux+pdfs", "local product", "wave scan", "Bc wait",
-         "prefix+replay+last", "Bd wait", "maps+compose", "map scan", "Be wait", "apply", "publish stats", "(shadow: outputs)",
-         "(shadow: prep)", "(param: counts+row sums)", "(param: shapes)", "(param: gamma)", "unused"]
-ROLES = {1, 14, 15, 16, 17, 18}
+         "prefix+replay+last", "Bd wait", "maps+compose", "map scan", "Be wait", "apply", "publish sums", "(shadow: outputs)",
+         "(shadow: prep)", "(param: counts+row sums)", "(param: shapes)", "(param: gamma)", "(stats: counts)", "Ba2 wait", "param finish | half trips", "(shadow: ux ahead)"]
+ROLES = {1, 13, 14, 15, 16, 17, 18, 19, 20, 21, 22}
 
 
 def cls(op):
