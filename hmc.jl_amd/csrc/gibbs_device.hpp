@@ -58,7 +58,7 @@ struct KernelParams {
     int32_t* status;
     const int32_t* x_init; int32_t* x_final; double* pif_final; uint8_t* xstate; double* sumacc;
     const uint32_t* window_ids;
-    unsigned long long* dbg;   // diagnostic (HMCG_STAMPS) builds only: per-wave phase cycle sums
+    unsigned long long* dbg;   // diagnostic (HMCG_STAMPS, HMCG_BARRIER_STAMPS) builds only: per-wave phase / barrier cycle sums
     // sampling schedule: n_samples consecutive blocks of (burnin_s discarded + nrun_s kept) sweeps; kept draw
     // d of global sweep g is (g / per_sample) * nrun_s + (g % per_sample - burnin_s); nd = n_samples * nrun_s
     // is the leading dimension of the per-draw outputs.  n_samples == 1 is the estimatemodel case.
@@ -867,6 +867,29 @@ __device__ __forceinline__ void sort_order(const double (&mu)[K], int (&order)[K
 #else
 #define STAMP(i)
 #endif
+// Barrier-arrival stamps: the second diagnostic level (-DHMCG_BARRIER_STAMPS, csrc/Makefile `barrier-stamps`).  The clock is
+// read only immediately before and immediately after each of a sweep's six block barriers and nothing else is pinned (no
+// sched_barrier, no wait of its own: the barrier's s_waitcnt lgkmcnt(0) covers the read before it), so the phases between
+// the barriers are scheduled as in the shipped build.  Per wave and barrier: ticks from the previous release to the arrival
+// (work) and from the arrival to the release (wait).  Barrier ids: Ba 0, Ba2 1, Bb 2, Bc 3, Bd 4, Be 5.
+#ifdef HMCG_BARRIER_STAMPS
+#ifdef HMCG_STAMPS
+#error "HMCG_STAMPS and HMCG_BARRIER_STAMPS are two builds: p.dbg holds one table"
+#endif
+#define HMCG_NBAR 6
+#define HMCG_NSTAMP_ALL (2 * HMCG_NBAR + 2)   // work[6], wait[6], the sweep loop's total in s_memtime and in s_memrealtime ticks
+#define SWEEP_BARRIER(i)                                                  \
+    do {                                                                  \
+        const unsigned long long a_ = __builtin_amdgcn_s_memtime();       \
+        __syncthreads();                                                  \
+        const unsigned long long r_ = __builtin_amdgcn_s_memtime();       \
+        bar_work[i] += a_ - stamp_prev;                                   \
+        bar_wait[i] += r_ - a_;                                           \
+        stamp_prev = r_;                                                  \
+    } while (0)
+#else
+#define SWEEP_BARRIER(i) __syncthreads()
+#endif
 
 // ------------------------------------------------------------- kernel ----
 
@@ -1362,6 +1385,10 @@ void gibbs_sweeps_kernel(const KernelParams p)
     unsigned long long stamp_acc[HMCG_NSTAMP];
     unsigned long long stamp_prev = 0;
 #endif
+#ifdef HMCG_BARRIER_STAMPS
+    unsigned long long bar_work[HMCG_NBAR], bar_wait[HMCG_NBAR];
+    unsigned long long stamp_prev = 0;
+#endif
     // per-wave partial statistics of the current X: counts, pivoted sums, transitions
     constexpr int PB = L <= 1 ? 1 : (L <= 3 ? 2 : (L <= 7 ? 3 : (L <= 15 ? 4 : 5)));   // bits holding a per-thread count <= L
     constexpr int FPW = 32 / PB;                       // per-thread fields per 32-bit word
@@ -1717,6 +1744,11 @@ void gibbs_sweeps_kernel(const KernelParams p)
     stamp_prev = __builtin_amdgcn_s_memtime();
     const unsigned long long stamp_t0 = stamp_prev, stamp_r0 = __builtin_amdgcn_s_memrealtime();
 #endif
+#ifdef HMCG_BARRIER_STAMPS
+    for (int i = 0; i < HMCG_NBAR; ++i) { bar_work[i] = 0; bar_wait[i] = 0; }
+    stamp_prev = __builtin_amdgcn_s_memtime();
+    const unsigned long long stamp_t0 = stamp_prev, stamp_r0 = __builtin_amdgcn_s_memrealtime();
+#endif
 
     if constexpr (NH > 0) {
         if (helper) {
@@ -1729,7 +1761,7 @@ void gibbs_sweeps_kernel(const KernelParams p)
                 }
             }
             for (int sweep = p.sweep_begin; sweep < p.sweep_end; ++sweep) {
-                __syncthreads();                                             // Ba
+                SWEEP_BARRIER(0);                                          // Ba
                 STAMP(0);
                 if constexpr (SPLIT) {
                     const bool first = sweep == p.sweep_begin;               // the prologue took counts and sums alike
@@ -1749,24 +1781,96 @@ void gibbs_sweeps_kernel(const KernelParams p)
                     if (first) job_uniform_trips(sweep);
                     else if (hb >= 0) job_uniforms_half(sweep, hb, min(hb + 64, nblk));
                     STAMP(1);
-                    __syncthreads();                                         // Ba2
+                    SWEEP_BARRIER(1);                                      // Ba2
                     STAMP(20);
                     if (!first && hb >= 0) job_uniforms_half(sweep, hb + 64, min(hb + 128, nblk));
                     STAMP(21);
-                    __syncthreads();                                         // Bb
+                    SWEEP_BARRIER(2);                                      // Bb
                     STAMP(2);
-                    if (sweep + 1 < p.sweep_end) {
-                        if (wave == PREP_WAVE) job_prep(sweep + 1);
-                        STAMP(15);
-                        if (wave == NW) job_uniforms(sweep + 1, 3 * 128, min(4 * 128, nblk));   // the fourth trip, a sweep ahead
-                        STAMP(22);
-                    }
+                    // The next sweep's RNG preparation (job_prep, statement for statement) as two stages with a barrier between
+                    // them: every lane's chain is cut in time, not by lanes -- Philox block, u53 and the log ahead of the cut;
+                    // Box-Muller, the rho normalisation and the stores behind it -- and carries r[2], r[3], uraw and lg in
+                    // registers.  Both stages of a sweep stand behind the same `more` condition, inside one loop iteration.
+                    constexpr int NTASK = 4 * NG + 2 * K, NPASS = (NTASK + 63) / 64;
+                    uint32_t pr2[NPASS], pr3[NPASS];
+                    double puraw[NPASS], plg[NPASS];
+                    auto prep_head = [&](int sw) __attribute__((always_inline)) {
+                        Rng g = rng;
+                        g.sweep = (uint32_t)sw;
+#pragma unroll
+                        for (int ps = 0; ps < NPASS; ++ps) {
+                            const int task = ps * 64 + lane;
+                            const bool t_rho = task < K;
+                            const bool t_gx = !t_rho && task < K + 2 * NG;
+                            const bool t_z = !t_rho && !t_gx && task < 2 * K + 2 * NG;
+                            const bool t_gl = !t_rho && !t_gx && !t_z;
+                            const int gt = t_gx ? task - K : task - (2 * K + 2 * NG);
+                            const int role = gt >> 1, j = gt & 1;
+                            uint32_t site = SITE_RHO, elem = (uint32_t)task, idx = 0;
+                            if (t_gx || t_gl) {
+                                site = role < K ? SITE_SIG2 : SITE_A;
+                                elem = role < K ? (uint32_t)role : (uint32_t)(role - K);
+                                idx = 2u * (uint32_t)j + (t_gl ? 1u : 0u);
+                            } else if (t_z) {
+                                site = SITE_MU; elem = (uint32_t)(task - (K + 2 * NG));
+                            }
+                            uint32_t r[4];
+                            g.block(site, elem, idx, r);
+                            puraw[ps] = u53(r[0], r[1]);
+                            plg[ps] = log_fast(1.0 - puraw[ps]);
+                            pr2[ps] = r[2]; pr3[ps] = r[3];
+                        }
+                    };
+                    auto prep_tail = [&](int sw) __attribute__((always_inline)) {
+                        RngBuf<K>& rb = sh.rb[sw & 1];
+#pragma unroll
+                        for (int ps = 0; ps < NPASS; ++ps) {
+                            const int task = ps * 64 + lane;
+                            const bool live = task < NTASK;
+                            const bool t_rho = task < K;
+                            const bool t_gx = !t_rho && task < K + 2 * NG;
+                            const bool t_z = !t_rho && !t_gx && task < 2 * K + 2 * NG;
+                            const bool t_gl = !t_rho && !t_gx && !t_z;
+                            const int gt = t_gx ? task - K : task - (2 * K + 2 * NG);
+                            const int role = gt >> 1, j = gt & 1;
+                            const double uraw = puraw[ps], lg = plg[ps];
+                            double val = lg;
+                            if (t_gx || t_z) val = sqrt_fast(-2.0 * lg) * cos2pi_fast(u53(pr2[ps], pr3[ps]));   // Box-Muller
+                            double rs = 0.0;
+#pragma unroll
+                            for (int i = 0; i < K; ++i) rs += -__shfl(lg, i, 64);
+                            if (live) {
+                                if (t_rho) rb.rho[task] = -lg * (1.0 / rs);
+                                else if (t_gx) rb.x[role][j] = val;
+                                else if (t_z) rb.z[task - (K + 2 * NG)] = val;
+                                else if (t_gl) { rb.lu[role][j] = val; rb.uu[role][j] = uraw; }
+                            }
+                        }
+                    };
+                    // The deal over the windows: the head of the preparation between Bb and Bc, where the
+                    // window's own waves are VALU-bound and a younger wave gets what they leave (measured unstamped: the whole
+                    // job there made all eight waves wait for helper NW + 1 at Bc); its tail between Bc and Bd, where that
+                    // helper's SIMD partner waits for the last wave's cross-wave prefix anyway.  rb[(sweep + 1) & 1] was last read
+                    // in sweep - 1's parameter phase and is read next at sweep + 1's Ba.
+                    const bool more = sweep + 1 < p.sweep_end;
+                    if (more && wave == PREP_WAVE) prep_head(sweep + 1);
+                    STAMP(15);
+                    if (more && wave == NW) job_uniforms(sweep + 1, 3 * 128, min(4 * 128, nblk));   // the fourth trip, a sweep ahead
+                    STAMP(22);
+                    if (!first) job_outputs(sweep - 1);                      // the previous sweep's outputs and forecasts (see below)
+                    STAMP(14);
+                    SWEEP_BARRIER(3);                                      // Bc
+                    if (more && wave == PREP_WAVE) prep_tail(sweep + 1);
+                    SWEEP_BARRIER(4);                                      // Bd
+                    SWEEP_BARRIER(5);                                      // Be
+                    STAMP(11);
+                    continue;
                 } else {
                     if (wave == PREP_WAVE && sweep + 1 < p.sweep_end) job_prep(sweep + 1);
                     STAMP(15);
                     job_uniform_trips(sweep);
                     STAMP(1);
-                    __syncthreads();                                         // Bb
+                    SWEEP_BARRIER(2);                                      // Bb
                     STAMP(2);
                 }
                 // the PREVIOUS sweep's per-draw outputs and forecasts (theta[par ^ 1] stays untouched until the next
@@ -1775,9 +1879,9 @@ void gibbs_sweeps_kernel(const KernelParams p)
                 // the shadow of the shorter backward pass instead, the helpers delayed barrier Be by ~0.9k cycles.)
                 if (sweep > p.sweep_begin) job_outputs(sweep - 1);
                 STAMP(14);
-                __syncthreads();                                             // Bc
-                __syncthreads();                                             // Bd
-                __syncthreads();                                             // Be
+                SWEEP_BARRIER(3);                                          // Bc
+                SWEEP_BARRIER(4);                                          // Bd
+                SWEEP_BARRIER(5);                                          // Be
                 STAMP(11);
             }
         }
@@ -1791,7 +1895,7 @@ void gibbs_sweeps_kernel(const KernelParams p)
             const int smp = sweep / p.per_sample;
             if (sweep == smp * p.per_sample) { regen_y(smp, true); publish_stats(); }
         }
-        __syncthreads();                                                     // Ba: statistics (SPLIT: the counts) + rb[par] ready
+        SWEEP_BARRIER(0);                                                  // Ba: statistics (SPLIT: the counts) + rb[par] ready
         STAMP(0);
         if (wave == 0) {
             // ---- parameter draws (sites 0,1,3; site 2 = rho comes ready-made from the shadow) ----
@@ -1923,7 +2027,7 @@ void gibbs_sweeps_kernel(const KernelParams p)
                 // the A rows are complete; the sig2 / mu lanes wait for the sums
                 if (is_A) th.A[qi][qj] = val * rcp_fast(gs);
                 STAMP(1);
-                __syncthreads();                                                 // Ba2: sums ready
+                SWEEP_BARRIER(1);                                              // Ba2: sums ready
                 STAMP(20);
                 if (is_sig) {
                     const int c = rowsum + ((sh.x_end == role) ? 1 : 0);
@@ -1967,7 +2071,7 @@ void gibbs_sweeps_kernel(const KernelParams p)
             if constexpr (SPLIT) {
                 if (sweep == p.sweep_begin) job_uniform_trips(sweep);
                 STAMP(1);
-                __syncthreads();                                                 // Ba2: sums ready
+                SWEEP_BARRIER(1);                                              // Ba2: sums ready
                 STAMP(20);
             } else if constexpr (NH > 0) {
                 job_uniform_trips(sweep);
@@ -2001,7 +2105,7 @@ void gibbs_sweeps_kernel(const KernelParams p)
             }
         }
         if constexpr (SPLIT) { STAMP(21); } else { STAMP(1); }
-        __syncthreads();                                                     // Bb: theta[par], ux ready
+        SWEEP_BARRIER(2);                                                  // Bb: theta[par], ux ready
         STAMP(2);
         // ---- everyone: parameters to registers ----
         double mu[K], isd[K], coef[K], rho[K], A[K][K];
@@ -2221,7 +2325,7 @@ void gibbs_sweeps_kernel(const KernelParams p)
             for (int i = 0; i < KK; ++i) sh.wtot[wave][i] = Q[i];
         }
         STAMP(5);
-        __syncthreads();                                                     // Bc
+        SWEEP_BARRIER(3);                                                  // Bc
         STAMP(6);
         // prefix vector: rho' * (totals of earlier waves) * (exclusive lane prefix)
         double av[K];
@@ -2404,7 +2508,7 @@ void gibbs_sweeps_kernel(const KernelParams p)
             }
         }
         STAMP(7);
-        __syncthreads();                                                     // Bd
+        SWEEP_BARRIER(4);                                                  // Bd
         STAMP(8);
         // ---- backward sampling (:459-484) as a suffix scan of state maps ----
         int xlast = 0;
@@ -2478,7 +2582,7 @@ void gibbs_sweeps_kernel(const KernelParams p)
         }
         if (lane == 0) sh.wmap[wave] = Hm;
         STAMP(10);
-        __syncthreads();                                                     // Be
+        SWEEP_BARRIER(5);                                                  // Be
         STAMP(11);
         uint32_t Rw = BMAP_IDENTITY;
 #pragma unroll
@@ -2517,6 +2621,14 @@ void gibbs_sweeps_kernel(const KernelParams p)
         for (int i = 0; i < HMCG_NSTAMP; ++i) o[i] = stamp_acc[i];
         o[HMCG_NSTAMP] = __builtin_amdgcn_s_memtime() - stamp_t0;             // in-kernel clock = ticks / realtime ticks * 100 MHz
         o[HMCG_NSTAMP + 1] = __builtin_amdgcn_s_memrealtime() - stamp_r0;
+    }
+#endif
+#ifdef HMCG_BARRIER_STAMPS
+    if (lane == 0 && p.dbg) {
+        unsigned long long* o = p.dbg + ((size_t)w * (NW + NH) + wave) * HMCG_NSTAMP_ALL;
+        for (int i = 0; i < HMCG_NBAR; ++i) { o[i] = bar_work[i]; o[HMCG_NBAR + i] = bar_wait[i]; }
+        o[2 * HMCG_NBAR] = __builtin_amdgcn_s_memtime() - stamp_t0;
+        o[2 * HMCG_NBAR + 1] = __builtin_amdgcn_s_memrealtime() - stamp_r0;
     }
 #endif
 

@@ -264,7 +264,7 @@ int plan_call(const hmcg_config* cfg, const hmcg_extras* ex, int W, int cu_count
     ov.force_big = diag_env("HMCG_FORCE_BIG") != nullptr;
     ov.no_buckets = diag_env("HMCG_NO_BUCKETS") != nullptr;
     ov.force_stream = diag_env("HMCG_FORCE_STREAM") != nullptr;
-#ifdef HMCG_STAMPS
+#if defined(HMCG_STAMPS) || defined(HMCG_BARRIER_STAMPS)
     ov.stamps = true;
 #endif
     const auto static_lds = [](const BigVariant& bv) { return static_lds_bytes(reinterpret_cast<const void*>(bv.fn), 48 * 1024); };
@@ -452,6 +452,63 @@ int print_stamps(const hmcg::KernelParams& p, const Plan& pl, unsigned long long
 }
 #endif
 
+#ifdef HMCG_BARRIER_STAMPS
+// The barrier-arrival build's table: per wave and sweep barrier the mean ticks from the previous release to the arrival (work)
+// and from the arrival to the release (wait).  Same switches and the same [clock] line as the phase-stamped build.
+int print_stamps(const hmcg::KernelParams& p, const Plan& pl, unsigned long long* ddbg, size_t ndbg, hipStream_t stream)
+{
+    static const char* names[HMCG_NBAR] = {"Ba", "Ba2", "Bb", "Bc", "Bd", "Be"};
+    HIP_TRY(hipStreamSynchronize(stream));
+    static int launches_seen = 0;
+    static const int print_after = diag_env("HMCG_STAMPS_AFTER") ? atoi(diag_env("HMCG_STAMPS_AFTER")) : 0;
+    if (launches_seen++ < print_after) return 0;
+    if (!pl.v) return 0;                        // the LDS-resident kernels carry no barrier stamps
+    const int nwv = pl.NT() / 64 + pl.NH();
+    std::vector<unsigned long long> h(ndbg);
+    HIP_TRY(hipMemcpy(h.data(), ddbg, ndbg * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    const int nsw = p.sweep_end - p.sweep_begin;
+    const double per = (double)p.W * (nsw > 0 ? nsw : 1);
+    {
+        std::vector<double> clk;
+        double ticks = 0;
+        for (int w = 0; w < p.W; ++w)
+            for (int wv = 0; wv < nwv; ++wv) {
+                const unsigned long long* o = &h[((size_t)w * nwv + wv) * HMCG_NSTAMP_ALL];
+                if (o[2 * HMCG_NBAR + 1]) { clk.push_back(100.0 * (double)o[2 * HMCG_NBAR] / (double)o[2 * HMCG_NBAR + 1]); ticks += (double)o[2 * HMCG_NBAR]; }
+            }
+        std::sort(clk.begin(), clk.end());
+        if (!clk.empty())
+            fprintf(stderr, "[clock] launch %d: in-kernel clock MHz min %.0f median %.0f max %.0f (s_memtime / s_memrealtime x 100 MHz); "
+                            "%.0f ticks per sweep (mean over waves)\n", launches_seen - 1, clk.front(), clk[clk.size() / 2], clk.back(),
+                    ticks / (double)clk.size() / (nsw > 0 ? nsw : 1));
+    }
+    fprintf(stderr, "[barrier stamps] K=%d L=%d NT=%d W=%d sweeps=%d: mean ticks per sweep by wave (s_memtime)\n",
+            pl.v->K, pl.L(), pl.NT(), p.W, nsw);
+    fprintf(stderr, "%-24s", "barrier");
+    for (int wv = 0; wv < nwv; ++wv) fprintf(stderr, "   wave%-2d", wv);
+    fprintf(stderr, "\n");
+    std::vector<double> tot(nwv, 0.0);
+    for (int i = 0; i < 2 * HMCG_NBAR; ++i) {
+        const int b = i / 2, slot = (i & 1) ? HMCG_NBAR + b : b;      // work to Ba, wait at Ba, work to Ba2, ...
+        char label[32];
+        snprintf(label, sizeof label, (i & 1) ? "%s wait" : "work -> %s", names[b]);
+        fprintf(stderr, "%-24s", label);
+        for (int wv = 0; wv < nwv; ++wv) {
+            double acc = 0;
+            for (int w = 0; w < p.W; ++w) acc += (double)h[((size_t)w * nwv + wv) * HMCG_NSTAMP_ALL + slot];
+            acc /= per;
+            tot[wv] += acc;
+            fprintf(stderr, " %8.0f", acc);
+        }
+        fprintf(stderr, "\n");
+    }
+    fprintf(stderr, "%-24s", "total");
+    for (int wv = 0; wv < nwv; ++wv) fprintf(stderr, " %8.0f", tot[wv]);
+    fprintf(stderr, "\n");
+    return 0;
+}
+#endif
+
 // ---- device-resident entry: one launch over caller-owned HBM buffers -----------------------------------------
 
 // Grows one of the device entry's context-owned arenas (scr, mom, ord).  An enqueue-only call on any stream may still be
@@ -508,7 +565,7 @@ int launch_device(DeviceCtx& c, const hmcg_config* cfg, const double* dY, const 
         if (pl.stream) { p.sscr = reinterpret_cast<uint8_t*>(c.scr.base + fbytes); p.stream_stride = (int64_t)slab_bytes(pl); }
     }
     if (timing) HIP_TRY(hipEventRecord(c.ev0, stream));
-#ifdef HMCG_STAMPS
+#if defined(HMCG_STAMPS) || defined(HMCG_BARRIER_STAMPS)
     const size_t ndbg = (size_t)cfg->W * (pl.NT() / 64 + pl.NH()) * HMCG_NSTAMP_ALL;
     unsigned long long* ddbg = nullptr;
     HIP_TRY(hipMalloc((void**)&ddbg, ndbg * sizeof(unsigned long long)));
@@ -527,7 +584,7 @@ int launch_device(DeviceCtx& c, const hmcg_config* cfg, const double* dY, const 
         HIP_TRY(hmcg_host::launch_corr_finalize(reinterpret_cast<double*>(c.mom.base), ex->corr, cfg->W, cfg->K, stream));
     }
     if (uses_scratch) HIP_TRY(hipEventRecord(c.ev_scr, stream));
-#ifdef HMCG_STAMPS
+#if defined(HMCG_STAMPS) || defined(HMCG_BARRIER_STAMPS)
     rc = print_stamps(p, pl, ddbg, ndbg, stream);
     (void)hipFree(ddbg);
     if (rc) return rc;

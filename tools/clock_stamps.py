@@ -1,10 +1,15 @@
 """In-kernel shader clock of the sweep kernels (MI355X_MICROARCH.md "DVFS give-back" item 6):
 the diagnostic (stamped) build is launched back to back for >= `warm_s` seconds, then one more launch prints its
 clock = d(s_memtime) / d(s_memrealtime) x 100 MHz around the sweep loop (median over every wave of every window) and
-the phase table.  usage: python tools/clock_stamps.py [K=3] [T=1000] [W=256] [draws=1000] [warm_s=2.5]"""
+the phase table.  usage: python tools/clock_stamps.py [--barriers] [K=3] [T=1000] [W=256] [draws=1000] [warm_s=2.5]
+--barriers: the barrier-arrival build instead (`make -C hmc.jl_amd/csrc barrier-stamps`: the clock read only around the six
+sweep barriers, the schedule between them as shipped); the table is then work and wait per wave and barrier."""
 import os, sys, time
 os.environ.setdefault("HMCG_DIAG", "1")      # arms the library's diagnostic switches (read once at first use)
-os.environ.setdefault("HMCG_LIB", "libhmcgibbs_stamps.so")
+barriers = "--barriers" in sys.argv
+if barriers:
+    sys.argv.remove("--barriers")
+os.environ.setdefault("HMCG_LIB", "libhmcgibbs_bstamps.so" if barriers else "libhmcgibbs_stamps.so")
 os.environ["HMCG_STAMPS_AFTER"] = "1000000"      # replaced below: the library reads it at its first launch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 K = int(sys.argv[1]) if len(sys.argv) > 1 else 3
