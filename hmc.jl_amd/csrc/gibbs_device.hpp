@@ -2320,9 +2320,22 @@ void gibbs_sweeps_kernel(const KernelParams p)
         scan_level<K, DPP_ROW_BCAST15, 0xA>(Q);
         scan_level<K, DPP_ROW_BCAST31, 0xC>(Q);
         rescale_pow2<KK>(Q);
+        // wave totals for the cross-wave prefix.  Wave 0 publishes the VECTOR rho' W_0 (every later wave starts from it and
+        // nobody reads the matrix W_0: the smoothing form's backward chain uses wtot[1..] only), in the statement form of the
+        // chain below -- same bits as when each of the later waves formed it for itself
         if (lane == 63) {
+            if (wave == 0) {
 #pragma unroll
-            for (int i = 0; i < KK; ++i) sh.wtot[wave][i] = Q[i];
+                for (int s = 0; s < K; ++s) {
+                    double acc = rho[0] * Q[s];
+#pragma unroll
+                    for (int r = 1; r < K; ++r) acc = fma(rho[r], Q[r * K + s], acc);
+                    sh.wtot[0][s] = acc;
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < KK; ++i) sh.wtot[wave][i] = Q[i];
+            }
         }
         STAMP(5);
         SWEEP_BARRIER(3);                                                  // Bc
@@ -2332,21 +2345,19 @@ void gibbs_sweeps_kernel(const KernelParams p)
 #pragma unroll
         for (int s = 0; s < K; ++s) av[s] = rho[s];
         const int wave_u = __builtin_amdgcn_readfirstlane(wave);       // scalar: the loops over other waves branch, not select
-        // (the last wave runs NW-1 dependent vector-matrix products here and everyone waits for it at the next barrier:
-        //  the next wave total is fetched from LDS while the current product runs)
-        double Wn[KK];
+        // (the last wave runs NW-2 dependent vector-matrix products here and everyone waits for it at the next barrier.  The
+        //  wave id is a scalar.  Four waves with registers to spare: each wave takes a straight-line path of its own -- every
+        //  LDS read it needs is issued at once, into registers of its own, one wait, then the products back to back.  Eight
+        //  waves (six products) and the register-capped L > 4 forms keep two totals in registers at a time: the next one is
+        //  fetched while the current product runs.  The straight-line form in every row was compiled: six totals in registers
+        //  cost gibbs<3,2,512> 65 spilled VGPRs and 232 B of scratch (none before), the L = 8 rows 30 / 27 spilled VGPRs against
+        //  24 / 21 -- profiles/r07/isa_lint_table_k3_hoist_every_row.txt)
+        constexpr bool HOIST = NW <= 4 && L <= 4;
+        if (wave_u != 0) {
 #pragma unroll
-        for (int i = 0; i < KK; ++i) Wn[i] = sh.wtot[0][i];
-#pragma unroll
-        for (int ww = 0; ww < NW - 1; ++ww) {
-            if (ww < wave_u) {
-                double Wc[KK], nv[K];
-#pragma unroll
-                for (int i = 0; i < KK; ++i) Wc[i] = Wn[i];
-                if (ww + 1 < NW - 1) {
-#pragma unroll
-                    for (int i = 0; i < KK; ++i) Wn[i] = sh.wtot[ww + 1][i];
-                }
+            for (int s = 0; s < K; ++s) av[s] = sh.wtot[0][s];
+            auto times = [&](const double (&Wc)[KK]) {
+                double nv[K];
 #pragma unroll
                 for (int s = 0; s < K; ++s) {
                     double acc = av[0] * Wc[s];
@@ -2356,17 +2367,52 @@ void gibbs_sweeps_kernel(const KernelParams p)
                 }
 #pragma unroll
                 for (int s = 0; s < K; ++s) av[s] = nv[s];
+            };
+            if constexpr (NW > 2 && HOIST) {
+#pragma unroll
+                for (int w1 = 2; w1 < NW; ++w1) {
+                    if (wave_u == w1) {
+                        double Wt[NW - 2][KK];                   // (only the w1 - 1 totals this wave reads exist)
+#pragma unroll
+                        for (int ww = 1; ww < w1; ++ww)
+#pragma unroll
+                            for (int i = 0; i < KK; ++i) Wt[ww - 1][i] = sh.wtot[ww][i];
+                        __builtin_amdgcn_s_waitcnt(0xC07F);      // lgkmcnt(0): the one wait, after the last read is on its way
+                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int ww = 1; ww < w1; ++ww) times(Wt[ww - 1]);
+                    }
+                }
+            } else if constexpr (NW > 2) {
+                double Wn[KK];
+#pragma unroll
+                for (int i = 0; i < KK; ++i) Wn[i] = sh.wtot[1][i];
+#pragma unroll
+                for (int ww = 1; ww < NW - 1; ++ww) {
+                    if (ww < wave_u) {
+                        double Wc[KK];
+#pragma unroll
+                        for (int i = 0; i < KK; ++i) Wc[i] = Wn[i];
+                        if (ww + 1 < NW - 1) {
+#pragma unroll
+                            for (int i = 0; i < KK; ++i) Wn[i] = sh.wtot[ww + 1][i];
+                        }
+                        times(Wc);
+                    }
+                }
             }
         }
         {
+            // multiply by this lane's own inclusive product, then shift the VECTOR one lane up: lane i receives what lane i-1
+            // formed -- the operations lane i used to perform on the shifted matrix -- and lane 0 keeps av, which is what the
+            // product with the identity returned
             double nv[K];
 #pragma unroll
             for (int s = 0; s < K; ++s) {
                 double acc = 0.0;
 #pragma unroll
-                for (int r = 0; r < K; ++r)
-                    acc = fma(av[r], dpp_f64<DPP_WAVE_SHR1, 0xF>((r == s) ? 1.0 : 0.0, Q[r * K + s]), acc);
-                nv[s] = acc;
+                for (int r = 0; r < K; ++r) acc = fma(av[r], Q[r * K + s], acc);
+                nv[s] = dpp_f64<DPP_WAVE_SHR1, 0xF>(av[s], acc);
             }
             rescale_pow2<K>(nv);
 #pragma unroll
@@ -2511,6 +2557,11 @@ void gibbs_sweeps_kernel(const KernelParams p)
         SWEEP_BARRIER(4);                                                  // Bd
         STAMP(8);
         // ---- backward sampling (:459-484) as a suffix scan of state maps ----
+        // The lane predicates of this phase (which slot holds the last step, which slots are padded, the lane's row) do not
+        // change from sweep to sweep: left to the compiler they are hoisted as 64-bit masks, for which the loop has no SGPRs
+        // left, and come back through two lane reads each.  Rebuilt here from two per-lane values with one compare each.
+        int dlast = T - 1 - t0, lane_o = lane;       // slot of the last step in this thread (negative: all padding; >= L: none)
+        asm volatile("" : "+v"(dlast), "+v"(lane_o));
         int xlast = 0;
         {
             const double ulast = sh.ulast;
@@ -2558,7 +2609,7 @@ void gibbs_sweeps_kernel(const KernelParams p)
                 m |= (uint32_t)idx << (8 * s);
             }
             if constexpr (K < 4) m |= BMAP_IDENTITY & (0xFFFFFFFFu << (8 * K));       // unused bytes: identity
-            m = (t == T - 1) ? bmap_const(xlast) : (t > T - 1 ? (PADMARK ? bmap_const(XPAD) : BMAP_IDENTITY) : m);
+            m = (l == dlast) ? bmap_const(xlast) : (l > dlast ? (PADMARK ? bmap_const(XPAD) : BMAP_IDENTITY) : m);
             gmap[l] = m;
             G = bmap_compose(m, G);      // G = g_{t0+l} o (g_{t0+l+1} o ...)
         }
@@ -2576,11 +2627,10 @@ void gibbs_sweeps_kernel(const KernelParams p)
             const uint32_t R2 = (uint32_t)__builtin_amdgcn_readlane((int)Hm, 32);
             const uint32_t R3 = (uint32_t)__builtin_amdgcn_readlane((int)Hm, 48);
             const uint32_t S1 = bmap_compose(R2, R3), S0 = bmap_compose(R1, S1);
-            const int row = lane >> 4;
-            const uint32_t after = row == 0 ? S0 : (row == 1 ? S1 : (row == 2 ? R3 : BMAP_IDENTITY));
+            const uint32_t after = lane_o < 16 ? S0 : (lane_o < 32 ? S1 : (lane_o < 48 ? R3 : BMAP_IDENTITY));
             Hm = bmap_compose(Hm, after);
         }
-        if (lane == 0) sh.wmap[wave] = Hm;
+        if (lane_o == 0) sh.wmap[wave] = Hm;
         STAMP(10);
         SWEEP_BARRIER(5);                                                  // Be
         STAMP(11);
