@@ -25,8 +25,13 @@ ST_SKIPPED = ST_NONFINITE | ST_BAD_T | ST_BAD_RANGE      # the window was not co
 HMCG_MAXTAIL = 256
 EXPORTS = ("hmcg_version", "hmcg_device_count", "hmcg_last_error", "hmcg_shutdown",
            "hmcg_estimate_batch", "hmcg_estimate_batch_device", "hmcg_estimate_batch_multi",
-           "hmcg_save_results_csv", "hmcg_write_table_csv", "hmcg_format_float")
+           "hmcg_save_results_csv", "hmcg_write_table_csv", "hmcg_format_float",
+           "hmcg_predictive_cdf", "hmcg_predictive_cdf_device")
 HMCG_MAXDEV = 16
+PRED_ROUND5 = 1
+HMCG_MAXGRID = 4096
+HMCG_PRED_MAXH = 1024           # largest horizon of the predictive CDFs
+PRED_SLAB = 1024                # draws per reduction slab (csrc/predictive_plan.hpp): the host entry uploads whole slabs
 
 
 class HmcgError(RuntimeError):
@@ -57,6 +62,12 @@ class Timing(C.Structure):
                 ("steps_per_thread", C.c_int32), ("lds_bytes", C.c_int32), ("helper_waves", C.c_int32),
                 ("device", C.c_int32), ("call_ms", C.c_double), ("windows", C.c_int32), ("occupancy", C.c_int32),
                 ("buckets", C.c_int32), ("streaming", C.c_int32)]
+
+
+class Predictive(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("W", C.c_int32), ("K", C.c_int32), ("device", C.c_int32),
+                ("nd", C.c_int64), ("nd_ld", C.c_int64), ("G", C.c_int32), ("n_h", C.c_int32),
+                ("horizons", C.c_int32 * HMCG_MAXH), ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
 _LIB = None
@@ -117,6 +128,8 @@ def load():
         L.hmcg_save_results_csv.restype = C.c_int
         L.hmcg_write_table_csv.restype = C.c_int
         L.hmcg_format_float.restype = C.c_int
+        L.hmcg_predictive_cdf.restype = C.c_int
+        L.hmcg_predictive_cdf_device.restype = C.c_int
         _LIB = L
     return _LIB
 
@@ -359,6 +372,57 @@ def estimate_batch_device(cfg, dY, dT, dyreal, dmu, dsig2, dA, dpi_end, dfcast, 
                                       C.byref(extras) if extras is not None else None, vp(stream),
                                       C.byref(tm) if timed else None)
     _check(rc)
+    return tm
+
+
+def make_predictive(W, K, nd, nd_ld, G, horizons=(0,), device=0, round5=True):
+    """hmcg_predictive of a call.  More than HMCG_MAXH horizons raise here; every other rule is the library's (HMCG_E_BADARG)."""
+    if len(horizons) > HMCG_MAXH:
+        raise ValueError("at most %d horizons" % HMCG_MAXH)
+    p = Predictive()
+    p.struct_size = C.sizeof(Predictive)
+    p.W, p.K, p.device, p.nd, p.nd_ld, p.G, p.n_h = int(W), int(K), int(device), int(nd), int(nd_ld), int(G), len(horizons)
+    for i, h in enumerate(horizons):
+        p.horizons[i] = int(h)
+    p.flags = PRED_ROUND5 if round5 else 0
+    return p
+
+
+def predictive_cdf_host(mu, sig2, pi_end, A, grid, horizons=(0,), device=0, round5=True, timing=None):
+    """hmcg_predictive_cdf over host (numpy) draw arrays in the C-ABI layouts -- mu/sig2/pi_end (W, K, nd), A (W, K, K, nd) with
+    A[w, j, i, d] = draw d of A[i, j] (None when every horizon is 0) -- as estimate_batch_host returns them.  Returns cdf
+    (W, n_h, G): per window and horizon the mean over the draws of sum_k omega[k] Phi((grid[g] - mu[k]) / sqrt(sig2[k])),
+    omega = pi_end A^h (calc_cdfs.jl:39-41 at h = 0).  round5 (default): every input is first rounded to 5 digits, as the cells
+    of the per-draw CSV files are.  timing: a Timing to fill."""
+    mu = np.ascontiguousarray(mu, dtype=np.float64)
+    W, K, nd = mu.shape
+    sig2 = np.ascontiguousarray(sig2, dtype=np.float64)
+    pi_end = np.ascontiguousarray(pi_end, dtype=np.float64)
+    if sig2.shape != mu.shape or pi_end.shape != mu.shape:
+        raise ValueError("mu, sig2 and pi_end must share the shape (W, K, nd)")
+    if A is not None:
+        A = np.ascontiguousarray(A, dtype=np.float64)
+        if A.shape != (W, K, K, nd):
+            raise ValueError("A must have the shape (W, K, K, nd)")
+    grid = np.ascontiguousarray(grid, dtype=np.float64).reshape(-1)
+    p = make_predictive(W, K, nd, nd, grid.size, horizons, device, round5)
+    cdf = np.zeros((W, len(horizons), grid.size))
+    _check(load().hmcg_predictive_cdf(C.byref(p), _np_ptr(mu), _np_ptr(sig2), _np_ptr(pi_end), _np_ptr(A), _np_ptr(grid),
+                                      _np_ptr(cdf), C.byref(timing) if timing is not None else None))
+    return cdf
+
+
+def predictive_cdf_device(pred, dmu, dsig2, dpi_end, dA, dgrid, dcdf, stream=None, timed=False):
+    """hmcg_predictive_cdf_device over raw device pointers (ints, e.g. torch tensor.data_ptr(); dA 0 / None when every horizon
+    is 0); pred: make_predictive(...).  Enqueued on `stream` (None: the library's own).  Returns the Timing struct when timed
+    (the call then waits for completion), else None."""
+    tm = Timing() if timed else None
+
+    def vp(x):
+        return None if not x else C.c_void_p(int(x))
+
+    _check(load().hmcg_predictive_cdf_device(C.byref(pred), vp(dmu), vp(dsig2), vp(dpi_end), vp(dA), vp(dgrid), vp(dcdf),
+                                             vp(stream), C.byref(tm) if timed else None))
     return tm
 
 

@@ -32,6 +32,7 @@
 #include "host_util.hpp"
 #include "moments.hpp"
 #include "plan.hpp"
+#include "predictive.hpp"
 
 namespace {
 
@@ -115,6 +116,7 @@ struct DeviceCtx {
     Arena mom;                     // device entry: the draw-moment tables behind extras.corr
     Arena scr;                     // device entry: the LDS-resident kernel's pdf scratch
     Arena ord;                     // device entry: the bucketed dispatch's window lists (bucket_lists_kernel)
+    Arena pred;                    // device entry of the predictive CDFs: the slab sums
     hmcg_hostutil::ScatterPool pool;              // host entries: helpers for the scatter into the caller's arrays
 };
 DeviceCtx g_ctx[HMCG_MAXDEV];
@@ -211,6 +213,7 @@ void destroy_context(DeviceCtx& c)
     c.mom.release();
     c.scr.release();
     c.ord.release();
+    c.pred.release();
     c.pool.stop();
     c.stream = c.copy = nullptr;
     c.ready = false;
@@ -944,6 +947,139 @@ int run_host_on_device(DeviceCtx& c, const hmcg_config* cfg, const int32_t* idx,
     return rc;
 }
 
+// ---- predictive CDFs of the regime mixture (predictive.hip; argument rules and slab / chunk cut: predictive_plan.hpp) ----------
+
+hmcg_host::PredictiveArgs predictive_args(const hmcg_predictive* p)
+{
+    hmcg_host::PredictiveArgs a{};
+    a.W = p->W; a.K = p->K; a.G = p->G; a.n_h = p->n_h;
+    for (int j = 0; j < HMCG_MAXH; ++j) a.horizons[j] = j < p->n_h ? p->horizons[j] : 0;
+    a.round5 = (p->flags & HMCG_PRED_ROUND5) != 0;
+    a.nslab_total = pred_slabs(p->nd);
+    return a;
+}
+
+void fill_predictive_timing(hmcg_timing* t, const hmcg_predictive* p, const DeviceCtx& c, double kernel_ms, int launches, double call_ms)
+{
+    memset(t, 0, sizeof *t);
+    t->kernel_ms = kernel_ms; t->launches = launches; t->call_ms = call_ms;
+    t->device = c.device; t->windows = p->W; t->buckets = 1;
+    t->lds_bytes = (int32_t)predictive_lds_bytes(p->K, p->n_h, pred_max_horizon(*p) > 0);
+}
+
+// Caller holds c.mu and has made c.device current.  The slab sums live in a context-owned arena (as the moment tables do).
+int predictive_device(DeviceCtx& c, const hmcg_predictive* p, const double* dmu, const double* dsig2, const double* dpi_end,
+                      const double* dA, const double* dgrid, double* dcdf, hipStream_t stream, hmcg_timing* timing)
+{
+    int rc = grow_shared(c, c.pred, sizeof(double) * predictive_part_doubles(p->W, p->nd, p->n_h, p->G));
+    if (rc) return rc;
+    HIP_TRY(hipStreamWaitEvent(stream, c.ev_scr, 0));
+    if (timing) HIP_TRY(hipEventRecord(c.ev0, stream));
+    hmcg_host::PredictiveArgs a = predictive_args(p);
+    a.mu = dmu; a.sig2 = dsig2; a.pi_end = dpi_end; a.A = dA; a.grid = dgrid;
+    a.part = reinterpret_cast<double*>(c.pred.base);
+    a.nd = p->nd; a.nd_ld = p->nd_ld; a.slab0 = 0;
+    HIP_TRY(launch_predictive(a, stream));
+    HIP_TRY(launch_predictive_finalize(a.part, dcdf, p->W, p->n_h, p->G, p->nd, stream));
+    HIP_TRY(hipEventRecord(c.ev_scr, stream));
+    if (timing) {
+        HIP_TRY(hipEventRecord(c.ev1, stream));
+        HIP_TRY(hipEventSynchronize(c.ev1));
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, c.ev0, c.ev1));
+        fill_predictive_timing(timing, p, c, ms, 2, 0.0);
+    }
+    return 0;
+}
+
+// Host entry on one device: the draws go up in chunks of whole slabs -- packed window by window, column by column into pinned
+// staging (leading dimension = the chunk's draws), copied on the copy stream, reduced on the compute stream -- RING buffers deep,
+// so chunk c + 1 is packed and copied while chunk c's kernel runs.  Every chunk adds its slabs' sums to the same table; one
+// finalize at the end.  Caller holds c.mu and has made c.device current.
+int predictive_host(DeviceCtx& c, const hmcg_predictive* p, const double* mu, const double* sig2, const double* pi_end, const double* A,
+                    const double* grid, double* cdf, hmcg_timing* timing)
+{
+    const auto t_call = std::chrono::steady_clock::now();
+    const int K = p->K, W = p->W;
+    const bool with_A = pred_max_horizon(*p) > 0;
+    const int ncol = pred_columns(*p);
+    long long cap = 0;
+    if (const char* cenv = diag_env("HMCG_CHUNK_DRAWS")) cap = atoll(cenv);
+    const long long cdraws = pred_chunk_draws(p->nd, W, ncol, cap);
+    const std::vector<PredChunk> chunks = pred_chunks(p->nd, cdraws);
+    const size_t items = (size_t)p->n_h * (size_t)p->G;
+    auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
+    const size_t b_chunk = up(sizeof(double) * (size_t)W * (size_t)ncol * (size_t)cdraws);
+    const size_t b_grid = up(sizeof(double) * (size_t)p->G), b_cdf = up(sizeof(double) * (size_t)W * items);
+    const size_t b_part = up(sizeof(double) * predictive_part_doubles(W, p->nd, p->n_h, p->G));
+    const int nbuf = (int)std::min<size_t>(RING, chunks.size());
+    if (c.dev.ensure(b_grid + b_cdf + b_part + b_chunk * (size_t)nbuf) || c.pin.ensure(b_grid + b_cdf + b_chunk * (size_t)nbuf)) {
+        set_err("workspace allocation failed (%zu B device, %zu B pinned)", b_grid + b_cdf + b_part + b_chunk * (size_t)nbuf,
+                b_grid + b_cdf + b_chunk * (size_t)nbuf);
+        return HMCG_E_NOMEM;
+    }
+    double* dgrid = reinterpret_cast<double*>(c.dev.base);
+    double* dcdf = reinterpret_cast<double*>(c.dev.base + b_grid);
+    double* dpart = reinterpret_cast<double*>(c.dev.base + b_grid + b_cdf);
+    char* dchunk = c.dev.base + b_grid + b_cdf + b_part;
+    double* pgrid = reinterpret_cast<double*>(c.pin.base);
+    double* pcdf = reinterpret_cast<double*>(c.pin.base + b_grid);
+    char* pchunk = c.pin.base + b_grid + b_cdf;
+
+    struct Events {
+        std::vector<hipEvent_t> ev;
+        ~Events() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+    } tev;                                       // two per chunk, around its kernel (created only when timing is asked for)
+    if (timing) {
+        tev.ev.assign(2 * chunks.size(), nullptr);
+        for (hipEvent_t& e : tev.ev) HIP_TRY(hipEventCreate(&e));
+    }
+    memcpy(pgrid, grid, sizeof(double) * (size_t)p->G);
+    HIP_TRY(hipMemcpyAsync(dgrid, pgrid, sizeof(double) * (size_t)p->G, hipMemcpyHostToDevice, c.stream));
+    hmcg_host::PredictiveArgs a = predictive_args(p);
+    a.grid = dgrid; a.part = dpart;
+    for (size_t ci = 0; ci < chunks.size(); ++ci) {
+        const PredChunk& ch = chunks[ci];
+        const int b = (int)(ci % (size_t)nbuf);
+        if (ci >= (size_t)nbuf) HIP_TRY(hipEventSynchronize(c.evk[b]));       // the kernel that read this buffer pair is done
+        double* pb = reinterpret_cast<double*>(pchunk + b_chunk * (size_t)b);
+        double* db = reinterpret_cast<double*>(dchunk + b_chunk * (size_t)b);
+        // packed chunk: mu | sig2 | pi_end | A, each [W][columns][ch.n]
+        const size_t n = (size_t)ch.n, o_sig = (size_t)W * K * n, o_pi = 2 * o_sig, o_A = 3 * o_sig;
+        auto pack = [&](const double* src, size_t cols, double* dst) {
+            for (size_t q = 0; q < (size_t)W * cols; ++q) memcpy(dst + q * n, src + q * (size_t)p->nd_ld + (size_t)ch.d0, sizeof(double) * n);
+        };
+        pack(mu, (size_t)K, pb);
+        pack(sig2, (size_t)K, pb + o_sig);
+        pack(pi_end, (size_t)K, pb + o_pi);
+        if (with_A) pack(A, (size_t)K * K, pb + o_A);
+        HIP_TRY(hipMemcpyAsync(db, pb, sizeof(double) * (size_t)W * (size_t)ncol * n, hipMemcpyHostToDevice, c.copy));
+        HIP_TRY(hipEventRecord(c.evc[b], c.copy));
+        HIP_TRY(hipStreamWaitEvent(c.stream, c.evc[b], 0));
+        a.mu = db; a.sig2 = db + o_sig; a.pi_end = db + o_pi; a.A = with_A ? db + o_A : nullptr;
+        a.nd = ch.n; a.nd_ld = ch.n; a.slab0 = ch.d0 / PRED_SLAB;
+        if (timing) HIP_TRY(hipEventRecord(tev.ev[2 * ci], c.stream));
+        HIP_TRY(launch_predictive(a, c.stream));
+        if (timing) HIP_TRY(hipEventRecord(tev.ev[2 * ci + 1], c.stream));
+        HIP_TRY(hipEventRecord(c.evk[b], c.stream));
+    }
+    HIP_TRY(launch_predictive_finalize(dpart, dcdf, W, p->n_h, p->G, p->nd, c.stream));
+    HIP_TRY(hipMemcpyAsync(pcdf, dcdf, sizeof(double) * (size_t)W * items, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    memcpy(cdf, pcdf, sizeof(double) * (size_t)W * items);
+    if (timing) {
+        double kernel_ms = 0.0;
+        for (size_t ci = 0; ci < chunks.size(); ++ci) {
+            float ms = 0.f;
+            HIP_TRY(hipEventElapsedTime(&ms, tev.ev[2 * ci], tev.ev[2 * ci + 1]));
+            kernel_ms += ms;
+        }
+        const double call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+        fill_predictive_timing(timing, p, c, kernel_ms, (int)chunks.size() + 1, call_ms);
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1049,6 +1185,36 @@ int hmcg_estimate_batch_multi(const hmcg_config* cfg, int32_t n_devices, const i
             return rcs[(size_t)r];
         }
     return 0;
+}
+
+int hmcg_predictive_cdf_device(const hmcg_predictive* p, const double* dmu, const double* dsig2, const double* dpi_end, const double* dA,
+                               const double* dgrid, double* dcdf, void* stream, hmcg_timing* timing)
+{
+    g_err[0] = 0;
+    char msg[160];
+    int rc = check_predictive(p, dmu, dsig2, dpi_end, dA, dgrid, dcdf, false, msg, sizeof msg);
+    if (rc) { set_err("%s", msg); return rc; }
+    DeviceCtx* c = nullptr;
+    rc = get_context(p->device, &c);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->phys));
+    return predictive_device(*c, p, dmu, dsig2, dpi_end, dA, dgrid, dcdf, stream ? (hipStream_t)stream : c->stream, timing);
+}
+
+int hmcg_predictive_cdf(const hmcg_predictive* p, const double* mu, const double* sig2, const double* pi_end, const double* A,
+                        const double* grid, double* cdf, hmcg_timing* timing)
+{
+    g_err[0] = 0;
+    char msg[160];
+    int rc = check_predictive(p, mu, sig2, pi_end, A, grid, cdf, true, msg, sizeof msg);
+    if (rc) { set_err("%s", msg); return rc; }
+    DeviceCtx* c = nullptr;
+    rc = get_context(p->device, &c);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->phys));
+    return predictive_host(*c, p, mu, sig2, pi_end, A, grid, cdf, timing);
 }
 
 }  // extern "C"

@@ -1,0 +1,190 @@
+// predictive.hip -- predictive CDFs of the regime mixture, averaged over a window's draws on the device.
+//
+// What it replaces (joe5saia/Hmc.jl): code/hassan_cdfs/calc_cdfs.jl reads `filtered_means_<date>.csv`, `filtered_variances_<date>.csv`
+// and `filtered_state_probs_<date>.csv` of every end date back from disk (250 000 rows each in production) and evaluates, for
+// every draw i and every grid point y of -5:.25:15,
+//   F_i(y) = sum_k pi_i[k] * Phi((y - mu_i[k]) / sqrt(sig2_i[k]))                                        (:39)
+// then averages over the draws (`expectationsbar`, :41).  Here the draws are read where they lie in HBM.  Horizons h > 0 use
+// the weights pi_i * A_i^h, the state law of forecast (src/Hmc.jl:662-663): the h-step-ahead predictive distribution.
+//
+// Shape: one block per (window, slab of PRED_SLAB draws, 128 (horizon, grid point) items).  A tile of 64 draws is staged in LDS --
+// per draw and state mu_k and c_k = 1 / (sqrt 2 * sqrt(sig2_k)) side by side, and the n_h * K weights, built per (draw, horizon) by
+// h successive row-vector x matrix products over the tile's transition draws (k ascending in every dot product).  Each thread then
+// owns one (horizon, grid point) and walks the tile in draw order: every lane reads the same mu, c (one broadcast ds_read_b128),
+// Phi = erfc(-(y - mu) c) / 2.  fp64 VALU work by construction: 8 (3K [+ K^2]) bytes read per draw against K * n_h * G erfc.
+//
+// Numerics: with round5 every input is rounded as a CSV cell is (round5.hpp).  No special cases: a zero variance gives c = inf,
+// so Phi is 0 or 1 and NaN where y == mu; a NaN term times a zero weight stays NaN.  Deterministic: a thread adds its slab's draws
+// in draw order and writes the slab sum; predictive_finalize_kernel adds the slab sums in slab order and divides by nd.  No atomics.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "predictive.hpp"
+#include "round5.hpp"
+
+namespace hmcg {
+
+constexpr int PRED_TD = 64;          // draws per LDS tile
+constexpr int PRED_NT = 128;         // threads per block = (horizon, grid point) items per block
+constexpr int PRED_FIN_NT = 256;
+
+struct PredictiveParams {
+    const double* mu; const double* sig2; const double* pi_end; const double* A; const double* grid;
+    double* part;                    // [W][nslab_total][items]
+    long long nd, nd_ld;             // draws in this launch, leading dimension of the draw arrays
+    long long nslab, slab0, nslab_total;     // slabs of this launch; its first slab and the slab count of the whole run
+    int G, n_h, items, round5;
+    int hz[HMCG_MAXH];
+};
+
+__device__ __forceinline__ double pred_in(double x, int r5) { return r5 ? round5(x) : x; }
+
+template <int K>
+__global__ __launch_bounds__(PRED_NT) void predictive_cdf_kernel(const PredictiveParams p)
+{
+    extern __shared__ double pred_lds[];
+    const int n_h = p.n_h;
+    double* MC = pred_lds;                               // [PRED_TD][K][2]: mu, c
+    double* Ws = MC + PRED_TD * K * 2;                   // [PRED_TD][n_h][K]: weights of every horizon
+    double* As = Ws + PRED_TD * n_h * K;                 // [K * K][PRED_TD]: transition draws (present with a horizon > 0)
+    const int tid = threadIdx.x;
+    const int w = (int)((long long)blockIdx.x / p.nslab);
+    const long long s = (long long)blockIdx.x - (long long)w * p.nslab;
+    const long long dbeg = s * hmcg_host::PRED_SLAB;
+    const long long dend = dbeg + hmcg_host::PRED_SLAB < p.nd ? dbeg + hmcg_host::PRED_SLAB : p.nd;
+    const int e = (int)blockIdx.y * PRED_NT + tid;       // this thread's item: horizon j, grid point g
+    const bool live = e < p.items;
+    const int j = live ? e / p.G : 0, g = live ? e - j * p.G : 0;
+    const double y = pred_in(p.grid[g], p.round5);
+    const double* mu = p.mu + (size_t)w * K * p.nd_ld;
+    const double* sig2 = p.sig2 + (size_t)w * K * p.nd_ld;
+    const double* pie = p.pi_end + (size_t)w * K * p.nd_ld;
+    const double* At = p.A ? p.A + (size_t)w * K * K * p.nd_ld : nullptr;
+    double acc = 0.0;
+    for (long long d0 = dbeg; d0 < dend; d0 += PRED_TD) {
+        const int nv = dend - d0 < PRED_TD ? (int)(dend - d0) : PRED_TD;
+        for (int q = tid; q < K * PRED_TD; q += PRED_NT) {
+            const int k = q / PRED_TD, dd = q - k * PRED_TD;
+            if (dd < nv) {
+                const size_t off = (size_t)k * p.nd_ld + (size_t)(d0 + dd);
+                MC[(dd * K + k) * 2] = pred_in(mu[off], p.round5);
+                MC[(dd * K + k) * 2 + 1] = 1.0 / (1.4142135623730951 * sqrt(pred_in(sig2[off], p.round5)));
+            }
+        }
+        if (At) {
+            for (int q = tid; q < K * K * PRED_TD; q += PRED_NT) {
+                const int c = q / PRED_TD, dd = q - c * PRED_TD;
+                if (dd < nv) As[q] = pred_in(At[(size_t)c * p.nd_ld + (size_t)(d0 + dd)], p.round5);
+            }
+        }
+        __syncthreads();
+        // weights: thread (draw dd, horizon jh) takes pi_end through hz[jh] products with the draw's A
+        for (int q = tid; q < n_h * PRED_TD; q += PRED_NT) {
+            const int jh = q / PRED_TD, dd = q - jh * PRED_TD;
+            if (dd >= nv) continue;
+            int h = 0;
+#pragma unroll
+            for (int i = 0; i < HMCG_MAXH; ++i) h = jh == i ? p.hz[i] : h;
+            double wv[K];
+#pragma unroll
+            for (int k = 0; k < K; ++k) wv[k] = pred_in(pie[(size_t)k * p.nd_ld + (size_t)(d0 + dd)], p.round5);
+            for (int step = 0; step < h; ++step) {
+                double nw[K];
+#pragma unroll
+                for (int c = 0; c < K; ++c) {
+                    double t = wv[0] * As[(K * c) * PRED_TD + dd];
+#pragma unroll
+                    for (int i = 1; i < K; ++i) t += wv[i] * As[(i + K * c) * PRED_TD + dd];
+                    nw[c] = t;
+                }
+#pragma unroll
+                for (int c = 0; c < K; ++c) wv[c] = nw[c];
+            }
+#pragma unroll
+            for (int k = 0; k < K; ++k) Ws[(dd * n_h + jh) * K + k] = wv[k];
+        }
+        __syncthreads();
+        if (live) {
+#pragma unroll 1
+            for (int dd = 0; dd < nv; ++dd) {
+                const double* mc = MC + dd * K * 2;
+                const double* wj = Ws + (dd * n_h + j) * K;
+                double F = 0.0;
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    const double t = (y - mc[2 * k]) * mc[2 * k + 1];
+                    const double ph = 0.5 * erfc(-t);
+                    F = k == 0 ? wj[0] * ph : fma(wj[k], ph, F);
+                }
+                acc += F;
+            }
+        }
+        __syncthreads();
+    }
+    if (live) p.part[((size_t)w * (size_t)p.nslab_total + (size_t)(p.slab0 + s)) * (size_t)p.items + (size_t)e] = acc;
+}
+
+__global__ __launch_bounds__(PRED_FIN_NT) void predictive_finalize_kernel(const double* part, double* cdf, long long nslab, int items,
+                                                                         long long total, double nd)
+{
+    const long long idx = (long long)blockIdx.x * PRED_FIN_NT + threadIdx.x;
+    if (idx >= total) return;
+    const long long w = idx / items;
+    const int e = (int)(idx - w * items);
+    const double* col = part + (size_t)w * (size_t)nslab * (size_t)items + (size_t)e;
+    double sum = 0.0;
+    for (long long sl = 0; sl < nslab; ++sl) sum += col[(size_t)sl * (size_t)items];
+    cdf[idx] = sum / nd;
+}
+
+}  // namespace hmcg
+
+namespace hmcg_host {
+
+size_t predictive_part_doubles(int W, long long nd, int n_h, int G) { return (size_t)W * (size_t)pred_slabs(nd) * (size_t)n_h * (size_t)G; }
+
+size_t predictive_lds_bytes(int K, int n_h, bool with_A)
+{
+    return sizeof(double) * (size_t)hmcg::PRED_TD * (size_t)(2 * K + n_h * K + (with_A ? K * K : 0));
+}
+
+hipError_t launch_predictive(const PredictiveArgs& a, hipStream_t stream)
+{
+    if (a.W <= 0 || a.nd <= 0) return hipSuccess;
+    hmcg::PredictiveParams p{};
+    p.mu = a.mu; p.sig2 = a.sig2; p.pi_end = a.pi_end; p.A = a.A; p.grid = a.grid; p.part = a.part;
+    p.nd = a.nd; p.nd_ld = a.nd_ld; p.nslab = pred_slabs(a.nd); p.slab0 = a.slab0; p.nslab_total = a.nslab_total;
+    p.G = a.G; p.n_h = a.n_h; p.items = a.n_h * a.G; p.round5 = a.round5 ? 1 : 0;
+    bool with_A = false;
+    for (int j = 0; j < HMCG_MAXH; ++j) { p.hz[j] = j < a.n_h ? a.horizons[j] : 0; with_A = with_A || p.hz[j] > 0; }
+    if (with_A && !a.A) return hipErrorInvalidValue;
+    if (!with_A) p.A = nullptr;
+    if (p.slab0 < 0 || p.slab0 + p.nslab > p.nslab_total || (long long)a.W * p.nslab > 0x7fffffffLL) return hipErrorInvalidValue;
+    const size_t lds = predictive_lds_bytes(a.K, a.n_h, with_A);
+    const dim3 grid((unsigned)((long long)a.W * p.nslab), (unsigned)((p.items + hmcg::PRED_NT - 1) / hmcg::PRED_NT)), block(hmcg::PRED_NT);
+#define HMCG_PRED(K_)                                                                                                     \
+    case K_: {                                                                                                            \
+        hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(hmcg::predictive_cdf_kernel<K_>),               \
+                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                         \
+        if (e_ != hipSuccess) return e_;                                                                                   \
+        hipLaunchKernelGGL(hmcg::predictive_cdf_kernel<K_>, grid, block, lds, stream, p);                                  \
+    } break
+    switch (a.K) {
+        HMCG_PRED(2); HMCG_PRED(3); HMCG_PRED(4); HMCG_PRED(5); HMCG_PRED(6); HMCG_PRED(7); HMCG_PRED(8);
+        default: return hipErrorInvalidValue;
+    }
+#undef HMCG_PRED
+    return hipGetLastError();
+}
+
+hipError_t launch_predictive_finalize(const double* part, double* cdf, int W, int n_h, int G, long long nd_total, hipStream_t stream)
+{
+    const long long total = (long long)W * n_h * G;
+    if (total <= 0) return hipSuccess;
+    const unsigned nb = (unsigned)((total + hmcg::PRED_FIN_NT - 1) / hmcg::PRED_FIN_NT);
+    hipLaunchKernelGGL(hmcg::predictive_finalize_kernel, dim3(nb), dim3(hmcg::PRED_FIN_NT), 0, stream, part, cdf, pred_slabs(nd_total),
+                       n_h * G, total, (double)nd_total);
+    return hipGetLastError();
+}
+
+}  // namespace hmcg_host

@@ -79,6 +79,25 @@ class DevicePanel:
         self.last_timing = tm
         return tm.kernel_ms if tm is not None else None
 
+    def predictive_cdf(self, grid, horizons=(0,), timed=False, round5=True):
+        """Predictive CDFs of the regime mixture from the panel's own HBM draws (hmcg_predictive_cdf_device; calc_cdfs.jl at
+        horizon 0, the weights pi_end A^h beyond it): a (W, n_h, G) tensor, the mean over the kept draws per window, horizon
+        and grid point.  Enqueued on the library stream behind `run`; with timed=True the call waits and last_timing holds
+        the HIP-event time, otherwise call sync() before reading the tensor."""
+        if self.mu is None:
+            raise _lib.HmcgError("predictive_cdf needs the draws in HBM: the panel was built with keep_draws=False")
+        torch = self.torch
+        g = torch.from_numpy(np.ascontiguousarray(grid, dtype=np.float64).reshape(-1)).to(self.dev)    # a blocking copy
+        cdf = torch.empty((self.W, len(horizons), g.numel()), dtype=torch.float64, device=self.dev)
+        pred = _lib.make_predictive(self.W, self.K, self.nrun, self.nrun, g.numel(), horizons, self.device_index, round5)
+        need_A = any(int(h) > 0 for h in horizons)
+        tm = _lib.predictive_cdf_device(pred, self.mu.data_ptr(), self.sig2.data_ptr(), self.pi_end.data_ptr(),
+                                        self.A.data_ptr() if need_A else 0, g.data_ptr(), cdf.data_ptr(), None, timed)
+        self._pred_grid = g                 # kept until the enqueued kernel has read it
+        if timed:
+            self.last_timing = tm
+        return cdf
+
     def sync(self):
         """Wait for the library stream (untimed runs are asynchronous)."""
         self.torch.cuda.synchronize(self.dev)

@@ -13,6 +13,7 @@ ABI.  Names, argument meaning and result layout follow the reference:
     saveresults/basicsave   src/Hmc.jl:707-748   (five per-window CSVs)
     runaggregate layout src/Hmc.jl:1025-1078 (`*_summary.csv`)
     calccorr            src/Hmc.jl:1094-1163 (correlations.xlsx; matrices from the files or from the device)
+    calccdfs            code/hassan_cdfs/calc_cdfs.jl:31-42 (predictive CDFs; from the files or from the device)
 
 New (the reference batches by launching one SLURM task per window,
 slurmscripts/base_estimation.sh:5): `estimatewindows`, one call for many windows.
@@ -348,6 +349,9 @@ class BatchResult:
         self.status = res["status"]
         self.kernel_ms = res.get("kernel_ms")
         self.corr = res.get("corr")            # (W, NC, NC) with corr=True: calccorr's matrix per window (corrnames)
+        self.cdf = res.get("cdf")              # (W, n_h, G) with cdf_grid: calc_cdfs.jl's expectationsbar per window and horizon
+        self.cdf_grid = res.get("cdf_grid")
+        self.cdf_horizons = res.get("cdf_horizons")
         self._res = res if keep_draws else None
 
     def samples(self, w):
@@ -357,13 +361,18 @@ class BatchResult:
         return _unpack(self._res, w, o.Nrun, o.D, len(o.horizons), enddate(o))
 
 
-def estimatewindows(rawdata, dates, endIndices, startIndex=1, keep_draws=False, device=0, window_ids=None, corr=False, **kwargs):
+def estimatewindows(rawdata, dates, endIndices, startIndex=1, keep_draws=False, device=0, window_ids=None, corr=False,
+                    cdf_grid=None, cdf_horizons=(0,), **kwargs):
     """Batched estimatemodel over many expanding windows (one GPU call).
 
     Window w uses sampleRange = startIndex:endIndices[w], endIndex = endIndices[w]; the
     remaining keyword arguments are estopt's.  RNG stream ids default to the position
     in `endIndices`; pass window_ids to pin them (sharded runs).  corr=True also accumulates, on the device, the
-    correlation matrix between each window's per-draw outputs (calccorr, src/Hmc.jl:1094-1163) -> BatchResult.corr."""
+    correlation matrix between each window's per-draw outputs (calccorr, src/Hmc.jl:1094-1163) -> BatchResult.corr.
+    cdf_grid: grid points ys -> BatchResult.cdf (W, n_h, G), the draw mean of the regime mixture's normal CDF at every grid
+    point (calc_cdfs.jl's expectationsbar; cdf_horizons: 0 = the end date, h > 0 = h steps ahead under pi_end A^h), computed on
+    the device from the 5-digit-rounded draws (_lib.predictive_cdf_host); the draw arrays it needs are fetched for it and
+    dropped again unless keep_draws."""
     if startIndex != 1:
         raise ValueError("windows must start at index 1 (see estopt)")
     rawdata = np.asarray(rawdata, dtype=np.float64)
@@ -381,8 +390,17 @@ def estimatewindows(rawdata, dates, endIndices, startIndex=1, keep_draws=False, 
     for w, o in enumerate(opts):
         Y[w, :Tw[w]] = makey(o)
         yreal[w] = _yreal_row(rawdata, o.endIndex, o.horizons)
+    want = keep_draws
+    if cdf_grid is not None and not keep_draws:
+        want = ("mu", "sig2", "pi_end") + (("A",) if any(int(h) > 0 for h in cdf_horizons) else ())
     res = _lib.estimate_batch_host(Y, Tw, o0.D, o0.burnin, o0.Nrun, tuple(o0.horizons), yreal, seed=o0.seed,
-                                   device=device, want_draws=keep_draws, window_ids=window_ids, want_corr=corr)
+                                   device=device, want_draws=want, window_ids=window_ids, want_corr=corr)
+    if cdf_grid is not None:
+        ys = np.ascontiguousarray(cdf_grid, dtype=np.float64).reshape(-1)
+        hz = tuple(int(h) for h in cdf_horizons)
+        res["cdf"] = _lib.predictive_cdf_host(res["mu"], res["sig2"], res["pi_end"], res.get("A") if any(h > 0 for h in hz) else None,
+                                              ys, hz, device=device)
+        res["cdf_grid"], res["cdf_horizons"] = ys, hz
     return BatchResult(opts, res, keep_draws)
 
 
@@ -800,3 +818,101 @@ def calccorr(datadir, startyear=1980, endyear=2018, startmonth=1, endmonth=2, re
     os.makedirs(datadir, exist_ok=True)
     path = write_corr_workbook(os.path.join(datadir, "correlations.xlsx"), dates, names, mats)
     return path, dates, names, mats
+
+
+# ---------------------------------------------------------------- calc_cdfs.jl --
+
+def _normcdf(z):
+    """StatsFuns.normcdf: erfc(-z / sqrt 2) / 2, element by element."""
+    erfc = np.frompyfunc(math.erfc, 1, 1)
+    with np.errstate(invalid="ignore"):
+        return (erfc(-np.asarray(z, dtype=np.float64) / math.sqrt(2.0)).astype(np.float64)) / 2.0
+
+
+def _cdfs_from_files(datadir, date, ys, horizons):
+    """One date's expectationsbar (n_h, G) from its per-draw files, as calc_cdfs.jl:33-41 computes it on the host."""
+    def cells(stem):
+        _, rows = _read_csv(os.path.join(datadir, "%s_%s.csv" % (stem, date)))
+        return np.array([[float(x) for x in r[1:]] for r in rows])
+    means, vars_, pis = cells("filtered_means"), cells("filtered_variances"), cells("filtered_state_probs")
+    trans = cells("filtered_trans_probs") if any(h > 0 for h in horizons) else None
+    return _cdfs_from_cells(means, vars_, pis, trans, ys, horizons)
+
+
+def _cdfs_from_cells(means, vars_, pis, trans, ys, horizons):
+    """expectationsbar (n_h, G) from the cells of one date's files: (n, K) each, trans (n, K * K) in the file's column order."""
+    n, K = means.shape
+    with np.errstate(invalid="ignore", divide="ignore"):
+        z = (ys[None, :, None] - means[:, None, :]) / np.sqrt(vars_)[:, None, :]           # (n, G, K)
+    phi = _normcdf(z)
+    A = None if trans is None else trans.reshape(n, K, K).transpose(0, 2, 1)               # columns trans_i_j, i fastest -> A[d, i, j]
+    out = np.empty((len(horizons), len(ys)))
+    for j, h in enumerate(horizons):
+        w = pis.copy()
+        for _ in range(h):                                                                  # S0 * A^h, one product at a time
+            nw = w[:, 0, None] * A[:, 0, :]
+            for i in range(1, K):
+                nw = nw + w[:, i, None] * A[:, i, :]
+            w = nw
+        f = w[:, None, 0] * phi[:, :, 0]
+        for k in range(1, K):
+            f = f + w[:, None, k] * phi[:, :, k]
+        out[j] = np.mean(f, axis=0)
+    return out
+
+
+def finverse(p):
+    """quantile.(Normal(), p) (calc_cdfs.jl:42): 0 -> -Inf, 1 -> +Inf, NaN (or a value outside [0, 1]) -> NaN."""
+    import statistics
+    nd = statistics.NormalDist()
+
+    def one(x):
+        x = float(x)
+        if x == 0.0:
+            return -math.inf
+        if x == 1.0:
+            return math.inf
+        if not 0.0 < x < 1.0:
+            return math.nan
+        return nd.inv_cdf(x)
+    with np.errstate(invalid="ignore"):
+        return np.frompyfunc(one, 1, 1)(np.asarray(p, dtype=np.float64)).astype(np.float64)
+
+
+def calccdfs(datadir, dates, ys=np.arange(-5, 15.25, .25), horizons=(0,), result=None):
+    """code/hassan_cdfs/calc_cdfs.jl:31-42 without the plots: for every end date the draw mean of
+    F_i(y) = sum_k pi_i[k] Phi((y - mu_i[k]) / sqrt(var_i[k])) on the grid ys (`expectationsbar`) and its image under the normal
+    quantile (`finverse`).  horizons: 0 = the end date, as upstream; h > 0 weights the states by pi_i A_i^h instead.
+
+    result=None: as upstream, every date's `filtered_means_`, `filtered_variances_`, `filtered_state_probs_<date>.csv` (and
+    `filtered_trans_probs_<date>.csv` with a horizon > 0) are read back and evaluated on the host in numpy; no GPU is touched.
+    result = a BatchResult of estimatewindows(..., cdf_grid=ys, cdf_horizons=horizons): the means were taken on the device
+    from the rounded draws; every date must be one of the result's end dates.
+    Returns (dates, ys, expectationsbar (n_dates, n_h, G), finverse of the same shape)."""
+    dates = [str(d) for d in dates]
+    ys = np.ascontiguousarray(ys, dtype=np.float64).reshape(-1)
+    horizons = tuple(int(h) for h in horizons)
+    if result is None:
+        bar = np.array([_cdfs_from_files(datadir, d, ys, horizons) for d in dates]).reshape(len(dates), len(horizons), len(ys))
+    else:
+        if getattr(result, "cdf", None) is None:
+            raise ValueError("result carries no predictive CDFs (estimatewindows(..., cdf_grid=ys))")
+        if not np.array_equal(result.cdf_grid, ys) or tuple(result.cdf_horizons) != horizons:
+            raise ValueError("result was computed on another grid or other horizons")
+        by_date = {str(enddate(o)): w for w, o in enumerate(result.opts)}
+        for d in dates:
+            if d not in by_date:
+                raise ValueError("no window ends on %s" % d)
+        bar = np.array([result.cdf[by_date[d]] for d in dates]).reshape(len(dates), len(horizons), len(ys))
+    return dates, ys, bar, finverse(bar)
+
+
+def write_cdfs(path, dates, ys, horizons, expectationsbar):
+    """One CSV `date,horizon,y,cdf,finverse` with a row per (date, horizon, grid point), float text as in the other files (_fmt).
+    Upstream writes only plots of these numbers (calc_cdfs.jl:44), so this layout is this project's own."""
+    bar = np.asarray(expectationsbar, dtype=np.float64)
+    fin = finverse(bar)
+    rows = [[str(d), str(int(h)), _fmt(y), _fmt(bar[i, j, g]), _fmt(fin[i, j, g])]
+            for i, d in enumerate(dates) for j, h in enumerate(horizons) for g, y in enumerate(ys)]
+    _write_csv(path, ["date", "horizon", "y", "cdf", "finverse"], rows)
+    return path

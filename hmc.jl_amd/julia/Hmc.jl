@@ -15,7 +15,8 @@
 # past the end date), saveresults with and without signals -- written by the library's native CSV writer
 # (hmcg_save_results_csv: CSV.jl 0.5.16 float text, 250k rows x 5 files in under a second).  Not wired here (available
 # through the C ABI and the Python host layer): checkpoint/resume, the smoothed-probability output, the correlation
-# workbook writer (calccorr's matrices themselves: estimatewindows(...; corr=true)).  runaggregate /
+# workbook writer (calccorr's matrices themselves: estimatewindows(...; corr=true)).  calccdfs / predictive_cdf: the
+# predictive CDFs of code/hassan_cdfs/calc_cdfs.jl from the draws, on the device (hmcg_predictive_cdf).  runaggregate /
 # calcdispersion of the reference work unchanged on the files written here (same names, columns and float text).
 #
 # Reference lines mirrored: estopt src/Hmc.jl:17-73, accessors :85-107, makedate :573-582,
@@ -83,7 +84,7 @@ end
 const HMCG_MAXTAIL = 256
 const HMCG_MAXDEV = 16
 
-struct hmcg_timing                    # include/hmcg.h (ABI 107)
+struct hmcg_timing                    # include/hmcg.h (ABI 108)
     kernel_ms::Float64
     launches::Int32
     threads_per_window::Int32
@@ -96,6 +97,21 @@ struct hmcg_timing                    # include/hmcg.h (ABI 107)
     occupancy::Int32
     buckets::Int32
     streaming::Int32
+end
+
+const HMCG_PRED_ROUND5 = Int32(1)
+struct hmcg_predictive                # include/hmcg.h: predictive CDFs of the regime mixture (calc_cdfs.jl)
+    struct_size::Int32
+    W::Int32
+    K::Int32
+    device::Int32
+    nd::Int64
+    nd_ld::Int64
+    G::Int32
+    n_h::Int32
+    horizons::NTuple{HMCG_MAXH,Int32}
+    flags::Int32
+    reserved::Int32
 end
 
 last_error() = unsafe_string(ccall((:hmcg_last_error, LIBHMCG), Cstring, ()))
@@ -244,6 +260,63 @@ derives from the CSV headers -- μ1..K, σ1..K, π1..K, trans_i_j (i fastest), f
 """
 corrnames(K::Integer, horizons) = vcat(["μ$i" for i in 1:K], ["σ$i" for i in 1:K], ["π$i" for i in 1:K],
                                        vec(["trans_$(i)_$(j)" for i in 1:K, j in 1:K]), ["forecast_$(horizons[1])"])
+
+# ---- predictive CDFs (code/hassan_cdfs/calc_cdfs.jl:31-42) -----------------------------------------------------------
+_predictive(W, K, nd, ld, G, horizons, device, round5) =
+    hmcg_predictive(Int32(sizeof(hmcg_predictive)), Int32(W), Int32(K), Int32(device), Int64(nd), Int64(ld), Int32(G),
+                    Int32(length(horizons)), ntuple(i -> i <= length(horizons) ? Int32(horizons[i]) : Int32(0), HMCG_MAXH),
+                    round5 ? HMCG_PRED_ROUND5 : Int32(0), Int32(0))
+
+"""
+    predictive_cdf(μ, σ, πe, A, ys; horizons=[0], device=0, round5=true) -> Array (G, n_h, W)
+
+hmcg_predictive_cdf over host draw arrays in the layouts estimatewindows fills -- μ, σ, πe (nrun, K, W), A (nrun, K, K, W),
+`nothing` when every horizon is 0: per window and horizon the mean over the draws of
+Σ_k ω[k] Φ((y - μ[k]) / sqrt(σ[k])), ω = πe A^h -- `expectationsbar` of calc_cdfs.jl:39-41 at h = 0.
+"""
+function predictive_cdf(μ::Array{Float64,3}, σ::Array{Float64,3}, πe::Array{Float64,3}, A, ys; horizons=[0], device::Integer=0,
+                        round5::Bool=true)
+    nrun, K, W = size(μ)
+    grid = Vector{Float64}(collect(ys))
+    cdf = Array{Float64}(undef, length(grid), length(horizons), W)
+    pa = A === nothing ? Ptr{Float64}(C_NULL) : pointer(A)
+    rc = GC.@preserve μ σ πe A grid cdf ccall((:hmcg_predictive_cdf, LIBHMCG), Cint,
+        (Ref{hmcg_predictive}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}),
+        _predictive(W, K, nrun, nrun, length(grid), horizons, device, round5), μ, σ, πe, pa, grid, cdf, C_NULL)
+    rc == 0 || error("libhmcgibbs rc=$rc: $(last_error())")
+    return cdf
+end
+
+"""
+    predictive_cdf_device(W, K, nd, ld, dμ, dσ, dπe, dA, dgrid, G, dcdf; horizons=[0], device=0, round5=true, stream=C_NULL)
+
+hmcg_predictive_cdf_device over device pointers (dA = C_NULL when every horizon is 0); enqueued on `stream`
+(C_NULL: the library's own) and not waited for.
+"""
+function predictive_cdf_device(W, K, nd, ld, dμ::Ptr{Float64}, dσ::Ptr{Float64}, dπe::Ptr{Float64}, dA::Ptr{Float64},
+                               dgrid::Ptr{Float64}, G, dcdf::Ptr{Float64}; horizons=[0], device::Integer=0, round5::Bool=true,
+                               stream::Ptr{Cvoid}=C_NULL)
+    rc = ccall((:hmcg_predictive_cdf_device, LIBHMCG), Cint,
+               (Ref{hmcg_predictive}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid},
+                Ptr{Cvoid}), _predictive(W, K, nd, ld, G, horizons, device, round5), dμ, dσ, dπe, dA, dgrid, dcdf, stream, C_NULL)
+    rc == 0 || error("libhmcgibbs rc=$rc: $(last_error())")
+    return nothing
+end
+
+"""
+    calccdfs(opts, ys=-5:.25:15; horizons=[0], device=0) -> (dates, ys, expectationsbar (G, n_h, W))
+
+calc_cdfs.jl without the per-draw files and the plots: estimates the windows and takes the predictive CDFs from their draws
+on the device.  `quantile.(Normal(), expectationsbar)` (Distributions) gives upstream's `finverse`.
+"""
+function calccdfs(opts::Vector{estopt}, ys=-5:.25:15; horizons=[0], device::Integer=0)
+    samples, _, _ = estimatewindows(opts; device=device)
+    W, K = length(opts), opts[1].D
+    cat3(f) = cat((f(s) for s in samples)...; dims=3)
+    μ, σ, πe = cat3(s -> s.μ), cat3(s -> s.σ), cat3(s -> s.πb[:, 1, :])
+    A = any(h -> h > 0, horizons) ? cat((s.A for s in samples)...; dims=4) : nothing
+    return [enddate(o) for o in opts], collect(ys), predictive_cdf(μ, σ, πe, A, ys; horizons=horizons, device=device)
+end
 
 """
     estimatemodel(opt) -> (μ, σ, πb, A, forecasts, obsdates)      (src/Hmc.jl:850-865)

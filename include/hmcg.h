@@ -21,6 +21,10 @@
  *                                  per-draw CSV rows of basicsave (src/Hmc.jl:707-722).
  *   W windows in one call          replace the SLURM array fan-out, one process per
  *                                  window (slurmscripts/base_estimation.sh:5,17).
+ *   hmcg_predictive_cdf[_device]   code/hassan_cdfs/calc_cdfs.jl:31-42: per end date the mean over the draws of the
+ *                                  regime mixture's normal CDF on a grid of points (`expectationsbar`), taken from the
+ *                                  draw arrays instead of the three per-draw CSV files it reads back; with horizons > 0
+ *                                  the same mixture under the h-step state law pi_end * A^h of forecast (src/Hmc.jl:662-663).
  *
  * Conventions: plain C structs, fixed-width ints, no C++ types or exceptions cross
  * the boundary.  Return 0 on success, negative on API misuse (HMCG_E_*), positive
@@ -53,7 +57,7 @@
 extern "C" {
 #endif
 
-#define HMCG_VERSION 107
+#define HMCG_VERSION 108
 #define HMCG_MAXH 8
 #define HMCG_MAXTAIL 256        /* most signal steps past the end date (sigLen, src/Hmc.jl:888) */
 #define HMCG_MAXK 8
@@ -241,6 +245,41 @@ int hmcg_estimate_batch_multi(const hmcg_config* cfg, int32_t n_devices, const i
                               const double* Y, const int32_t* T, const double* yreal,
                               double* mu, double* sig2, double* A, double* pi_end, double* fcast,
                               double* summary, int32_t* status, const hmcg_extras* extras, hmcg_timing* timing);
+
+/* ---- predictive CDFs of the regime mixture (calc_cdfs.jl) ----------------------------------------------------------------
+ * cdf[w][j][g] = mean over the nd draws d of  sum_k omega_{d,j}[k] * Phi((grid[g] - mu_d[k]) / sqrt(sig2_d[k])),
+ * omega_{d,j} = pi_end_d * A_d^h_j, built by h_j successive row-vector x matrix products (k ascending in every dot product),
+ * Phi(z) = erfc(-z / sqrt 2) / 2 as StatsFuns.normcdf computes it.  horizons[j] = 0 is the end date itself: calc_cdfs.jl:39-41,
+ * `expectationsbar` of one end date on ys = grid.  The draw arrays are those of the estimate entries (layouts above) with
+ * leading dimension nd_ld >= nd: element (d, k, w) at d + nd_ld * (k + K * w), A's (d, i, j, w) at d + nd_ld * (i + K * (j + K * w)).
+ * HMCG_PRED_ROUND5: every input (draws and grid) is first rounded as basicsave rounds a CSV cell (round(x; digits=5)), so the
+ * values are the cells upstream reads back; without it the raw draws are used.  IEEE cases fall as they do in Julia: a
+ * variance of 0 gives Phi = 0 or 1 and NaN where grid[g] == mu; a NaN term makes its cell NaN even under a zero weight.
+ * Deterministic: the draws are reduced in fixed slabs of draws, in draw order inside a slab and slab by slab after that (no
+ * floating-point atomics), so the result is bit-identical from run to run, from both entries, and however the host entry
+ * cuts its upload into chunks (HMCG_CHUNK_DRAWS under HMCG_DIAG=1, rounded up to whole slabs).
+ * Misuse (HMCG_E_BADARG, checked before any HIP call): struct_size, K outside 2..HMCG_MAXK, G outside 1..HMCG_MAXGRID, n_h
+ * outside 1..HMCG_MAXH, a horizon outside 0..HMCG_PRED_MAXH, W < 1, nd < 1, nd_ld < nd, a NULL mu / sig2 / pi_end / grid /
+ * cdf, NULL A with a horizon > 0; the host entry also refuses a non-finite grid point. */
+#define HMCG_PRED_ROUND5 1
+#define HMCG_MAXGRID 4096
+#define HMCG_PRED_MAXH 1024            /* largest horizon */
+typedef struct hmcg_predictive {
+    int32_t struct_size, W, K, device;
+    int64_t nd, nd_ld;                 /* draws per window; leading dimension of the draw arrays (>= nd) */
+    int32_t G, n_h;                    /* grid points 1..HMCG_MAXGRID; horizons 1..HMCG_MAXH */
+    int32_t horizons[HMCG_MAXH];       /* 0 = the end date itself (calc_cdfs.jl) */
+    int32_t flags, reserved;
+} hmcg_predictive;
+/* Device entry: every data pointer is HBM-resident on p->device; enqueued on `stream` (NULL: the library's own) behind the
+ * library's earlier work there; returns after enqueueing unless `timing` is given (kernel_ms: HIP events around the kernels). */
+int hmcg_predictive_cdf_device(const hmcg_predictive* p, const double* dmu, const double* dsig2, const double* dpi_end,
+                               const double* dA /* NULL iff every horizon is 0 */, const double* dgrid,
+                               double* dcdf /* [W][n_h][G] */, void* stream, hmcg_timing* timing);
+/* Host entry (blocking): uploads the draws in chunks of whole slabs through pinned staging, the copy of one chunk beside the
+ * kernel of the one before. */
+int hmcg_predictive_cdf(const hmcg_predictive* p, const double* mu, const double* sig2, const double* pi_end,
+                        const double* A, const double* grid, double* cdf, hmcg_timing* timing);
 
 /* ---- per-draw CSV output (host code, no GPU): basicsave / saveresults, src/Hmc.jl:707-748 ------------------------------
  * The five per-window files `filtered_means_<date>.csv`, `filtered_variances_<date>.csv`, `filtered_state_probs_<date>.csv`,
