@@ -125,7 +125,7 @@ def test_signals_past_the_end_date_reporting(oracle):
     assert np.max(np.abs(rep["fcast"][:, 0] - (a * ysig + (1 - a) * plain["fcast"][:, 0]))) < 1e-12
     assert np.max(np.abs(rep["pi_end"].sum(axis=1) - 1)) < 1e-12
     assert np.max(np.abs(rep["pi_end"] - plain["pi_end"])) > 1e-3              # smoothed at endIndex != filtered at the end
-    # the smoother row itself: rerun one sweep's filter + smoother from the final parameters is not available
-    # draw by draw, so check the defining property on the last draw's neighbours instead: with sigLen = 0 both agree
+    # (the smoother row itself, and every other row of that sweep, is recomputed from the run's own outputs by the reference's
+    # formulas in tests/test_sweep_identities.py)  with sigLen = 0 both agree
     same = oracle.estimate_signals(y, K, 5, 20, 2, horizons=(0, 7), yreal=[0.0, 1.0], end_pos=T - 1, **kw)
     assert np.array_equal(same["pi_end"], plain["pi_end"])

@@ -5,6 +5,9 @@ case names a kernel that is not compiled.  The tables are parsed from csrc/varia
 against the kernel symbols of the built libhmcgibbs.so, so that a regex which silently drops a row fails here; the cases are
 the parametrize lists of the GPU tests themselves (importing those modules needs no GPU).
 
+tests/sweep_identities.py's table (one sweep against the reference's formulas, on the oracle and on the GPU) is held to the same
+parsed tables: every smoothing-capable form has a case there.
+
 The device entry's contract is held the same way: every pointer member of hmcg_extras (parsed from include/hmcg.h) is passed by
 some case of tests/test_gpu_device_entry.py, and its split-chain table covers every kernel form."""
 import os
@@ -13,6 +16,7 @@ import shutil
 import subprocess
 
 import device_entry
+import sweep_identities
 import test_gpu_big_variants as big
 import test_gpu_device_entry as dev
 import test_gpu_parity as parity
@@ -200,3 +204,48 @@ def test_split_chain_table_covers_every_kernel_form():
         carried |= device_entry.extras_passed(*args, **kw) & set(device_entry.CARRIED)
     assert carried == set(device_entry.CARRIED) - {"status"}, sorted(carried)
     assert {v for c in cases for k, v in c["env"] if k == "HMCG_FLAVOUR"} == set(FLAVOUR)
+
+
+# ---- one sweep against the reference's formulas (tests/sweep_identities.py) ----
+def test_sweep_identity_cases_cover_every_smoothing_form():
+    """A SM or SIG + SM row, or a smoothing form of the LDS-resident kernel, that is added to the variant tables without a case in
+    sweep_identities.CASES fails here; so does a case that names a row which is not compiled, or whose windows the production
+    dispatch would hand to another kernel."""
+    rows, cases = big.register_rows(), sweep_identities.CASES
+    reg = [c for c in cases if c["kernel"] == "register"]
+    # every SM register row's (K, L); the flavours a case forces are compiled
+    sm_rows = {(K, L) for (K, L, nt, sig, sm, _, _) in rows if (nt, sig, sm) == (256, False, True)}
+    named = {(c["K"], c["L"]) for c in reg if c["path"] == "smooth"}
+    assert sm_rows and sm_rows <= named, "SM rows without a sweep-identity case: %s" % sorted(sm_rows - named)
+    for c in reg:
+        sig = c["path"] != "smooth"
+        if c["flavour"]:
+            assert (c["K"], c["L"], 256, sig, True) + FLAVOUR[c["flavour"]] in rows, c["id"]
+        else:
+            assert sig and [r[5:] for r in rows if r[:5] == (c["K"], c["L"], 256, True, True)] == [(0, 1)], c["id"]
+        classes = sorted({L for (K, L, nt, s, m, _, _) in rows if (K, nt, s, m) == (c["K"], 256, sig, True)})
+        for T in c["lens"]:                                   # every window selects the row the case names: one launch, no buckets
+            assert min(L for L in classes if 256 * L >= T) == c["L"], (c["id"], T)
+    assert {fl for c in reg if c["path"] == "smooth" and c["L"] in (1, 4) for fl in [c["flavour"]]} == set(FLAVOUR)
+    assert any(c["flavour"] == "h" and any(769 <= T <= 1024 for T in c["lens"]) for c in reg)
+    # every SIG + SM register row's K
+    sigsm_ks = {K for (K, L, nt, sig, sm, _, _) in rows if (nt, sig, sm) == (256, True, True)}
+    named_ks = {c["K"] for c in reg if c["path"] != "smooth"}
+    assert sigsm_ks and sigsm_ks <= named_ks, "SIG + SM rows without a sweep-identity case: K = %s" % sorted(sigsm_ks - named_ks)
+    # each smoothing form of the LDS-resident kernel, reached the way production reaches it
+    forms = {}
+    for c in cases:
+        if c["kernel"] != "register":
+            sig, stream, top = c["path"] != "smooth", c["kernel"] == "stream", max(c["lens"])
+            assert (sig, True, stream, c["K"]) in big.big_instantiations(), c["id"]
+            assert top > big.ladder_ceiling(c["K"], sig, True) and top % 256 != 0, c["id"]
+            assert (big.dyn_bytes((top + 255) // 256) > big.LDS_LIMIT) == stream, c["id"]
+            forms.setdefault((sig, True, stream), c["id"])
+    smoothing_forms = {f for f in big.big_forms().values() if f[1]}
+    assert len(smoothing_forms) == 4 and smoothing_forms <= set(forms), sorted(smoothing_forms - set(forms))
+    # the tail path (end_pos with smoothing outputs) on a register form, an LDS form and a streaming form
+    assert {c["kernel"] for c in cases if c["path"] == "tail+smooth"} == {"register", "lds", "stream"}
+    for id in sweep_identities.MULTI_SAMPLE + sweep_identities.DEVICE_ENTRY:
+        assert sweep_identities.case_by_id(id)["path"] == "tail+smooth"
+    assert [sweep_identities.case_by_id(id)["kernel"] for id in sweep_identities.MULTI_SAMPLE] == ["register", "lds", "stream"]
+    assert [sweep_identities.case_by_id(id)["kernel"] for id in sweep_identities.DEVICE_ENTRY] == ["register", "lds"]
