@@ -18,11 +18,9 @@ import numpy as np
 
 from hmc_jl_amd import synth
 
-import test_gpu_big_variants as big
-import test_gpu_parity as parity
-import test_gpu_variants as reg
+import kernel_tables as kt
+from kernel_tables import NT
 
-NT = 256
 HORIZONS = (1, 12)
 
 Case = collections.namedtuple("Case", "id kind K T sig smooth env tpw burnin nrun n_samples alpha nu recipe seed window_id expect branches")
@@ -118,15 +116,15 @@ def reg_length(L):
 def mixed_cases():
     """One window for every instantiation the coverage contract names (tests/test_variant_coverage.py), from the same lists."""
     out = []
-    for (K, L, path, fl) in reg.CASES:
+    for (K, L, path, fl) in kt.VARIANT_CASES:
         out.append(_mixed("K%d-L%d-%s-%s" % (K, L, path, fl), "reg", K, reg_length(L), path == "sig", path == "smooth",
                           {"HMCG_FLAVOUR": fl}, 0, (K, L, path, fl)))
-    for (K, L) in reg.SIGSMOOTH:
+    for (K, L) in kt.SIGSMOOTH:
         out.append(_mixed("sigsmooth-K%d-L%d" % (K, L), "sigsmooth", K, reg_length(L), True, True, {}, 0, (K, L)))
-    for (K, L, nt) in parity.THREADS_PER_WINDOW_CASES:
+    for (K, L, nt) in kt.OWN_THREAD_COUNT:
         out.append(_mixed("tpw-K%d-L%d-NT%d" % (K, L, nt), "tpw", K, 1000, False, False, {}, nt, (K, L, nt)))
-    for (sig, sm, st, K) in big.BIG:
-        out.append(_mixed("big-%s-K%d" % (big.form_id(sig, sm, st), K), "big", K, big.coverage_lengths(sig, sm, st, K)[0], sig, sm,
+    for (sig, sm, st, K) in kt.BIG:
+        out.append(_mixed("big-%s-K%d" % (kt.form_id(sig, sm, st), K), "big", K, kt.coverage_lengths(sig, sm, st, K)[0], sig, sm,
                           {}, 0, (sig, sm, st, K)))
     return out
 
@@ -138,11 +136,10 @@ def mixed_cases():
 #   place: (kind, K, T of the short case, T >= 1000, env, expect builder)
 def _place(place, K, T, sig):
     if place in ("p1", "p2", "h"):
-        ladder = sorted(l for (k, l, p) in reg.ROWS if (k, p) == (K, "sig" if sig else "base"))
-        L = min(l for l in ladder if NT * l >= T)
+        L = kt.steps_per_thread(K, T, sig)
         return "reg", {"HMCG_FLAVOUR": place}, (K, L, "sig" if sig else "base", place)
     stream = place == "stream"
-    assert (big.dyn_bytes((T + NT - 1) // NT) > big.LDS_LIMIT) == stream and T > big.ladder_ceiling(K, sig, False), (place, K, T)
+    assert (kt.dyn_bytes((T + NT - 1) // NT) > kt.LDS_LIMIT) == stream and T > kt.ladder_ceiling(K, sig, False), (place, K, T)
     return "big", {}, (sig, False, stream, K)
 
 

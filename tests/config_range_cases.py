@@ -21,10 +21,9 @@ import numpy as np
 
 from hmc_jl_amd import synth
 
-import test_gpu_big_variants as big
-import test_gpu_parity as parity
+import kernel_tables as kt
+from kernel_tables import NT
 
-NT = 256
 FULL = (0, 1, 25, 26, 27, 12, 12, 5000)              # H = 4..7 use its prefixes
 REVERSED = (5000, 0, 27, 26)                         # lane order ascending, horizon order not
 JUNK_HORIZON = 999999                                # in a blended slot: ignored
@@ -265,11 +264,10 @@ def planned_route(c):
     env = dict(c.env)
     sig, top = is_sig(c), max(c.lens)
     if c.tpw:
-        mine = [(K, L, nt) for (K, L, nt) in parity.THREADS_PER_WINDOW_CASES if (K, nt) == (c.K, c.tpw) and nt * L >= top > nt * L // 2]
+        mine = [(K, L, nt) for (K, L, nt) in kt.OWN_THREAD_COUNT if (K, nt) == (c.K, c.tpw) and nt * L >= top > nt * L // 2]
         return ("tpw", mine[0][1]) if mine and not env else ("none", 0)
-    if "HMCG_FORCE_BIG" not in env and top <= big.ladder_ceiling(c.K, sig, False):
-        ladder = sorted(L for (k, L, nt, s, m, _, _) in big.REG_ROWS if (k, nt, s, m) == (c.K, NT, sig, False))
-        return ("none", 0) if "HMCG_FORCE_STREAM" in env else ("register", min(L for L in ladder if NT * L >= top))
+    if "HMCG_FORCE_BIG" not in env and top <= kt.ladder_ceiling(c.K, sig, False):
+        return ("none", 0) if "HMCG_FORCE_STREAM" in env else ("register", kt.steps_per_thread(c.K, top, sig))
     L = (top + NT - 1) // NT
-    stream = "HMCG_FORCE_STREAM" in env or big.dyn_bytes(L) > big.LDS_LIMIT
+    stream = "HMCG_FORCE_STREAM" in env or kt.dyn_bytes(L) > kt.LDS_LIMIT
     return ("stream" if stream else "lds"), L

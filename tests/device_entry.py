@@ -175,3 +175,42 @@ def estimate_batch_device_np(Y, T, K, burnin, nrun, horizons=(12,), yreal=None, 
         else:
             torch.cuda.synchronize(c.dev)
     return c.collect()
+
+
+# ---- comparisons between two runs ----
+T_AXIS = {"x_final": 0, "xstate": 0, "pif_final": 0, "pi_smooth_mean": 0, "pi_filter_mean": 0, "pi_smooth_draws": 1}   # per window
+# (every kernel guards its per-step stores with t < T[w], pif_final included)
+UNTOUCHED_BEYOND_T = tuple(T_AXIS)
+
+
+def arrays_of(g):
+    return {k: v for k, v in g.items() if isinstance(v, np.ndarray)}
+
+
+def assert_device_equals_host(d, h, Tw, save=None):
+    """Every array both entries return, bit for bit, over what a window owns: steps t < T[w] of the per-step arrays, the saved
+    positions of sigvals.  Beyond it the host entry hands back zeros; the device entry must have left the sentinel."""
+    D, Hh = arrays_of(d), arrays_of(h)
+    assert set(D) <= set(Hh), sorted(set(D) - set(Hh))
+    for k, dv in D.items():
+        hv = Hh[k]
+        assert dv.shape == hv.shape and dv.dtype == hv.dtype, (k, dv.shape, hv.shape, dv.dtype, hv.dtype)
+        for w, T in enumerate(Tw):
+            x, y = dv[w], hv[w]
+            if k in T_AXIS:
+                ax = T_AXIS[k]
+                rest = np.take(x, range(int(T), x.shape[ax]), axis=ax)
+                x, y = np.take(x, range(int(T)), axis=ax), np.take(y, range(int(T)), axis=ax)
+                if k in UNTOUCHED_BEYOND_T:
+                    assert np.array_equal(rest, sentinel_like(rest), equal_nan=True), (k, w, "written beyond T")
+            elif k == "sigvals" and save is not None:
+                n = int(save[w][1] - save[w][0])
+                x, y = x[:, :n], y[:, :n]
+            assert np.array_equal(x, y, equal_nan=True), (k, w)
+
+
+def kept_after(sweeps, burnin, nrun, n_samples):
+    """Kept draws of the first `sweeps` sweeps (sample-major on the signal path)."""
+    per = burnin + nrun
+    full, rem = divmod(sweeps, per)
+    return min(full, n_samples) * nrun + (max(0, rem - burnin) if full < n_samples else 0)

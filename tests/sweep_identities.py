@@ -22,14 +22,13 @@ product of its own beside the full smoother.  tests/test_variant_coverage.py hol
 import numpy as np
 
 from hmc_jl_amd import synth
-from test_gpu_big_variants import NT, STREAM_T, ladder_ceiling
+from kernel_tables import NT, STREAM_T, ladder_ceiling
 
 LD = np.longdouble
 IDENTITIES = ("filter", "smoother", "row", "forecast")
 KAPPA, ALPHA_SIG = 0.6, 2.0                      # the signal paths' kappa and alpha = nu
 MAXTAIL = 256                                    # HMCG_MAXTAIL (tests/test_sweep_identities.py holds it to _lib's)
 TAIL_HORIZONS, TAIL_BLEND = (0, 12), 1           # slot 0 is the blend (h == sigLen), slot 1 is h = sigLen + 12
-FLAVOUR_WAVES = {"p1": (0, 1), "p2": (0, 2), "h": (4, 2)}        # HMCG_FLAVOUR -> (helper_waves, occupancy)
 
 
 def normpdf_ld(y, mu, sd):

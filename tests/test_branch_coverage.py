@@ -18,6 +18,7 @@ the parent commit's whole `-m "not gpu"` suite takes 7 min 7 s."""
 import pytest
 
 import branch_cases as bc
+import kernel_tables as kt
 import test_gpu_big_variants as big
 import test_gpu_branches as gpu
 import test_variant_coverage as cov
@@ -27,16 +28,16 @@ DIRECTED = gpu.DIRECTED
 
 
 def instantiation_of(c):
-    """The kernel a mixed-label case selects, in the tuples of big.register_rows() / big.big_instantiations()."""
+    """The kernel a mixed-label case selects, in the tuples of kt.register_rows() / kt.big_instantiations()."""
     if c.kind == "reg":
         K, L, path, fl = c.expect
-        return (K, L, 256) + cov.PATH[path] + cov.FLAVOUR[fl]
+        return (K, L, 256) + kt.PATH[path] + kt.FLAVOUR_WAVES[fl]
     if c.kind == "sigsmooth":
         K, L = c.expect
         return (K, L, 256, True, True, 0, 1)
     if c.kind == "tpw":
         K, L, nt = c.expect
-        mine = [r for r in big.register_rows() if r[:5] == (K, L, nt, False, False)]
+        mine = [r for r in kt.register_rows() if r[:5] == (K, L, nt, False, False)]
         return mine[0] if len(mine) == 1 else (K, L, nt, False, False, -1, -1)
     return tuple(c.expect)
 
@@ -49,7 +50,7 @@ def test_the_gpu_module_runs_these_lists():
 
 
 def test_mixed_label_list_is_the_instantiation_set():
-    rows, bigs = set(big.register_rows()), set(big.big_instantiations())
+    rows, bigs = set(kt.register_rows()), set(kt.big_instantiations())
     named = [instantiation_of(c) for c in MIXED]
     assert len(set(named)) == len(named), "two mixed-label cases name one kernel"
     regs = {n for n in named if len(n) == 7}
@@ -70,11 +71,11 @@ def test_mixed_label_cases_select_their_kernel_by_length():
         if c.kind in ("reg", "sigsmooth"):
             K, L = c.expect[:2]
             path = (c.sig, c.smooth)
-            below = [l for (k, l, nt, s, m, _, _) in big.register_rows() if (k, nt, s, m) == (K, 256) + path and l < L]
+            below = [l for (k, l, nt, s, m, _, _) in kt.register_rows() if (k, nt, s, m) == (K, 256) + path and l < L]
             assert 256 * max(below, default=0) < c.T <= 256 * L and c.T >= 2, c.id
         elif c.kind == "big":
             sig, sm, st, K = c.expect
-            assert c.T > big.ladder_ceiling(K, sig, sm) and (big.dyn_bytes((c.T + 255) // 256) > big.LDS_LIMIT) == st, c.id
+            assert c.T > kt.ladder_ceiling(K, sig, sm) and (kt.dyn_bytes((c.T + 255) // 256) > kt.LDS_LIMIT) == st, c.id
 
 
 @pytest.mark.parametrize("case", MIXED, ids=[c.id for c in MIXED])

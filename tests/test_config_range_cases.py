@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import config_range_cases as cr
+import kernel_tables as kt
 import test_gpu_config_range as gpu
 import test_variant_coverage as cov
 
@@ -124,7 +125,7 @@ def test_each_case_selects_the_route_it_claims():
         if c.route in ("lds", "stream"):
             assert L == (max(c.lens) + 255) // 256, c.id
         if c.route == "register":
-            assert c.K <= 4 and max(c.lens) <= cov.big.ladder_ceiling(c.K, cr.is_sig(c), False), c.id
+            assert c.K <= 4 and max(c.lens) <= kt.ladder_ceiling(c.K, cr.is_sig(c), False), c.id
         if c.route == "lds":
             assert c.K >= 5 or dict(c.env).get("HMCG_FORCE_BIG"), c.id
 

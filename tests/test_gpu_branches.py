@@ -51,8 +51,8 @@ import pytest
 from hmc_jl_amd import _lib
 
 import branch_cases as bc
-import test_gpu_big_variants as big
-from test_gpu_parity import TOL, close
+from kernel_tables import FLAVOUR_WAVES
+from oracle_parity import FLOAT_KEYS, TOL, assert_ran_on_big, assert_window_matches_oracle, close
 
 pytestmark = pytest.mark.gpu
 
@@ -64,8 +64,7 @@ def assert_intended_kernel_ran(c, g):
     if c.kind == "reg":
         K, L, path, fl = c.expect
         assert g["steps_per_thread"] == L and g["threads_per_window"] == 256, (g["steps_per_thread"], L)
-        assert g["helper_waves"] == (4 if fl == "h" else 0)
-        assert g["occupancy"] == {"p1": 1, "p2": 2, "h": 2}[fl] and g["buckets"] == 1
+        assert (g["helper_waves"], g["occupancy"]) == FLAVOUR_WAVES[fl] and g["buckets"] == 1
         assert not g["streaming"]
     elif c.kind == "sigsmooth":
         K, L = c.expect
@@ -76,7 +75,7 @@ def assert_intended_kernel_ran(c, g):
         assert g["threads_per_window"] == nt and g["steps_per_thread"] == L and g["buckets"] == 1
     else:
         sig, smooth, stream, K = c.expect
-        big.assert_ran_on_big(g, stream, c.T, sig, smooth)
+        assert_ran_on_big(g, stream, c.T, sig, smooth)
 
 
 def run_and_compare(oracle, monkeypatch, c):
@@ -86,33 +85,20 @@ def run_and_compare(oracle, monkeypatch, c):
     o = oracle.estimate_signals(Y, c.K, c.burnin, c.nrun, **bc.oracle_kwargs(c, yreal, x0))
     g = _lib.estimate_batch_host(Y[None, :], [c.T], c.K, c.burnin, c.nrun, bc.HORIZONS, yreal[None, :], **bc.gpu_kwargs(c, x0))
     assert_intended_kernel_ran(c, g)
-    assert g["status"][0] == o["status"] == 0, (g["status"][0], o["status"])
-    assert np.array_equal(g["x_final"][0], o["x_final"]), "state path differs"
-    got = dict(mu=g["mu"][0].T, sig2=g["sig2"][0].T, A=np.transpose(g["A"][0], (2, 1, 0)), pi_end=g["pi_end"][0].T,
-               fcast=g["fcast"][0].T, summary=g["summary"][0], pif_final=g["pif_final"][0])
-    ref = {k: o[k] for k in got}
-    if c.smooth:
-        got.update(pi_smooth_mean=g["pi_smooth_mean"][0], pi_filter_mean=g["pi_filter_mean"][0])
-        ref.update(pi_smooth_mean=o["pi_smooth"].mean(axis=0), pi_filter_mean=o["pi_filter_mean"])
+    fields = FLOAT_KEYS + (("pi_smooth_mean", "pi_filter_mean") if c.smooth else ())
     if c.sig:
-        got.update(sigvals=g["sigvals"][0], sample_summary=g["sample_summary"][0])
-        ref.update(sigvals=o["sigvals"], sample_summary=o["sample_summary"])
-    elif c.smooth:                                                            # samples.pib itself: (nd, T, K)
-        got.update(pi_smooth_draws=np.transpose(g["pi_smooth_draws"][0], (2, 1, 0)))
-        ref.update(pi_smooth_draws=o["pi_smooth"])
-    else:                                                                     # calccorr's matrix of the rounded draws (test_gpu_corr.py)
+        fields += ("sigvals", "sample_summary")                               # (sigvals: the whole slab, as wide as the save range)
+    elif c.smooth:
+        fields += ("pi_smooth_draws",)                                        # samples.pib itself: (nd, T, K)
+    assert_window_matches_oracle(g, 0, c.T, o, fields=fields)
+    if not c.sig and not c.smooth:                                            # calccorr's matrix of the rounded draws (test_gpu_corr.py)
         cols = np.concatenate([o["mu"].T, o["sig2"].T, o["pi_end"].T, np.transpose(o["A"], (2, 1, 0)).reshape(c.K * c.K, -1), o["fcast"].T[:1]])
         with np.errstate(invalid="ignore", divide="ignore"):
             want = np.corrcoef(np.round(cols, 5))
         have = g["corr"][0]
         assert np.array_equal(np.isfinite(have), np.isfinite(want)), "corr: the constant columns differ"
         ok = np.isfinite(want)
-        got.update(corr=have[ok])
-        ref.update(corr=want[ok])
-    errs = {k: close(np.asarray(got[k]), np.asarray(ref[k])) for k in got}
-    print(c.id, " ".join("%s=%.1e" % kv for kv in errs.items()))
-    for k, e in errs.items():
-        assert got[k].shape == ref[k].shape and e < TOL, (k, e)
+        assert close(have[ok], want[ok]) < TOL, ("corr", close(have[ok], want[ok]))
     return g, o
 
 

@@ -14,15 +14,11 @@ import numpy as np
 import pytest
 
 from hmc_jl_amd import _lib, device as hdev, synth
+from oracle_parity import TOL, assert_same, assert_window_matches_oracle, close
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-9
 K, HOR = 3, (1, 12)
 NAMES = ("mu", "sig2", "A", "pi_end", "fcast", "summary")
-
-
-def close(g, o):
-    return float(np.max(np.abs(g - o) / (1.0 + np.abs(o)))) if g.size else 0.0
 
 
 @pytest.fixture(scope="module")
@@ -65,10 +61,7 @@ def test_a_window_does_not_depend_on_its_batch(hmclib, oracle, panel460):
     for w in (0, 180, 459):                                           # T = 120, 300, 579 against the oracle
         T = int(Tw[w])
         o = oracle.estimate_window(Y[w, :T], K, burnin, nrun, HOR, yreal[w], window_id=w)
-        assert np.array_equal(g["x_final"][w, :T], o["x_final"]), "state path differs from the oracle (window %d)" % w
-        assert close(g["mu"][w].T, o["mu"]) < TOL and close(g["sig2"][w].T, o["sig2"]) < TOL
-        assert close(np.transpose(g["A"][w], (2, 1, 0)), o["A"]) < TOL
-        assert close(g["pi_end"][w].T, o["pi_end"]) < TOL and close(g["fcast"][w].T, o["fcast"]) < TOL
+        assert_window_matches_oracle(g, w, T, o, fields=("mu", "sig2", "A", "pi_end", "fcast"), status0=False)
 
 
 def test_device_entry_with_the_min_T_hint(hmclib, panel460):
@@ -123,8 +116,7 @@ def test_shuffled_batch_equals_sorted_batch_on_both_entries(hmclib, panel460, mo
     monkeypatch.setenv("HMCG_NO_BUCKET_LISTS", "1")
     h = _lib.estimate_batch_host(np.ascontiguousarray(Y[perm]), Tw[perm], K, burnin, nrun, HOR, np.ascontiguousarray(yreal[perm]),
                                  want_state=True, window_ids=ids[perm])
-    for k in NAMES + ("x_final", "status"):
-        assert np.array_equal(h[k], g[k]), k
+    assert_same(h, g, NAMES + ("x_final", "status"), equal_nan=False)
 
 
 @pytest.mark.parametrize("order", ["sorted", "shuffled"])

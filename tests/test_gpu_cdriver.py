@@ -11,12 +11,13 @@ import numpy as np
 import pytest
 
 from hmc_jl_amd import synth
+from oracle_parity import assert_same, assert_window_matches_oracle
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DRV_DIR = os.path.join(ROOT, "tests", "cdriver")
 DRV = os.path.join(DRV_DIR, "hmcg_cdriver")
-TOL = 1e-9
+DRAWS = ("mu", "sig2", "A", "pi_end", "fcast", "summary")
 
 
 def build_driver():
@@ -68,15 +69,9 @@ def run_driver(tmp_path, mode, Y, Tw, K, burnin, nrun, horizons, yreal, n_sample
     return out, r.stdout
 
 
-def close(g, o):
-    return float(np.max(np.abs(g - o) / (1.0 + np.abs(o)))) if g.size else 0.0
-
-
-def check(g, o, w):
-    assert g["status"][w] == o["status"] == 0
-    assert close(g["mu"][w].T, o["mu"]) < TOL and close(g["sig2"][w].T, o["sig2"]) < TOL
-    assert close(np.transpose(g["A"][w], (2, 1, 0)), o["A"]) < TOL and close(g["pi_end"][w].T, o["pi_end"]) < TOL
-    assert close(g["fcast"][w].T, o["fcast"]) < TOL and close(g["summary"][w], o["summary"]) < TOL
+def check(g, o, w, **sigvals):
+    """(states are not returned on this path)"""
+    assert_window_matches_oracle(g, w, None, o, fields=DRAWS + (("sigvals",) if sigvals else ()), states=False, **sigvals)
 
 
 def test_c_driver_cfg1_estimatemodel(hmclib, oracle, tmp_path):
@@ -99,9 +94,7 @@ def test_c_driver_signal_call(hmclib, oracle, tmp_path):
     for w in range(3):
         o = oracle.estimate_signals(Y[w], K, 3, 8, 3, sig=tuple(sig[w]), kappa=0.6, alpha=2.0, nu=2.0, sigma_signal=float(ssig[w]),
                                     save=tuple(save[w]), yreal=fut[w, 11:12], window_id=w)
-        check(g, o, w)
-        ns = save[w][1] - save[w][0]
-        assert close(g["sigvals"][w][:, :ns], o["sigvals"]) < TOL
+        check(g, o, w, nsave=save[w][1] - save[w][0])
 
 
 def test_c_driver_multi_device_entry_one_device(hmclib, oracle, tmp_path):
@@ -124,8 +117,7 @@ def test_multi_entry_four_virtual_devices_equals_single_device(hmclib, oracle, t
     one, _ = run_driver(tmp_path, 2, Y, Tw, 3, 4, 3000, (1, 12), fut[:, [0, 11]], n_devices=1)
     four, log = run_driver(tmp_path, 2, Y, Tw, 3, 4, 3000, (1, 12), fut[:, [0, 11]], n_devices=4,
                            env_extra={"HMCG_VIRTUAL_DEVICES": "4", "HMCG_CHUNK_DRAWS": "1500"})
-    for k in ("mu", "sig2", "A", "pi_end", "fcast", "summary", "status"):
-        assert np.array_equal(one[k], four[k]), k
+    assert_same(one, four, DRAWS + ("status",), equal_nan=False)
     for w in (0, 3, 10):
         check(four, oracle.estimate_window(Y[w, :Tw[w]], 3, 4, 3000, (1, 12), fut[w, [0, 11]], window_id=w), w)
     # more devices than the box offers without the switch: refused, not silently folded

@@ -22,10 +22,10 @@ import pytest
 import config_range_cases as cr
 import device_entry as de
 from hmc_jl_amd import _lib
-from test_gpu_big_variants import NT, REG_ROWS
-from test_gpu_device_entry import FLAVOUR_WAVES, arrays_of, assert_device_equals_host, assert_identical, kept_after
-from test_gpu_parity import (TOL, check_against_oracle, check_signals_against_oracle, check_tail_signals_against_oracle, close,
-                             close_nan)
+from device_entry import assert_device_equals_host, kept_after
+from kernel_tables import FLAVOUR_WAVES, NT, REG_ROWS
+from oracle_parity import (TOL, assert_same, check_against_oracle, check_signals_against_oracle, check_tail_signals_against_oracle, close,
+                           close_nan)
 
 pytestmark = pytest.mark.gpu
 CASES = cr.CASES
@@ -154,14 +154,7 @@ def test_summaries_from_the_calls_own_draws(hmclib, monkeypatch, c):
             assert "sample_summary" not in g
 
 
-# ---- equalities between two GPU runs (exact) ----
-def assert_same_arrays(a, b, what):
-    A, B = arrays_of(a), arrays_of(b)
-    assert sorted(A) == sorted(B), (what, sorted(A), sorted(B))
-    for k in A:
-        assert np.array_equal(A[k], B[k], equal_nan=A[k].dtype.kind == "f"), (what, k)
-
-
+# ---- equalities between two GPU runs (exact: oracle_parity.assert_same over every array) ----
 DEVICE_CASES = [c for c in H8 if c.route in ("register", "lds")]
 
 
@@ -185,7 +178,7 @@ def test_chunked_run_equals_one_launch(hmclib, monkeypatch, c):
     args, kw = cr.gpu_call(c)
     g = _lib.estimate_batch_host(*args, **kw)
     assert g["launches"] >= 2 and g["launches"] > one["launches"], (g["launches"], one["launches"])
-    assert_same_arrays(g, one, c.id)
+    assert_same(g, one, what=c.id)
 
 
 MULTI_CASES = [c for c in H8 if len(c.lens) >= 3]
@@ -201,7 +194,7 @@ def test_three_devices_equal_one(hmclib, monkeypatch, c):
     g = _lib.estimate_batch_host(*args, devices=[0, 1, 2], **kw)
     assert sorted(d["device"] for d in g["per_device"]) == [0, 1, 2] and sum(d["windows"] for d in g["per_device"]) == len(c.lens)
     assert all(d["windows"] > 0 for d in g["per_device"])
-    assert_same_arrays(g, one, c.id)
+    assert_same(g, one, what=c.id)
 
 
 WRAP_CASES = [c for c in CASES if c.window_base]
@@ -215,7 +208,7 @@ def test_wrapped_window_base_equals_explicit_ids(hmclib, monkeypatch, c):
     assert wrapped.tolist() == [0xFFFFFFFE, 0xFFFFFFFF, 0]
     args, kw = cr.gpu_call(c, window_base=None, window_ids=wrapped)
     assert "window_base" not in kw
-    assert_same_arrays(_lib.estimate_batch_host(*args, **kw), based, c.id)
+    assert_same(_lib.estimate_batch_host(*args, **kw), based, what=c.id)
 
 
 SPLIT_CASES = [c for c in CASES if c.split]
@@ -244,7 +237,7 @@ def test_cut_chain_equals_one_launch(hmclib, monkeypatch, c):
                 assert np.array_equal(g[k][..., :d], one[k][..., :d], equal_nan=True), (cuts, end, k)
                 assert np.isnan(g[k][..., d:]).all(), (cuts, end, k, "a draw beyond this piece was written")
             base = end
-        assert_identical(g, one, "%s cut after %s" % (c.id, cuts))
+        assert_same(g, one, what="%s cut after %s" % (c.id, cuts))
 
 
 # ---- extras.corr ----

@@ -24,10 +24,11 @@ import pytest
 
 import device_entry as de
 from hmc_jl_amd import _lib, synth
-from test_gpu_big_variants import (NT, REG_ROWS, SIGMA_SIGNAL, STREAM_T, assert_ran_on_big, check_smoothing_against_oracle,
-                                   coverage_lengths, ladder_ceiling, signal_ranges)
-from test_gpu_parity import (TOL, check_against_oracle, check_signals_against_oracle, check_tail_signals_against_oracle,
-                             check_teacher_forced_against_oracle, close)
+from device_entry import arrays_of, assert_device_equals_host, kept_after
+from kernel_tables import FLAVOUR_WAVES, NT, STREAM_T, coverage_lengths, ladder_ceiling, register_classes
+from oracle_parity import (SIGMA_SIGNAL, assert_ran_on_big, assert_same, check_against_oracle, check_signals_against_oracle,
+                           check_smoothing_against_oracle, check_tail_signals_against_oracle, check_teacher_forced_against_oracle,
+                           signal_ranges)
 
 pytestmark = pytest.mark.gpu
 
@@ -155,10 +156,6 @@ class Recorder:
 
 
 # ---- which kernel ran ----
-def register_classes(K, sig, smooth):
-    return sorted({L for (k, L, nt, s, m, _, _) in REG_ROWS if (k, nt, s, m) == (K, NT, sig, smooth)})
-
-
 def assert_ran_as_planned(g, c):
     path, K, lens = c["path"], c["K"], c["lens"]
     sig, smooth = path in ("sig", "tail", "sig+smooth"), path in ("smooth", "sig+smooth")
@@ -175,46 +172,6 @@ def assert_ran_as_planned(g, c):
     else:
         assert maxT > ladder_ceiling(K, sig, smooth)                          # the production route, no HMCG_FORCE_BIG
         assert_ran_on_big(g, c["kernel"] == "stream", maxT, sig, smooth)
-
-
-# ---- comparisons between two runs ----
-T_AXIS = {"x_final": 0, "xstate": 0, "pif_final": 0, "pi_smooth_mean": 0, "pi_filter_mean": 0, "pi_smooth_draws": 1}   # per window
-# (every kernel guards its per-step stores with t < T[w], pif_final included)
-UNTOUCHED_BEYOND_T = tuple(T_AXIS)
-
-
-def arrays_of(g):
-    return {k: v for k, v in g.items() if isinstance(v, np.ndarray)}
-
-
-def assert_identical(a, b, what):
-    """Two device-entry results: every array, every byte (NaN sentinels included)."""
-    A, B = arrays_of(a), arrays_of(b)
-    assert sorted(A) == sorted(B), (what, sorted(A), sorted(B))
-    for k in A:
-        assert np.array_equal(A[k], B[k], equal_nan=A[k].dtype.kind == "f"), (what, k)
-
-
-def assert_device_equals_host(d, h, Tw, save=None):
-    """Every array both entries return, bit for bit, over what a window owns: steps t < T[w] of the per-step arrays, the saved
-    positions of sigvals.  Beyond it the host entry hands back zeros; the device entry must have left the sentinel."""
-    D, Hh = arrays_of(d), arrays_of(h)
-    assert set(D) <= set(Hh), sorted(set(D) - set(Hh))
-    for k, dv in D.items():
-        hv = Hh[k]
-        assert dv.shape == hv.shape and dv.dtype == hv.dtype, (k, dv.shape, hv.shape, dv.dtype, hv.dtype)
-        for w, T in enumerate(Tw):
-            x, y = dv[w], hv[w]
-            if k in T_AXIS:
-                ax = T_AXIS[k]
-                rest = np.take(x, range(int(T), x.shape[ax]), axis=ax)
-                x, y = np.take(x, range(int(T)), axis=ax), np.take(y, range(int(T)), axis=ax)
-                if k in UNTOUCHED_BEYOND_T:
-                    assert np.array_equal(rest, de.sentinel_like(rest), equal_nan=True), (k, w, "written beyond T")
-            elif k == "sigvals" and save is not None:
-                n = int(save[w][1] - save[w][0])
-                x, y = x[:, :n], y[:, :n]
-            assert np.array_equal(x, y, equal_nan=True), (k, w)
 
 
 # ---- (a) oracle parity through the device entry; the host entry agrees bit for bit ----
@@ -260,10 +217,10 @@ def test_fresh_call_ignores_buffer_contents(hmclib, c):
     assert (first["status"] == 0).all(), first["status"]
     again = de.estimate_batch_device_np(*args, **kw, **device_kw(c), out=first)
     assert again["_call"].buf is first["_call"].buf
-    assert_identical(again, first, "second run into dirty buffers")
+    assert_same(again, first, what="second run into dirty buffers")
     third = de.estimate_batch_device_np(*args, **kw, **device_kw(c), out=first, timed=False)
     assert third["kernel_ms"] is None
-    assert_identical(third, first, "third run, enqueue-only")
+    assert_same(third, first, what="third run, enqueue-only")
 
 
 # ---- (b) split chains ----
@@ -289,14 +246,6 @@ SPLIT_CASES = [
     split("lds-sm-K6", "sm", "lds", "smooth", 6, 400),
     split("lds-sigsm-K8", "sig+sm", "lds", "sig+smooth", 8, 300),
 ]
-FLAVOUR_WAVES = {"p1": (0, 1), "p2": (0, 2), "h": (4, 2)}                 # HMCG_FLAVOUR -> (helper_waves, occupancy)
-
-
-def kept_after(sweeps, burnin, nrun, n_samples):
-    """Kept draws of the first `sweeps` sweeps (sample-major on the signal path)."""
-    per = burnin + nrun
-    full, rem = divmod(sweeps, per)
-    return min(full, n_samples) * nrun + (max(0, rem - burnin) if full < n_samples else 0)
 
 
 @pytest.mark.parametrize("c", SPLIT_CASES, ids=[c["id"] for c in SPLIT_CASES])
@@ -331,7 +280,7 @@ def test_split_chain_equals_one_launch(hmclib, monkeypatch, c):
                 assert np.array_equal(g[k][..., :d], one[k][..., :d], equal_nan=True), (cuts, i, k)
                 assert np.isnan(g[k][..., d:]).all(), (cuts, i, k, "a draw beyond this piece was written")
             base = end
-        assert_identical(g, one, "pieces %s" % (cuts,))
+        assert_same(g, one, what="pieces %s" % (cuts,))
 
 
 # ---- (c) skipped windows ----
@@ -397,7 +346,7 @@ def test_lds_resident_smoothing_without_pif_final_is_refused(hmclib):
     assert "pif_final" not in left
     for k, v in arrays_of(left).items():
         assert np.array_equal(v, de.sentinel_like(v), equal_nan=True), (k, "written by a refused call")
-    assert_identical(de.estimate_batch_device_np(*args, **kw), ok, "the next valid call")
+    assert_same(de.estimate_batch_device_np(*args, **kw), ok, what="the next valid call")
     # the register-resident smoothing kernels keep pif in registers: no pif_final needed
     Y3, T3, f3 = synth.generate_panel(2, 300, 3)
     r = de.estimate_batch_device_np(Y3, T3, 3, 1, 3, (12,), f3[:, 11:12], **kw, pass_pif=False)
@@ -414,7 +363,7 @@ def test_results_are_complete_once_the_callers_stream_is(hmclib):
     assert ref["buckets"] > 1                                               # (the bucket streams join the caller's stream)
     s = torch.cuda.Stream()
     g = de.estimate_batch_device_np(*args, **kw, stream=s, timed=False)     # the runner waits for s alone
-    assert_identical(g, ref, "caller's stream")
+    assert_same(g, ref, what="caller's stream")
 
 
 # ---- (c) the context's scratch arena across calls and streams ----

@@ -7,8 +7,8 @@ import os
 import numpy as np
 import pytest
 
-from hmc_jl_amd import synth
-from test_gpu_parity import check_against_oracle
+from hmc_jl_amd import _lib, synth
+from oracle_parity import assert_window_matches_oracle, check_against_oracle, check_signals_against_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -61,7 +61,6 @@ def test_random_signal_runs_against_oracle(hmclib, oracle, seed):
     """The same for the signal Monte-Carlo path (estimatesignals!, sigLen = 0): random signal tails, save ranges, noise
     levels, kappa and numbers of chained noise samples, K = 2..8 across the steps-per-thread variants of the register-resident
     kernel and, for K >= 5 and one case in seven with longer windows, the SIG form of the LDS-resident one."""
-    from test_gpu_parity import check_signals_against_oracle
     rng = np.random.default_rng(5000 + seed)
     K = int(rng.integers(2, 9))                          # K >= 5 (and longer K <= 4 windows): the SIG form of the LDS-resident kernel
     W = int(rng.integers(1, 4))
@@ -85,8 +84,6 @@ def test_random_signal_runs_against_oracle(hmclib, oracle, seed):
 def test_random_smoothing_runs_against_oracle(hmclib, oracle, seed):
     """extras.pi_smooth_mean / pi_filter_mean on random shapes, K = 2..8: the SMOOTH variants of the register-resident
     kernel, the smoothing variant of the LDS-resident one beyond their range, against the oracle's literal Pb recursion."""
-    from hmc_jl_amd import _lib
-    from test_gpu_parity import TOL, close
     rng = np.random.default_rng(9000 + seed)
     K = int(rng.integers(2, 9))
     W = int(rng.integers(1, 4))
@@ -98,8 +95,5 @@ def test_random_smoothing_runs_against_oracle(hmclib, oracle, seed):
     for w in range(W):
         T = int(Tw[w])
         o = oracle.estimate_window(Y[w, :T], K, burnin, nrun, (12,), fut[w, 11:12], window_id=w, want_smooth=True)
-        assert g["status"][w] == o["status"] == 0
-        assert np.array_equal(g["x_final"][w, :T], o["x_final"])
-        assert np.max(np.abs(g["pi_smooth_mean"][w, :T] - o["pi_smooth"].mean(axis=0))) < TOL
+        assert_window_matches_oracle(g, w, T, o, fields=("pi_smooth_mean", "mu", "pif_final"))
         assert np.max(np.abs(g["pi_filter_mean"][w, :T].sum(axis=1) - 1)) < 1e-12
-        assert close(g["mu"][w].T, o["mu"]) < TOL and close(g["pif_final"][w, :T], o["pif_final"]) < TOL

@@ -11,17 +11,13 @@ import numpy as np
 import pytest
 
 from hmc_jl_amd import _lib, synth
+from oracle_parity import assert_same, assert_window_matches_oracle, forced_flavour_call
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-9
 KEYS = ("mu", "sig2", "A", "pi_end", "fcast", "summary", "x_final", "status")
 LENGTHS = [769, 895, 896, 897, 1023, 1024]
 CASES = [(K, T) for K in (2, 3, 4) for T in LENGTHS]
 BURNIN, NRUN, HORIZONS = 2, 10, (1, 12)
-
-
-def close(g, o):
-    return float(np.max(np.abs(g - o) / (1.0 + np.abs(o)))) if g.size else 0.0
 
 
 _panels, _runs = {}, {}
@@ -36,11 +32,9 @@ def panel(K, T):
 
 def call(monkeypatch, flavour, K, T, burnin=BURNIN, nrun=NRUN, **kw):
     """One call on the (K, T) panel under the forced flavour, on the four-steps-per-thread kernel."""
-    monkeypatch.setenv("HMCG_FLAVOUR", flavour)
     Y, Tw, yreal, ids = panel(K, T)
-    g = _lib.estimate_batch_host(Y, Tw, K, burnin, nrun, HORIZONS, yreal, want_state=True, window_ids=ids, **kw)
+    g = forced_flavour_call(monkeypatch, flavour, Y, Tw, K, burnin, nrun, HORIZONS, yreal, window_ids=ids, **kw)
     assert g["steps_per_thread"] == 4 and g["threads_per_window"] == 256
-    assert g["helper_waves"] == (4 if flavour == "h" else 0)
     assert not (g["status"] & _lib.ST_SKIPPED).any()
     return g
 
@@ -52,25 +46,15 @@ def run(monkeypatch, flavour, K, T):
     return _runs[flavour, K, T]
 
 
-def same(h, p, keys=KEYS):
-    for k in keys:
-        assert np.array_equal(h[k], p[k]), k
-
-
-def against_oracle(oracle, g, Y, lens, K, burnin, nrun, yreal, ids):
+def against_oracle(oracle, g, Y, lens, K, burnin, nrun, yreal, ids, fields=("mu", "sig2", "A", "pi_end", "fcast", "summary"), **want):
     for w, T in enumerate(lens):
-        o = oracle.estimate_window(Y[w, :T], K, burnin, nrun, HORIZONS, yreal[w], window_id=int(ids[w]))
-        assert g["status"][w] == o["status"]
-        assert np.array_equal(g["x_final"][w, :T], o["x_final"]), "state path differs (window %d)" % w
-        assert close(g["mu"][w].T, o["mu"]) < TOL and close(g["sig2"][w].T, o["sig2"]) < TOL
-        assert close(np.transpose(g["A"][w], (2, 1, 0)), o["A"]) < TOL
-        assert close(g["pi_end"][w].T, o["pi_end"]) < TOL and close(g["fcast"][w].T, o["fcast"]) < TOL
-        assert close(g["summary"][w], o["summary"]) < TOL
+        o = oracle.estimate_window(Y[w, :T], K, burnin, nrun, HORIZONS, yreal[w], window_id=int(ids[w]), **want)
+        assert_window_matches_oracle(g, w, T, o, fields=fields, status0=False)
 
 
 @pytest.mark.parametrize("K,T", CASES, ids=["K%d-T%d" % c for c in CASES])
 def test_trip_edges_equal_plain_bit_for_bit(hmclib, monkeypatch, K, T):
-    same(run(monkeypatch, "h", K, T), run(monkeypatch, "p1", K, T))
+    assert_same(run(monkeypatch, "h", K, T), run(monkeypatch, "p1", K, T), KEYS, equal_nan=False)
 
 
 @pytest.mark.parametrize("K,T", CASES, ids=["K%d-T%d" % c for c in CASES])
@@ -85,7 +69,7 @@ def test_sweep_counts_at_which_a_stage_could_dangle(hmclib, oracle, monkeypatch,
     done; a one-sweep launch runs no stage at all, a two-sweep launch exactly one of each."""
     K, T = 3, 897
     h = call(monkeypatch, "h", K, T, burnin, nrun)
-    same(h, call(monkeypatch, "p1", K, T, burnin, nrun))
+    assert_same(h, call(monkeypatch, "p1", K, T, burnin, nrun), KEYS, equal_nan=False)
     Y, Tw, yreal, ids = panel(K, T)
     against_oracle(oracle, h, Y, [T, T], K, burnin, nrun, yreal, ids)
 
@@ -99,7 +83,7 @@ def test_resumed_chains_at_both_buffer_parities(hmclib, monkeypatch, parts):
     total = sum(parts)
     nrun = total - burnin
     one = call(monkeypatch, "h", K, T, burnin, nrun)
-    same(one, call(monkeypatch, "p1", K, T, burnin, nrun))
+    assert_same(one, call(monkeypatch, "p1", K, T, burnin, nrun), KEYS, equal_nan=False)
     g, base = None, 0
     for n in parts:
         last = base + n == total
@@ -120,13 +104,11 @@ def test_smoothing_instantiations(hmclib, oracle, monkeypatch, K):
     T, burnin, nrun = 897, 2, 10
     Y, Tw, yreal, ids = panel(K, T)
     out = {fl: call(monkeypatch, fl, K, T, burnin, nrun, want_smooth=True, want_filter_mean=True) for fl in ("h", "p1")}
-    same(out["h"], out["p1"], KEYS + ("pi_smooth_mean", "pi_filter_mean", "pif_final"))
+    assert_same(out["h"], out["p1"], KEYS + ("pi_smooth_mean", "pi_filter_mean", "pif_final"), equal_nan=False)
     g = out["h"]
-    against_oracle(oracle, g, Y, [T, T], K, burnin, nrun, yreal, ids)
+    against_oracle(oracle, g, Y, [T, T], K, burnin, nrun, yreal, ids, want_smooth=True,
+                   fields=("mu", "sig2", "A", "pi_end", "fcast", "summary", "pi_smooth_mean", "pif_final"))
     for w in range(2):
-        o = oracle.estimate_window(Y[w, :T], K, burnin, nrun, HORIZONS, yreal[w], window_id=int(ids[w]), want_smooth=True)
-        assert np.max(np.abs(g["pi_smooth_mean"][w, :T] - o["pi_smooth"].mean(axis=0))) < TOL
-        assert np.max(np.abs(g["pif_final"][w, :T] - o["pif_final"])) < TOL
         assert np.max(np.abs(g["pi_filter_mean"][w, :T].sum(axis=1) - 1)) < 1e-12
 
 
@@ -140,9 +122,8 @@ def test_short_window_beside_a_long_one(hmclib, oracle, monkeypatch, T):
     monkeypatch.setenv("HMCG_NO_BUCKETS", "1")
     out = {}
     for fl in ("h", "p1"):
-        monkeypatch.setenv("HMCG_FLAVOUR", fl)
-        out[fl] = g = _lib.estimate_batch_host(Y, Tw, K, BURNIN, NRUN, HORIZONS, yreal, want_state=True, window_ids=ids)
-        assert g["steps_per_thread"] == 4 and g["buckets"] == 1 and g["helper_waves"] == (4 if fl == "h" else 0)
+        out[fl] = g = forced_flavour_call(monkeypatch, fl, Y, Tw, K, BURNIN, NRUN, HORIZONS, yreal, window_ids=ids)
+        assert g["steps_per_thread"] == 4 and g["buckets"] == 1
         assert not (g["status"] & _lib.ST_SKIPPED).any()
-    same(out["h"], out["p1"])
+    assert_same(out["h"], out["p1"], KEYS, equal_nan=False)
     against_oracle(oracle, out["h"], Y, lens, K, BURNIN, NRUN, yreal, ids)

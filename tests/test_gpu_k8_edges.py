@@ -22,16 +22,12 @@ import numpy as np
 import pytest
 
 from hmc_jl_amd import _lib, synth
+from oracle_parity import assert_same, assert_window_matches_oracle
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-9
 K = 8
 EPS = float(np.finfo(np.float64).eps)
 LENS = (3000, 3001)
-
-
-def close(g, o):
-    return float(np.max(np.abs(g - o) / (1.0 + np.abs(o)))) if g.size else 0.0
 
 
 def regimes(T, seed, stay=0.97, sd=0.05, gap=1.0):
@@ -49,19 +45,15 @@ def run_both(oracle, Y, Tw, burnin, nrun, x_init=None):
     kw = dict(x_init=x_init) if x_init is not None else {}
     g = _lib.estimate_batch_host(Y, Tw, K, burnin, nrun, (12,), None, **kw)
     gs = _lib.estimate_batch_host(Y, Tw, K, burnin, nrun, (12,), None, want_state=True, **kw)
+    draws = ("mu", "sig2", "A", "pi_end", "fcast", "summary")
+    assert_same(g, gs, draws + ("status",))
     outs = []
     for w in range(Y.shape[0]):
         T = int(Tw[w])
         o = oracle.estimate_window(Y[w, :T], K, burnin, nrun, (12,), None, window_id=w,
                                    x_init=None if x_init is None else x_init[w, :T])
-        assert g["status"][w] == o["status"] == gs["status"][w], (w, g["status"][w], o["status"])
-        assert np.array_equal(gs["x_final"][w, :T], o["x_final"]), "state path differs in window %d" % w
-        assert close(g["mu"][w].T, o["mu"]) < TOL and close(g["sig2"][w].T, o["sig2"]) < TOL
-        assert close(np.transpose(g["A"][w], (2, 1, 0)), o["A"]) < TOL
-        assert close(g["pi_end"][w].T, o["pi_end"]) < TOL
-        assert close(gs["pif_final"][w, :T], o["pif_final"]) < TOL
-        for k in ("mu", "sig2", "A", "pi_end", "fcast", "summary"):
-            assert np.array_equal(g[k][w], gs[k][w], equal_nan=True), (k, w)
+        # the draws of the run without want_state (equal to the other's, above), the states and the last filter of the one with it
+        assert_window_matches_oracle(gs, w, T, o, fields=("mu", "sig2", "A", "pi_end", "pif_final"), status0=False)
         outs.append(o)
     return g, outs
 

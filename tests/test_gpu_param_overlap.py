@@ -12,21 +12,14 @@ import numpy as np
 import pytest
 
 from hmc_jl_amd import _lib, synth
+from kernel_tables import steps_per_thread
+from oracle_parity import assert_same, assert_window_matches_oracle, forced_flavour_call
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-9
 KEYS = ("mu", "sig2", "A", "pi_end", "fcast", "summary", "x_final", "status")
 LENGTHS = [2, 37, 63, 64, 65, 511, 1023, 2047]
 CASES = [(K, T) for K in (2, 3, 4) for T in LENGTHS]
 BURNIN, NRUN, HORIZONS = 2, 10, (1, 12)
-
-
-def steps_per_thread(T):
-    return 1 if T <= 256 else 2 if T <= 512 else 4 if T <= 1024 else 8
-
-
-def close(g, o):
-    return float(np.max(np.abs(g - o) / (1.0 + np.abs(o)))) if g.size else 0.0
 
 
 _panels, _runs = {}, {}
@@ -44,37 +37,30 @@ def run(monkeypatch, flavour, K, T, **kw):
     key = (flavour, K, T) if not kw else None
     if key in _runs:
         return _runs[key]
-    monkeypatch.setenv("HMCG_FLAVOUR", flavour)
     Y, Tw, yreal, ids = panel(K, T)
-    g = _lib.estimate_batch_host(Y, Tw, K, BURNIN, NRUN, HORIZONS, yreal, want_state=True, window_ids=ids, **kw)
-    assert g["steps_per_thread"] == steps_per_thread(T) and g["threads_per_window"] == 256
-    assert g["helper_waves"] == (4 if flavour == "h" else 0)
+    g = forced_flavour_call(monkeypatch, flavour, Y, Tw, K, BURNIN, NRUN, HORIZONS, yreal, window_ids=ids, **kw)
+    assert g["steps_per_thread"] == steps_per_thread(K, T) and g["threads_per_window"] == 256
     assert not (g["status"] & _lib.ST_SKIPPED).any()
     if key:
         _runs[key] = g
     return g
 
 
+def against_oracle(oracle, g, Y, lens, K, yreal, ids):
+    for w, T in enumerate(lens):
+        o = oracle.estimate_window(Y[w, :T], K, BURNIN, NRUN, HORIZONS, yreal[w], window_id=int(ids[w]))
+        assert_window_matches_oracle(g, w, T, o, fields=("mu", "sig2", "A", "pi_end", "fcast", "summary"), status0=False)
+
+
 @pytest.mark.parametrize("K,T", CASES, ids=["K%d-T%d" % c for c in CASES])
 def test_helper_flavour_equals_plain_bit_for_bit(hmclib, monkeypatch, K, T):
-    h = run(monkeypatch, "h", K, T)
-    p = run(monkeypatch, "p1", K, T)
-    for k in KEYS:
-        assert np.array_equal(h[k], p[k]), k
+    assert_same(run(monkeypatch, "h", K, T), run(monkeypatch, "p1", K, T), KEYS, equal_nan=False)
 
 
 @pytest.mark.parametrize("K,T", CASES, ids=["K%d-T%d" % c for c in CASES])
 def test_helper_flavour_against_oracle(hmclib, oracle, monkeypatch, K, T):
-    g = run(monkeypatch, "h", K, T)
     Y, Tw, yreal, ids = panel(K, T)
-    for w in range(2):
-        o = oracle.estimate_window(Y[w, :T], K, BURNIN, NRUN, HORIZONS, yreal[w], window_id=int(ids[w]))
-        assert g["status"][w] == o["status"]
-        assert np.array_equal(g["x_final"][w, :T], o["x_final"]), "state path differs (window %d)" % w
-        assert close(g["mu"][w].T, o["mu"]) < TOL and close(g["sig2"][w].T, o["sig2"]) < TOL
-        assert close(np.transpose(g["A"][w], (2, 1, 0)), o["A"]) < TOL
-        assert close(g["pi_end"][w].T, o["pi_end"]) < TOL and close(g["fcast"][w].T, o["fcast"]) < TOL
-        assert close(g["summary"][w], o["summary"]) < TOL
+    against_oracle(oracle, run(monkeypatch, "h", K, T), Y, [T, T], K, yreal, ids)
 
 
 @pytest.mark.parametrize("T", [37, 511, 1023])
@@ -106,12 +92,10 @@ def test_state_never_visited(hmclib, monkeypatch, K, T):
     monkeypatch.setenv("HMCG_NO_BUCKETS", "1")
     out = {}
     for fl in ("h", "p1"):
-        monkeypatch.setenv("HMCG_FLAVOUR", fl)
-        out[fl] = g = _lib.estimate_batch_host(Y, Tw, K, 4, 16, HORIZONS, yreal, want_state=True, window_ids=ids)
-        assert g["steps_per_thread"] == 4 and g["buckets"] == 1 and g["helper_waves"] == (4 if fl == "h" else 0)
+        out[fl] = g = forced_flavour_call(monkeypatch, fl, Y, Tw, K, 4, 16, HORIZONS, yreal, window_ids=ids)
+        assert g["steps_per_thread"] == 4 and g["buckets"] == 1
         assert not (g["status"] & _lib.ST_SKIPPED).any()
-    for k in KEYS:
-        assert np.array_equal(out["h"][k], out["p1"][k]), k
+    assert_same(out["h"], out["p1"], KEYS, equal_nan=False)
     assert np.isfinite(out["h"]["mu"]).all() and np.isfinite(out["h"]["A"]).all()
 
 
@@ -127,18 +111,8 @@ def test_short_windows_on_the_four_step_kernel(hmclib, oracle, monkeypatch, K):
     monkeypatch.setenv("HMCG_NO_BUCKETS", "1")
     out = {}
     for fl in ("h", "p1"):
-        monkeypatch.setenv("HMCG_FLAVOUR", fl)
-        out[fl] = g = _lib.estimate_batch_host(Y, Tw, K, BURNIN, NRUN, HORIZONS, yreal, want_state=True, window_ids=ids)
-        assert g["steps_per_thread"] == 4 and g["buckets"] == 1 and g["helper_waves"] == (4 if fl == "h" else 0)
+        out[fl] = g = forced_flavour_call(monkeypatch, fl, Y, Tw, K, BURNIN, NRUN, HORIZONS, yreal, window_ids=ids)
+        assert g["steps_per_thread"] == 4 and g["buckets"] == 1
         assert not (g["status"] & _lib.ST_SKIPPED).any()
-    for k in KEYS:
-        assert np.array_equal(out["h"][k], out["p1"][k]), k
-    g = out["h"]
-    for w, T in enumerate(lens):
-        o = oracle.estimate_window(Y[w, :T], K, BURNIN, NRUN, HORIZONS, yreal[w], window_id=int(ids[w]))
-        assert g["status"][w] == o["status"]
-        assert np.array_equal(g["x_final"][w, :T], o["x_final"]), "state path differs (T = %d)" % T
-        assert close(g["mu"][w].T, o["mu"]) < TOL and close(g["sig2"][w].T, o["sig2"]) < TOL
-        assert close(np.transpose(g["A"][w], (2, 1, 0)), o["A"]) < TOL
-        assert close(g["pi_end"][w].T, o["pi_end"]) < TOL and close(g["fcast"][w].T, o["fcast"]) < TOL
-        assert close(g["summary"][w], o["summary"]) < TOL
+    assert_same(out["h"], out["p1"], KEYS, equal_nan=False)
+    against_oracle(oracle, out["h"], Y, lens, K, yreal, ids)

@@ -34,9 +34,9 @@ import pytest
 import device_entry as de
 import sweep_identities as si
 from hmc_jl_amd import _lib
-from test_gpu_big_variants import NT, assert_ran_on_big, ladder_ceiling
-from test_gpu_device_entry import assert_device_equals_host
-from test_gpu_parity import TOL, close, close_nan
+from device_entry import assert_device_equals_host
+from kernel_tables import FLAVOUR_WAVES, NT, ladder_ceiling
+from oracle_parity import TOL, assert_ran_on_big, assert_window_matches_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -48,7 +48,7 @@ def assert_ran_as_planned(g, c, kw):
         assert g["threads_per_window"] == NT and g["steps_per_thread"] == c["L"], (g["threads_per_window"], g["steps_per_thread"], c["L"])
         assert g["buckets"] == 1 and not g["streaming"]
         # the SIG + SM rows are compiled in the plain flavour alone
-        assert (g["helper_waves"], g["occupancy"]) == (si.FLAVOUR_WAVES[c["flavour"]] if c["flavour"] else (0, 1)), (g["helper_waves"], g["occupancy"])
+        assert (g["helper_waves"], g["occupancy"]) == (FLAVOUR_WAVES[c["flavour"]] if c["flavour"] else (0, 1)), (g["helper_waves"], g["occupancy"])
     else:
         assert top > ladder_ceiling(c["K"], sig, True), c["id"]            # the production route, no HMCG_FORCE_BIG
         assert_ran_on_big(g, c["kernel"] == "stream", top, sig, True)
@@ -56,20 +56,10 @@ def assert_ran_as_planned(g, c, kw):
 
 def check_window_against_oracle(g, args, kw, w, o):
     """The suite's contract for window w: status equal, states exact, every float within TOL."""
-    T = int(args[1][w])
-    assert g["status"][w] == o["status"] == 0, (w, g["status"][w], o["status"])
-    assert np.array_equal(g["x_final"][w, :T], o["x_final"]), "state path differs in window %d" % w
-    got = dict(mu=g["mu"][w].T, sig2=g["sig2"][w].T, A=np.transpose(g["A"][w], (2, 1, 0)), pi_end=g["pi_end"][w].T, pif_final=g["pif_final"][w, :T],
-               pi_smooth_mean=g["pi_smooth_mean"][w, :T], pi_filter_mean=g["pi_filter_mean"][w, :T],
-               pi_smooth=np.transpose(g["pi_smooth_draws"][w, :, :T, :], (2, 1, 0)))
-    want = dict(o, pi_smooth_mean=o["pi_smooth"].mean(axis=0))
-    for k, v in got.items():
-        assert close(v, want[k]) < TOL, (w, k, close(v, want[k]))
-    assert close_nan(g["fcast"][w].T, o["fcast"]) < TOL, (w, "fcast")
-    assert close_nan(g["summary"][w], o["summary"]) < TOL, (w, "summary")
-    if "sig_range" in kw:
-        n = int(kw["sig_range"][w][1] - kw["sig_range"][w][0])
-        assert close(g["sigvals"][w][:, :n], o["sigvals"]) < TOL, (w, "sigvals")
+    fields = ("mu", "sig2", "A", "pi_end", "pif_final", "pi_smooth_mean", "pi_filter_mean", "pi_smooth_draws")
+    n = int(kw["sig_range"][w][1] - kw["sig_range"][w][0]) if "sig_range" in kw else None
+    assert_window_matches_oracle(g, w, int(args[1][w]), o, fields=fields + (("sigvals",) if n is not None else ()),
+                                 nan_fields=("fcast", "summary"), nsave=n)
 
 
 @pytest.mark.parametrize("c", si.CASES, ids=si.CASE_IDS)

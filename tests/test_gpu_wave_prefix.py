@@ -25,16 +25,17 @@ must not miss W_0.  Asserted: status 0, the state path equal to the oracle's, ev
 import numpy as np
 import pytest
 
-from hmc_jl_amd import _lib, synth
+from hmc_jl_amd import synth
+from kernel_tables import register_classes
+from oracle_parity import assert_batch_matches_oracle, assert_same, assert_window_matches_oracle, forced_flavour_call
 
 pytestmark = pytest.mark.gpu
-TOL = 1e-9
 BURNIN, NRUN, HORIZONS = 2, 6, (1, 12)
 FLOATS = ("mu", "sig2", "A", "pi_end", "fcast", "summary")
 KEYS = FLOATS + ("x_final", "status")
 FLAVOURS = ("h", "p1", "p2")
-# the steps-per-thread classes of the base path's 256-thread rows (csrc/variants_k2|k3|mid|k3_l16|k4.hip)
-CLASSES = {2: (1, 2, 3, 4, 8), 3: (1, 2, 3, 4, 6, 8, 12, 16), 4: (1, 2, 3, 4, 8)}
+# the steps-per-thread classes of the base path's 256-thread rows (csrc/variants_k2|k3|mid|k3_l16|k4.hip), from the parsed tables
+CLASSES = {K: tuple(register_classes(K, False, False)) for K in (2, 3, 4)}
 CASES = [(K, L) for K in (2, 3, 4) for L in CLASSES[K]]
 WIDE = [(128, 8), (512, 2)]                     # (threads per window, L): HMCG_V(3, 8, 128, ...) and HMCG_V(3, 2, 512, ...)
 
@@ -42,10 +43,6 @@ WIDE = [(128, 8), (512, 2)]                     # (threads per window, L): HMCG_
 def lengths(L, nw=4):
     edge = [64 * L * j for j in range(1, nw)]
     return [64 * L * nw, 64 * L * nw - 1] + edge + [e + 1 for e in edge] + [L + 1, 2]
-
-
-def close(g, o):
-    return float(np.max(np.abs(g - o) / (1.0 + np.abs(o)))) if g.size else 0.0
 
 
 _panels, _runs, _oracle = {}, {}, {}
@@ -64,15 +61,9 @@ def run(monkeypatch, flavour, K, L, nt=0, **kw):
     key = (flavour, K, L, nt) + tuple(sorted(kw))
     if key not in _runs:
         monkeypatch.setenv("HMCG_NO_BUCKETS", "1")
-        if flavour is None:
-            monkeypatch.delenv("HMCG_FLAVOUR", raising=False)
-        else:
-            monkeypatch.setenv("HMCG_FLAVOUR", flavour)
         Y, Tw, yreal = panel(K, L, nt // 64 if nt else 4)
-        g = _lib.estimate_batch_host(Y, Tw, K, BURNIN, NRUN, HORIZONS, yreal, want_state=True, threads_per_window=nt, **kw)
+        g = forced_flavour_call(monkeypatch, flavour, Y, Tw, K, BURNIN, NRUN, HORIZONS, yreal, threads_per_window=nt, **kw)
         assert g["steps_per_thread"] == L and g["threads_per_window"] == (nt or 256) and g["buckets"] == 1
-        if flavour is not None:
-            assert g["helper_waves"] == (4 if flavour == "h" else 0)
         _runs[key] = g
     return _runs[key]
 
@@ -86,39 +77,25 @@ def reference(oracle, K, L, nw=4):
     return _oracle[K, L, nw]
 
 
-def against_oracle(g, o):
-    assert (g["status"] == 0).all(), g["status"]
-    assert np.array_equal(g["x_final"], o["x_final"]), "state paths differ"
-    for k in FLOATS:
-        err = close(g[k], o[k])
-        print(k, err)
-        assert err < TOL, (k, err)
-
-
-def same(a, b, keys=KEYS):
-    for k in keys:
-        assert np.array_equal(a[k], b[k]), k
-
-
 @pytest.mark.parametrize("K,L", CASES, ids=["K%d-L%d" % c for c in CASES])
 def test_wave_edges_against_oracle(hmclib, oracle, monkeypatch, K, L):
     o = reference(oracle, K, L)
-    against_oracle(run(monkeypatch, "h", K, L), o)
+    assert_batch_matches_oracle(run(monkeypatch, "h", K, L), o, FLOATS)
 
 
 @pytest.mark.parametrize("K,L", CASES, ids=["K%d-L%d" % c for c in CASES])
 def test_wave_edges_flavours_equal_bit_for_bit(hmclib, oracle, monkeypatch, K, L):
     reference(oracle, K, L)
     h = run(monkeypatch, "h", K, L)
-    same(h, run(monkeypatch, "p1", K, L))
-    same(h, run(monkeypatch, "p2", K, L))
+    assert_same(h, run(monkeypatch, "p1", K, L), KEYS, equal_nan=False)
+    assert_same(h, run(monkeypatch, "p2", K, L), KEYS, equal_nan=False)
 
 
 @pytest.mark.parametrize("nt,L", WIDE, ids=["2-waves", "8-waves"])
 def test_two_and_eight_waves(hmclib, oracle, monkeypatch, nt, L):
     """No product at all (two waves: wave 1 takes the vector as it is) and the six-product chain (eight waves)."""
     o = reference(oracle, 3, L, nt // 64)
-    against_oracle(run(monkeypatch, None, 3, L, nt), o)
+    assert_batch_matches_oracle(run(monkeypatch, None, 3, L, nt), o, FLOATS)
 
 
 def test_smoothing_reads_the_later_totals_only(hmclib, oracle, monkeypatch):
@@ -130,12 +107,9 @@ def test_smoothing_reads_the_later_totals_only(hmclib, oracle, monkeypatch):
     smooth = [oracle.estimate_window(Y[w, :T], K, BURNIN, NRUN, HORIZONS, yreal[w], window_id=w, want_smooth=True) for w, T in enumerate(Tw)]
     assert all(o["status"] == 0 for o in smooth)
     out = {fl: run(monkeypatch, fl, K, L, want_smooth=True) for fl in FLAVOURS}
-    same(out["h"], out["p1"], KEYS + ("pi_smooth_mean",))
-    same(out["h"], out["p2"], KEYS + ("pi_smooth_mean",))
+    assert_same(out["h"], out["p1"], KEYS + ("pi_smooth_mean",), equal_nan=False)
+    assert_same(out["h"], out["p2"], KEYS + ("pi_smooth_mean",), equal_nan=False)
     g = out["h"]
-    against_oracle(g, ref)
+    assert_batch_matches_oracle(g, ref, FLOATS)
     for w, T in enumerate(Tw):
-        o = smooth[w]
-        err = close(g["pi_smooth_mean"][w, :T], o["pi_smooth"].mean(axis=0))
-        print("pi_smooth_mean", w, err)
-        assert err < TOL, (w, err)
+        assert_window_matches_oracle(g, w, T, smooth[w], fields=("pi_smooth_mean",))

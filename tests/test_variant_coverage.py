@@ -16,6 +16,7 @@ import shutil
 import subprocess
 
 import device_entry
+import kernel_tables as kt
 import sweep_identities
 import test_gpu_big_variants as big
 import test_gpu_device_entry as dev
@@ -24,8 +25,7 @@ import test_gpu_variants as reg
 from hmc_jl_amd import _lib
 from hmcg_header import extras_pointer_members
 
-FLAVOUR = {"p1": (0, 1), "p2": (0, 2), "h": (4, 2)}                      # (NH, OCC) of the three HMCG_V3 expansions
-PATH = {"base": (False, False), "sig": (True, False), "smooth": (False, True)}
+FLAVOUR, PATH = kt.FLAVOUR_WAVES, kt.PATH                               # (NH, OCC) of the three HMCG_V3 expansions; (sig, smooth) of a path
 
 
 def fmt_reg(r):
@@ -69,7 +69,7 @@ def library_kernels():
 def test_parsed_tables_are_the_kernels_of_the_built_library():
     """129 register-resident and 56 LDS-resident instantiations today; whatever the numbers, the source parse and the
     library's symbols name the same kernels, none twice."""
-    rows, bigs = big.register_rows(), big.big_instantiations()
+    rows, bigs = kt.register_rows(), kt.big_instantiations()
     assert len(set(rows)) == len(rows) and len(set(bigs)) == len(bigs)
     lib_rows, lib_bigs = library_kernels()
     assert len(lib_rows) + len(lib_bigs) == len(rows) + len(bigs), (len(lib_rows), len(lib_bigs), len(rows), len(bigs))
@@ -85,7 +85,7 @@ def covered_register_rows():
         named[(K, L, 256) + PATH[path] + FLAVOUR[fl]] = "test_every_variant_against_oracle[K%d-L%d-%s-%s]" % (K, L, path, fl)
     for (K, L) in cases_of(reg.test_smoothed_and_filtered_means_on_the_signal_path):
         named[(K, L, 256, True, True, 0, 1)] = "test_smoothed_and_filtered_means_on_the_signal_path[K%d-L%d]" % (K, L)
-    rows = big.register_rows()
+    rows = kt.register_rows()
     for (K, L, nt) in parity.THREADS_PER_WINDOW_CASES:
         # a thread count of its own: the one base-path row of that (K, L, NT) is what threads_per_window=NT selects
         mine = [r for r in rows if r[:5] == (K, L, nt, False, False)]
@@ -95,7 +95,7 @@ def covered_register_rows():
 
 
 def test_every_register_resident_instantiation_has_an_oracle_case():
-    rows, named = set(big.register_rows()), covered_register_rows()
+    rows, named = set(kt.register_rows()), covered_register_rows()
     missing = sorted(rows - set(named))
     assert not missing, "compiled, but no oracle-parity case names it: " + "; ".join(fmt_reg(r) for r in missing)
     extra = sorted(set(named) - rows)
@@ -103,7 +103,7 @@ def test_every_register_resident_instantiation_has_an_oracle_case():
 
 
 def test_every_lds_resident_instantiation_has_an_oracle_case():
-    bigs = set(big.big_instantiations())
+    bigs = set(kt.big_instantiations())
     cases = cases_of(big.test_every_big_instantiation_against_oracle)
     assert len(set(cases)) == len(cases)
     missing = sorted(bigs - set(cases))
@@ -112,9 +112,9 @@ def test_every_lds_resident_instantiation_has_an_oracle_case():
     assert not extra, "a case names a kernel that is not compiled: " + "; ".join(fmt_big(b) for b in extra)
     # the coverage case must take the production route to its kernel: beyond the ladder (LDS forms) / beyond the LDS (streaming)
     for (sig, sm, st, K) in cases:
-        top = big.coverage_lengths(sig, sm, st, K)[0]
-        assert top > big.ladder_ceiling(K, sig, sm) and top % 256 != 0, fmt_big((sig, sm, st, K))
-        assert (big.dyn_bytes((top + 255) // 256) > big.LDS_LIMIT) == st, fmt_big((sig, sm, st, K))
+        top = kt.coverage_lengths(sig, sm, st, K)[0]
+        assert top > kt.ladder_ceiling(K, sig, sm) and top % 256 != 0, fmt_big((sig, sm, st, K))
+        assert (kt.dyn_bytes((top + 255) // 256) > kt.LDS_LIMIT) == st, fmt_big((sig, sm, st, K))
 
 
 def test_depth_cases_stay_beyond_the_ladder():
@@ -122,9 +122,9 @@ def test_depth_cases_stay_beyond_the_ladder():
     every K has its deepest ones."""
     cases = cases_of(big.test_base_form_depth_edges)
     for (K, L) in cases:
-        assert 256 * L - 1 > big.ladder_ceiling(K, False, False), (K, L)
-    for K in big.big_form_ks():
-        assert {L for (k, L) in cases if k == K} >= {L for L in (8, 9, 16, 17) if 256 * L - 1 > big.ladder_ceiling(K, False, False)}, K
+        assert 256 * L - 1 > kt.ladder_ceiling(K, False, False), (K, L)
+    for K in kt.big_form_ks():
+        assert {L for (k, L) in cases if k == K} >= {L for L in (8, 9, 16, 17) if 256 * L - 1 > kt.ladder_ceiling(K, False, False)}, K
         assert (K, 17) in cases
 
 
@@ -171,10 +171,10 @@ def test_device_entry_parity_cases_cover_every_family_and_path():
         sig, smooth = c["path"] in ("sig", "tail"), c["path"] == "smooth"
         top = max(c["lens"])
         if c["kernel"] == "register":
-            assert top <= big.ladder_ceiling(c["K"], sig, smooth), c["id"]
+            assert top <= kt.ladder_ceiling(c["K"], sig, smooth), c["id"]
         else:                                                  # the production route to the LDS-resident kernel and its streaming form
-            assert top > big.ladder_ceiling(c["K"], sig, smooth), c["id"]
-            assert (big.dyn_bytes((top + 255) // 256) > big.LDS_LIMIT) == (c["kernel"] == "stream"), c["id"]
+            assert top > kt.ladder_ceiling(c["K"], sig, smooth), c["id"]
+            assert (kt.dyn_bytes((top + 255) // 256) > kt.LDS_LIMIT) == (c["kernel"] == "stream"), c["id"]
 
 
 def test_split_chain_table_covers_every_kernel_form():
@@ -188,9 +188,9 @@ def test_split_chain_table_covers_every_kernel_form():
         sig, smooth = "sig_range" in kw, "want_smooth" in kw
         assert (c["form"] in ("sig", "sig+sm")) == sig and (c["form"] in ("sm", "sig+sm")) == smooth, c["id"]
         if c["kernel"] == "register":
-            assert max(c["lens"]) <= big.ladder_ceiling(c["K"], sig, smooth), c["id"]
+            assert max(c["lens"]) <= kt.ladder_ceiling(c["K"], sig, smooth), c["id"]
         else:
-            assert max(c["lens"]) > big.ladder_ceiling(c["K"], sig, smooth) or ("HMCG_FORCE_BIG", "1") in c["env"], c["id"]
+            assert max(c["lens"]) > kt.ladder_ceiling(c["K"], sig, smooth) or ("HMCG_FORCE_BIG", "1") in c["env"], c["id"]
         burnin, nrun = c["sweeps"]
         per = burnin + nrun
         # the cuts the issue of this table asks for: inside burn-in, exactly at burnin, after a kept draw, a three-piece run;
@@ -211,7 +211,7 @@ def test_sweep_identity_cases_cover_every_smoothing_form():
     """A SM or SIG + SM row, or a smoothing form of the LDS-resident kernel, that is added to the variant tables without a case in
     sweep_identities.CASES fails here; so does a case that names a row which is not compiled, or whose windows the production
     dispatch would hand to another kernel."""
-    rows, cases = big.register_rows(), sweep_identities.CASES
+    rows, cases = kt.register_rows(), sweep_identities.CASES
     reg = [c for c in cases if c["kernel"] == "register"]
     # every SM register row's (K, L); the flavours a case forces are compiled
     sm_rows = {(K, L) for (K, L, nt, sig, sm, _, _) in rows if (nt, sig, sm) == (256, False, True)}
@@ -237,11 +237,11 @@ def test_sweep_identity_cases_cover_every_smoothing_form():
     for c in cases:
         if c["kernel"] != "register":
             sig, stream, top = c["path"] != "smooth", c["kernel"] == "stream", max(c["lens"])
-            assert (sig, True, stream, c["K"]) in big.big_instantiations(), c["id"]
-            assert top > big.ladder_ceiling(c["K"], sig, True) and top % 256 != 0, c["id"]
-            assert (big.dyn_bytes((top + 255) // 256) > big.LDS_LIMIT) == stream, c["id"]
+            assert (sig, True, stream, c["K"]) in kt.big_instantiations(), c["id"]
+            assert top > kt.ladder_ceiling(c["K"], sig, True) and top % 256 != 0, c["id"]
+            assert (kt.dyn_bytes((top + 255) // 256) > kt.LDS_LIMIT) == stream, c["id"]
             forms.setdefault((sig, True, stream), c["id"])
-    smoothing_forms = {f for f in big.big_forms().values() if f[1]}
+    smoothing_forms = {f for f in kt.big_forms().values() if f[1]}
     assert len(smoothing_forms) == 4 and smoothing_forms <= set(forms), sorted(smoothing_forms - set(forms))
     # the tail path (end_pos with smoothing outputs) on a register form, an LDS form and a streaming form
     assert {c["kernel"] for c in cases if c["path"] == "tail+smooth"} == {"register", "lds", "stream"}
