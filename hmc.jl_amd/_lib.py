@@ -26,12 +26,18 @@ HMCG_MAXTAIL = 256
 EXPORTS = ("hmcg_version", "hmcg_device_count", "hmcg_last_error", "hmcg_shutdown",
            "hmcg_estimate_batch", "hmcg_estimate_batch_device", "hmcg_estimate_batch_multi",
            "hmcg_save_results_csv", "hmcg_write_table_csv", "hmcg_format_float",
-           "hmcg_predictive_cdf", "hmcg_predictive_cdf_device")
+           "hmcg_predictive_cdf", "hmcg_predictive_cdf_device", "hmcg_bias_moments", "hmcg_bias_moments_device")
 HMCG_MAXDEV = 16
 PRED_ROUND5 = 1
 HMCG_MAXGRID = 4096
 HMCG_PRED_MAXH = 1024           # largest horizon of the predictive CDFs
 PRED_SLAB = 1024                # draws per reduction slab (csrc/predictive_plan.hpp): the host entry uploads whole slabs
+BIAS_ROUND5 = 1
+
+
+def bias_stride(K):
+    """HMCG_BIAS_STRIDE(K): doubles per window of the bias-moment output (uncbias, totalbias, mean[2K], cov[2K][2K])."""
+    return 2 + 2 * K + 4 * K * K
 
 
 class HmcgError(RuntimeError):
@@ -68,6 +74,12 @@ class Predictive(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("W", C.c_int32), ("K", C.c_int32), ("device", C.c_int32),
                 ("nd", C.c_int64), ("nd_ld", C.c_int64), ("G", C.c_int32), ("n_h", C.c_int32),
                 ("horizons", C.c_int32 * HMCG_MAXH), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Bias(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("W", C.c_int32), ("K", C.c_int32), ("device", C.c_int32),
+                ("nd", C.c_int64), ("nd_ld", C.c_int64), ("horizon", C.c_int32), ("H", C.c_int32),
+                ("flags", C.c_int32), ("reserved", C.c_int32)]
 
 
 _LIB = None
@@ -130,6 +142,8 @@ def load():
         L.hmcg_format_float.restype = C.c_int
         L.hmcg_predictive_cdf.restype = C.c_int
         L.hmcg_predictive_cdf_device.restype = C.c_int
+        L.hmcg_bias_moments.restype = C.c_int
+        L.hmcg_bias_moments_device.restype = C.c_int
         _LIB = L
     return _LIB
 
@@ -423,6 +437,67 @@ def predictive_cdf_device(pred, dmu, dsig2, dpi_end, dA, dgrid, dcdf, stream=Non
 
     _check(load().hmcg_predictive_cdf_device(C.byref(pred), vp(dmu), vp(dsig2), vp(dpi_end), vp(dA), vp(dgrid), vp(dcdf),
                                              vp(stream), C.byref(tm) if timed else None))
+    return tm
+
+
+def make_bias(W, K, nd, nd_ld, horizon=12, H=0, device=0, round5=True):
+    """hmcg_bias of a call; every rule is the library's (HMCG_E_BADARG).  H: fcast has 2H columns per window (0 without fcast)."""
+    p = Bias()
+    p.struct_size = C.sizeof(Bias)
+    p.W, p.K, p.device, p.nd, p.nd_ld, p.horizon, p.H = int(W), int(K), int(device), int(nd), int(nd_ld), int(horizon), int(H)
+    p.flags = BIAS_ROUND5 if round5 else 0
+    return p
+
+
+def unpack_bias(out, K):
+    """The (W, HMCG_BIAS_STRIDE(K)) output block as a dict: uncerbias (W,), totalbias (W,), mean (W, 2K) in the order
+    futstate | means, cov (W, 2K, 2K) in the same order."""
+    out = np.asarray(out)
+    W = out.shape[0]
+    return {"uncerbias": out[:, 0].copy(), "totalbias": out[:, 1].copy(), "mean": out[:, 2:2 + 2 * K].copy(),
+            "cov": out[:, 2 + 2 * K:].reshape(W, 2 * K, 2 * K).copy()}
+
+
+def bias_moments_host(mu, pi_end, A, fcast=None, horizon=12, device=0, round5=True, timing=None):
+    """hmcg_bias_moments over host (numpy) draw arrays in the C-ABI layouts -- mu/pi_end (W, K, nd), A (W, K, K, nd) with
+    A[w, j, i, d] = draw d of A[i, j] (None when horizon is 0), fcast (W, 2H, nd) or None -- as estimate_batch_host returns them.
+    Returns the (W, 2 + 2K + 4K^2) block (unpack_bias names its parts): per window uncbias = nab cov nab' with upstream's
+    column orders (bias_calcs.jl:49-51), totalbias = the mean of fcast[:, 1] (NaN without fcast), the mean and the covariance
+    (divisor nd - 1) of [pi_end A^horizon | mu] over the draws.  round5 (default): every input is first rounded to 5 digits,
+    as the cells of the per-draw CSV files are.  timing: a Timing to fill."""
+    mu = np.ascontiguousarray(mu, dtype=np.float64)
+    W, K, nd = mu.shape
+    pi_end = np.ascontiguousarray(pi_end, dtype=np.float64)
+    if pi_end.shape != mu.shape:
+        raise ValueError("mu and pi_end must share the shape (W, K, nd)")
+    if A is not None:
+        A = np.ascontiguousarray(A, dtype=np.float64)
+        if A.shape != (W, K, K, nd):
+            raise ValueError("A must have the shape (W, K, K, nd)")
+    H = 0
+    if fcast is not None:
+        fcast = np.ascontiguousarray(fcast, dtype=np.float64)
+        if fcast.ndim != 3 or fcast.shape[0] != W or fcast.shape[2] != nd or fcast.shape[1] % 2:
+            raise ValueError("fcast must have the shape (W, 2H, nd)")
+        H = fcast.shape[1] // 2
+    p = make_bias(W, K, nd, nd, horizon, H, device, round5)
+    out = np.zeros((W, bias_stride(K)))
+    _check(load().hmcg_bias_moments(C.byref(p), _np_ptr(mu), _np_ptr(pi_end), _np_ptr(A), _np_ptr(fcast), _np_ptr(out),
+                                    C.byref(timing) if timing is not None else None))
+    return out
+
+
+def bias_moments_device(bias, dmu, dpi_end, dA, dfcast, dout, stream=None, timed=False):
+    """hmcg_bias_moments_device over raw device pointers (ints, e.g. torch tensor.data_ptr(); dA 0 / None when the horizon is 0,
+    dfcast 0 / None for no totalbias); bias: make_bias(...).  Enqueued on `stream` (None: the library's own).  Returns the
+    Timing struct when timed (the call then waits for completion), else None."""
+    tm = Timing() if timed else None
+
+    def vp(x):
+        return None if not x else C.c_void_p(int(x))
+
+    _check(load().hmcg_bias_moments_device(C.byref(bias), vp(dmu), vp(dpi_end), vp(dA), vp(dfcast), vp(dout), vp(stream),
+                                           C.byref(tm) if timed else None))
     return tm
 
 

@@ -33,6 +33,7 @@
 #include "moments.hpp"
 #include "plan.hpp"
 #include "predictive.hpp"
+#include "bias.hpp"
 
 namespace {
 
@@ -117,6 +118,7 @@ struct DeviceCtx {
     Arena scr;                     // device entry: the LDS-resident kernel's pdf scratch
     Arena ord;                     // device entry: the bucketed dispatch's window lists (bucket_lists_kernel)
     Arena pred;                    // device entry of the predictive CDFs: the slab sums
+    Arena bias;                    // device entry of the uncertainty-bias moments: the slab sums and pivots
     hmcg_hostutil::ScatterPool pool;              // host entries: helpers for the scatter into the caller's arrays
 };
 DeviceCtx g_ctx[HMCG_MAXDEV];
@@ -214,6 +216,7 @@ void destroy_context(DeviceCtx& c)
     c.scr.release();
     c.ord.release();
     c.pred.release();
+    c.bias.release();
     c.pool.stop();
     c.stream = c.copy = nullptr;
     c.ready = false;
@@ -1080,6 +1083,130 @@ int predictive_host(DeviceCtx& c, const hmcg_predictive* p, const double* mu, co
     return 0;
 }
 
+// ---- uncertainty-bias moments of the draws (bias.hip; argument rules: bias_plan.hpp; slab / chunk cut: predictive_plan.hpp) ------
+
+void fill_bias_timing(hmcg_timing* t, const hmcg_bias* p, const DeviceCtx& c, double kernel_ms, int launches, double call_ms)
+{
+    memset(t, 0, sizeof *t);
+    t->kernel_ms = kernel_ms; t->launches = launches; t->call_ms = call_ms;
+    t->device = c.device; t->windows = p->W; t->buckets = 1; t->threads_per_window = 256;
+}
+
+// Caller holds c.mu and has made c.device current.  The slab sums live in a context-owned arena (as those of the predictive CDFs do).
+int bias_device(DeviceCtx& c, const hmcg_bias* p, const double* dmu, const double* dpi_end, const double* dA, const double* dfcast,
+                double* dout, hipStream_t stream, hmcg_timing* timing)
+{
+    int rc = grow_shared(c, c.bias, sizeof(double) * bias_part_doubles(p->W, p->nd, p->K));
+    if (rc) return rc;
+    HIP_TRY(hipStreamWaitEvent(stream, c.ev_scr, 0));
+    if (timing) HIP_TRY(hipEventRecord(c.ev0, stream));
+    hmcg_host::BiasArgs a{};
+    a.W = p->W; a.K = p->K; a.horizon = p->horizon; a.round5 = (p->flags & HMCG_BIAS_ROUND5) != 0;
+    a.mu = dmu; a.pi_end = dpi_end; a.A = dA;
+    a.fc = dfcast ? dfcast + p->nd_ld : nullptr;             // column 1: forecast_error of the first horizon
+    a.fc_wstride = 2LL * p->H * p->nd_ld;
+    a.part = reinterpret_cast<double*>(c.bias.base);
+    a.nd = p->nd; a.nd_ld = p->nd_ld; a.slab0 = 0; a.nslab_total = pred_slabs(p->nd);
+    HIP_TRY(launch_bias(a, stream));
+    HIP_TRY(launch_bias_finalize(a.part, dout, p->W, p->K, p->nd, dfcast != nullptr, stream));
+    HIP_TRY(hipEventRecord(c.ev_scr, stream));
+    if (timing) {
+        HIP_TRY(hipEventRecord(c.ev1, stream));
+        HIP_TRY(hipEventSynchronize(c.ev1));
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, c.ev0, c.ev1));
+        fill_bias_timing(timing, p, c, ms, 2, 0.0);
+    }
+    return 0;
+}
+
+// Host entry on one device, as predictive_host: whole-slab chunks packed window by window, column by column into pinned staging
+// (mu | pi_end | A | forecast error, leading dimension = the chunk's draws), RING buffers deep, the copy of chunk c + 1 beside the
+// kernel of chunk c; every chunk files its slabs' sums in the same table (the first one the pivots too); one finalize at the end.
+int bias_host(DeviceCtx& c, const hmcg_bias* p, const double* mu, const double* pi_end, const double* A, const double* fcast, double* out,
+              hmcg_timing* timing)
+{
+    const auto t_call = std::chrono::steady_clock::now();
+    const int K = p->K, W = p->W;
+    const bool with_A = p->horizon > 0, with_fc = fcast != nullptr;
+    const int ncol = bias_columns(*p, with_fc);
+    long long cap = 0;
+    if (const char* cenv = diag_env("HMCG_CHUNK_DRAWS")) cap = atoll(cenv);
+    const long long cdraws = pred_chunk_draws(p->nd, W, ncol, cap);
+    const std::vector<PredChunk> chunks = pred_chunks(p->nd, cdraws);
+    const size_t nout = (size_t)W * (size_t)HMCG_BIAS_STRIDE(K);
+    auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
+    const size_t b_chunk = up(sizeof(double) * (size_t)W * (size_t)ncol * (size_t)cdraws);
+    const size_t b_out = up(sizeof(double) * nout);
+    const size_t b_part = up(sizeof(double) * bias_part_doubles(W, p->nd, K));
+    const int nbuf = (int)std::min<size_t>(RING, chunks.size());
+    if (c.dev.ensure(b_out + b_part + b_chunk * (size_t)nbuf) || c.pin.ensure(b_out + b_chunk * (size_t)nbuf)) {
+        set_err("workspace allocation failed (%zu B device, %zu B pinned)", b_out + b_part + b_chunk * (size_t)nbuf,
+                b_out + b_chunk * (size_t)nbuf);
+        return HMCG_E_NOMEM;
+    }
+    double* dout = reinterpret_cast<double*>(c.dev.base);
+    double* dpart = reinterpret_cast<double*>(c.dev.base + b_out);
+    char* dchunk = c.dev.base + b_out + b_part;
+    double* pout = reinterpret_cast<double*>(c.pin.base);
+    char* pchunk = c.pin.base + b_out;
+
+    struct Events {
+        std::vector<hipEvent_t> ev;
+        ~Events() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+    } tev;                                       // two per chunk, around its kernel (created only when timing is asked for)
+    if (timing) {
+        tev.ev.assign(2 * chunks.size(), nullptr);
+        for (hipEvent_t& e : tev.ev) HIP_TRY(hipEventCreate(&e));
+    }
+    hmcg_host::BiasArgs a{};
+    a.W = W; a.K = K; a.horizon = p->horizon; a.round5 = (p->flags & HMCG_BIAS_ROUND5) != 0;
+    a.part = dpart; a.nslab_total = pred_slabs(p->nd);
+    for (size_t ci = 0; ci < chunks.size(); ++ci) {
+        const PredChunk& ch = chunks[ci];
+        const int b = (int)(ci % (size_t)nbuf);
+        if (ci >= (size_t)nbuf) HIP_TRY(hipEventSynchronize(c.evk[b]));       // the kernel that read this buffer pair is done
+        double* pb = reinterpret_cast<double*>(pchunk + b_chunk * (size_t)b);
+        double* db = reinterpret_cast<double*>(dchunk + b_chunk * (size_t)b);
+        // packed chunk: mu | pi_end | A | forecast error, each [W][columns][ch.n]
+        const size_t n = (size_t)ch.n, o_pi = (size_t)W * K * n, o_A = 2 * o_pi, o_fc = o_A + (with_A ? (size_t)W * K * K * n : 0);
+        auto pack = [&](const double* src, size_t cols, double* dst) {
+            for (size_t q = 0; q < (size_t)W * cols; ++q) memcpy(dst + q * n, src + q * (size_t)p->nd_ld + (size_t)ch.d0, sizeof(double) * n);
+        };
+        pack(mu, (size_t)K, pb);
+        pack(pi_end, (size_t)K, pb + o_pi);
+        if (with_A) pack(A, (size_t)K * K, pb + o_A);
+        if (with_fc)
+            for (size_t w = 0; w < (size_t)W; ++w)
+                memcpy(pb + o_fc + w * n, fcast + (w * 2 * (size_t)p->H + 1) * (size_t)p->nd_ld + (size_t)ch.d0, sizeof(double) * n);
+        HIP_TRY(hipMemcpyAsync(db, pb, sizeof(double) * (size_t)W * (size_t)ncol * n, hipMemcpyHostToDevice, c.copy));
+        HIP_TRY(hipEventRecord(c.evc[b], c.copy));
+        HIP_TRY(hipStreamWaitEvent(c.stream, c.evc[b], 0));
+        a.mu = db; a.pi_end = db + o_pi; a.A = with_A ? db + o_A : nullptr;
+        a.fc = with_fc ? db + o_fc : nullptr; a.fc_wstride = ch.n;
+        a.nd = ch.n; a.nd_ld = ch.n; a.slab0 = ch.d0 / PRED_SLAB;
+        if (timing) HIP_TRY(hipEventRecord(tev.ev[2 * ci], c.stream));
+        HIP_TRY(launch_bias(a, c.stream));
+        if (timing) HIP_TRY(hipEventRecord(tev.ev[2 * ci + 1], c.stream));
+        HIP_TRY(hipEventRecord(c.evk[b], c.stream));
+    }
+    HIP_TRY(launch_bias_finalize(dpart, dout, W, K, p->nd, with_fc, c.stream));
+    HIP_TRY(hipMemcpyAsync(pout, dout, sizeof(double) * nout, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    memcpy(out, pout, sizeof(double) * nout);
+    if (timing) {
+        double kernel_ms = 0.0;
+        for (size_t ci = 0; ci < chunks.size(); ++ci) {
+            float ms = 0.f;
+            HIP_TRY(hipEventElapsedTime(&ms, tev.ev[2 * ci], tev.ev[2 * ci + 1]));
+            kernel_ms += ms;
+        }
+        const double call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+        fill_bias_timing(timing, p, c, kernel_ms, (int)chunks.size() + 1, call_ms);
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1215,6 +1342,36 @@ int hmcg_predictive_cdf(const hmcg_predictive* p, const double* mu, const double
     std::lock_guard<std::mutex> lk(c->mu);
     HIP_TRY(hipSetDevice(c->phys));
     return predictive_host(*c, p, mu, sig2, pi_end, A, grid, cdf, timing);
+}
+
+int hmcg_bias_moments_device(const hmcg_bias* p, const double* dmu, const double* dpi_end, const double* dA, const double* dfcast,
+                             double* dout, void* stream, hmcg_timing* timing)
+{
+    g_err[0] = 0;
+    char msg[160];
+    int rc = check_bias(p, dmu, dpi_end, dA, dfcast, dout, msg, sizeof msg);
+    if (rc) { set_err("%s", msg); return rc; }
+    DeviceCtx* c = nullptr;
+    rc = get_context(p->device, &c);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->phys));
+    return bias_device(*c, p, dmu, dpi_end, dA, dfcast, dout, stream ? (hipStream_t)stream : c->stream, timing);
+}
+
+int hmcg_bias_moments(const hmcg_bias* p, const double* mu, const double* pi_end, const double* A, const double* fcast, double* out,
+                      hmcg_timing* timing)
+{
+    g_err[0] = 0;
+    char msg[160];
+    int rc = check_bias(p, mu, pi_end, A, fcast, out, msg, sizeof msg);
+    if (rc) { set_err("%s", msg); return rc; }
+    DeviceCtx* c = nullptr;
+    rc = get_context(p->device, &c);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->phys));
+    return bias_host(*c, p, mu, pi_end, A, fcast, out, timing);
 }
 
 }  // extern "C"

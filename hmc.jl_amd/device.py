@@ -98,6 +98,23 @@ class DevicePanel:
             self.last_timing = tm
         return cdf
 
+    def bias_moments(self, horizon=12, timed=False, round5=True):
+        """Uncertainty-bias moments from the panel's own HBM draws (hmcg_bias_moments_device; bias_calcs.jl:40-53): a
+        (W, 2 + 2K + 4K^2) tensor, per window uncbias, totalbias (NaN for a panel without horizons), the mean and the covariance
+        of [pi_end A^horizon | mu] over the kept draws (_lib.unpack_bias names the parts of its numpy copy).  Enqueued on the
+        library stream behind `run`; with timed=True the call waits and last_timing holds the HIP-event time, otherwise call
+        sync() before reading the tensor."""
+        if self.mu is None:
+            raise _lib.HmcgError("bias_moments needs the draws in HBM: the panel was built with keep_draws=False")
+        H = len(self.horizons)
+        out = self.torch.empty((self.W, _lib.bias_stride(self.K)), dtype=self.torch.float64, device=self.dev)
+        bias = _lib.make_bias(self.W, self.K, self.nrun, self.nrun, horizon, H, self.device_index, round5)
+        tm = _lib.bias_moments_device(bias, self.mu.data_ptr(), self.pi_end.data_ptr(), self.A.data_ptr() if int(horizon) > 0 else 0,
+                                      self.fcast.data_ptr() if H > 0 else 0, out.data_ptr(), None, timed)
+        if timed:
+            self.last_timing = tm
+        return out
+
     def sync(self):
         """Wait for the library stream (untimed runs are asynchronous)."""
         self.torch.cuda.synchronize(self.dev)

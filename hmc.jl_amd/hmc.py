@@ -14,6 +14,7 @@ ABI.  Names, argument meaning and result layout follow the reference:
     runaggregate layout src/Hmc.jl:1025-1078 (`*_summary.csv`)
     calccorr            src/Hmc.jl:1094-1163 (correlations.xlsx; matrices from the files or from the device)
     calccdfs            code/hassan_cdfs/calc_cdfs.jl:31-42 (predictive CDFs; from the files or from the device)
+    calcbias            code/hassan_cdfs/bias_calcs.jl:40-53 (uncerbias / totalbias; from the files or from the device)
 
 New (the reference batches by launching one SLURM task per window,
 slurmscripts/base_estimation.sh:5): `estimatewindows`, one call for many windows.
@@ -340,6 +341,14 @@ def estimatesignalswindows(opts, device=0, window_ids=None, keep_draws=True, sum
     return (out, extra) if summaries else out
 
 
+class BiasMoments:
+    """bias_calcs.jl's numbers per window: uncerbias (W,), totalbias (W,), and the moments behind them, mean (W, 2K) and
+    cov (W, 2K, 2K) of [pi_end A^horizon | mu] over the draws, both in the order futstate | means."""
+
+    def __init__(self, horizon, uncerbias, totalbias, mean, cov):
+        self.horizon, self.uncerbias, self.totalbias, self.mean, self.cov = int(horizon), uncerbias, totalbias, mean, cov
+
+
 class BatchResult:
     """Result of estimatewindows: per-window posterior summaries (+ optional draws)."""
 
@@ -352,6 +361,7 @@ class BatchResult:
         self.cdf = res.get("cdf")              # (W, n_h, G) with cdf_grid: calc_cdfs.jl's expectationsbar per window and horizon
         self.cdf_grid = res.get("cdf_grid")
         self.cdf_horizons = res.get("cdf_horizons")
+        self.bias = res.get("bias")            # with bias_horizon: BiasMoments (uncerbias, totalbias, mean, cov) per window
         self._res = res if keep_draws else None
 
     def samples(self, w):
@@ -362,7 +372,7 @@ class BatchResult:
 
 
 def estimatewindows(rawdata, dates, endIndices, startIndex=1, keep_draws=False, device=0, window_ids=None, corr=False,
-                    cdf_grid=None, cdf_horizons=(0,), **kwargs):
+                    cdf_grid=None, cdf_horizons=(0,), bias_horizon=None, **kwargs):
     """Batched estimatemodel over many expanding windows (one GPU call).
 
     Window w uses sampleRange = startIndex:endIndices[w], endIndex = endIndices[w]; the
@@ -372,7 +382,10 @@ def estimatewindows(rawdata, dates, endIndices, startIndex=1, keep_draws=False, 
     cdf_grid: grid points ys -> BatchResult.cdf (W, n_h, G), the draw mean of the regime mixture's normal CDF at every grid
     point (calc_cdfs.jl's expectationsbar; cdf_horizons: 0 = the end date, h > 0 = h steps ahead under pi_end A^h), computed on
     the device from the 5-digit-rounded draws (_lib.predictive_cdf_host); the draw arrays it needs are fetched for it and
-    dropped again unless keep_draws."""
+    dropped again unless keep_draws.
+    bias_horizon: h (upstream: 12) -> BatchResult.bias, the BiasMoments of bias_calcs.jl's calcbias per window (uncerbias,
+    totalbias, mean, cov), computed on the device from the 5-digit-rounded draws (_lib.bias_moments_host); its draw arrays are
+    fetched and dropped likewise."""
     if startIndex != 1:
         raise ValueError("windows must start at index 1 (see estopt)")
     rawdata = np.asarray(rawdata, dtype=np.float64)
@@ -391,8 +404,13 @@ def estimatewindows(rawdata, dates, endIndices, startIndex=1, keep_draws=False, 
         Y[w, :Tw[w]] = makey(o)
         yreal[w] = _yreal_row(rawdata, o.endIndex, o.horizons)
     want = keep_draws
-    if cdf_grid is not None and not keep_draws:
-        want = ("mu", "sig2", "pi_end") + (("A",) if any(int(h) > 0 for h in cdf_horizons) else ())
+    if not keep_draws:
+        want = ()
+        if cdf_grid is not None:
+            want += ("mu", "sig2", "pi_end") + (("A",) if any(int(h) > 0 for h in cdf_horizons) else ())
+        if bias_horizon is not None:
+            want += ("mu", "pi_end") + (("A",) if int(bias_horizon) > 0 else ()) + (("fcast",) if len(o0.horizons) else ())
+        want = tuple(k for k in _lib.DRAW_KEYS if k in want) or False
     res = _lib.estimate_batch_host(Y, Tw, o0.D, o0.burnin, o0.Nrun, tuple(o0.horizons), yreal, seed=o0.seed,
                                    device=device, want_draws=want, window_ids=window_ids, want_corr=corr)
     if cdf_grid is not None:
@@ -401,6 +419,11 @@ def estimatewindows(rawdata, dates, endIndices, startIndex=1, keep_draws=False, 
         res["cdf"] = _lib.predictive_cdf_host(res["mu"], res["sig2"], res["pi_end"], res.get("A") if any(h > 0 for h in hz) else None,
                                               ys, hz, device=device)
         res["cdf_grid"], res["cdf_horizons"] = ys, hz
+    if bias_horizon is not None:
+        h = int(bias_horizon)
+        b = _lib.unpack_bias(_lib.bias_moments_host(res["mu"], res["pi_end"], res.get("A") if h > 0 else None,
+                                                    res.get("fcast") if len(o0.horizons) else None, h, device=device), o0.D)
+        res["bias"] = BiasMoments(h, b["uncerbias"], b["totalbias"], b["mean"], b["cov"])
     return BatchResult(opts, res, keep_draws)
 
 
@@ -915,4 +938,80 @@ def write_cdfs(path, dates, ys, horizons, expectationsbar):
     rows = [[str(d), str(int(h)), _fmt(y), _fmt(bar[i, j, g]), _fmt(fin[i, j, g])]
             for i, d in enumerate(dates) for j, h in enumerate(horizons) for g, y in enumerate(ys)]
     _write_csv(path, ["date", "horizon", "y", "cdf", "finverse"], rows)
+    return path
+
+
+# --------------------------------------------------------------- bias_calcs.jl --
+
+def _bias_from_cells(means, states, trans, ferr, horizon):
+    """calcbias (bias_calcs.jl:40-53) on the cells of one date's files: means, states (n, K), trans (n, K * K) in the file's
+    column order (trans_i_j, i fastest), ferr (n,) the forecast_error column of the first horizon or None.  Returns
+    (uncbias, totalbias, mean (2K,), cov (2K, 2K)), the last two in the order futstate | means."""
+    n, K = means.shape
+    fut = np.array(states, dtype=np.float64)
+    if horizon > 0:
+        A = trans.reshape(n, K, K).transpose(0, 2, 1)                                       # A[d, i, j]
+        for _ in range(horizon):                                                            # states' * A^h, one product at a time
+            nw = fut[:, 0, None] * A[:, 0, :]
+            for i in range(1, K):
+                nw = nw + fut[:, i, None] * A[:, i, :]
+            fut = nw
+    v = np.hstack([fut, means])
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = v.mean(axis=0)
+        dv = v - mean
+        covv = dv.T @ dv / (n - 1.0)                                                        # cov(hcat(futstate, means))
+        nab = np.hstack([means, fut]).mean(axis=0)                                          # mean(hcat(means, futstate), dims=1)
+        unc = float(nab @ covv @ nab)                                                       # upstream's index swap, kept
+        tot = float(np.mean(ferr)) if ferr is not None else math.nan
+    return unc, tot, mean, covv
+
+
+def _bias_from_files(datadir, date, horizon):
+    def cells(stem):
+        _, rows = _read_csv(os.path.join(datadir, "%s_%s.csv" % (stem, date)))
+        return np.array([[float(x) for x in r[1:]] for r in rows])
+    means, states = cells("filtered_means"), cells("filtered_state_probs")
+    trans = cells("filtered_trans_probs")
+    fc = cells("forecasts")
+    return _bias_from_cells(means, states, trans, fc[:, 1], horizon)                        # forecasts[:, 3]: date, forecast, error
+
+
+def calcbias(datadir, dates, horizon=12, result=None):
+    """code/hassan_cdfs/bias_calcs.jl:40-53 without the plot: per end date `uncerbias` = nab * covv * nab' with
+    covv = cov(hcat(futstate, means)), nab = mean(hcat(means, futstate)), futstate = states * trans^horizon per draw -- the two
+    column orders differ upstream and are kept -- and `totalbias` = the mean of the first horizon's forecast_error column.
+
+    result=None: as upstream, every date's `filtered_means_`, `filtered_state_probs_`, `filtered_trans_probs_` and
+    `forecasts_<date>.csv` are read back and evaluated on the host in numpy; no GPU is touched.
+    result = a BatchResult of estimatewindows(..., bias_horizon=horizon): the moments were taken on the device from the rounded
+    draws; every date must be one of the result's end dates.
+    Returns (dates, uncerbias (n_dates,), totalbias (n_dates,), mean (n_dates, 2K), cov (n_dates, 2K, 2K)); mean and cov are
+    those of [futstate | means]."""
+    dates = [str(d) for d in dates]
+    horizon = int(horizon)
+    if result is None:
+        rows = [_bias_from_files(datadir, d, horizon) for d in dates]
+        unc, tot = np.array([r[0] for r in rows]), np.array([r[1] for r in rows])
+        mean, cov = np.array([r[2] for r in rows]), np.array([r[3] for r in rows])
+    else:
+        b = getattr(result, "bias", None)
+        if b is None:
+            raise ValueError("result carries no bias moments (estimatewindows(..., bias_horizon=h))")
+        if b.horizon != horizon:
+            raise ValueError("result was computed for another horizon")
+        by_date = {str(enddate(o)): w for w, o in enumerate(result.opts)}
+        for d in dates:
+            if d not in by_date:
+                raise ValueError("no window ends on %s" % d)
+        idx = [by_date[d] for d in dates]
+        unc, tot, mean, cov = b.uncerbias[idx], b.totalbias[idx], b.mean[idx], b.cov[idx]
+    return dates, unc, tot, mean, cov
+
+
+def write_biases(path, dates, uncerbias, totalbias):
+    """One CSV `date,uncerbias,totalbias` with a row per end date, float text as in the other files (_fmt).  Upstream only
+    plots these numbers (bias_calcs.jl:63-64), so this layout is this project's own."""
+    rows = [[str(d), _fmt(u), _fmt(t)] for d, u, t in zip(dates, uncerbias, totalbias)]
+    _write_csv(path, ["date", "uncerbias", "totalbias"], rows)
     return path

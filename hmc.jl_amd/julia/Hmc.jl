@@ -16,7 +16,8 @@
 # (hmcg_save_results_csv: CSV.jl 0.5.16 float text, 250k rows x 5 files in under a second).  Not wired here (available
 # through the C ABI and the Python host layer): checkpoint/resume, the smoothed-probability output, the correlation
 # workbook writer (calccorr's matrices themselves: estimatewindows(...; corr=true)).  calccdfs / predictive_cdf: the
-# predictive CDFs of code/hassan_cdfs/calc_cdfs.jl from the draws, on the device (hmcg_predictive_cdf).  runaggregate /
+# predictive CDFs of code/hassan_cdfs/calc_cdfs.jl from the draws, on the device (hmcg_predictive_cdf).  calcbias /
+# bias_moments: uncerbias and totalbias of code/hassan_cdfs/bias_calcs.jl likewise (hmcg_bias_moments).  runaggregate /
 # calcdispersion of the reference work unchanged on the files written here (same names, columns and float text).
 #
 # Reference lines mirrored: estopt src/Hmc.jl:17-73, accessors :85-107, makedate :573-582,
@@ -84,7 +85,7 @@ end
 const HMCG_MAXTAIL = 256
 const HMCG_MAXDEV = 16
 
-struct hmcg_timing                    # include/hmcg.h (ABI 108)
+struct hmcg_timing                    # include/hmcg.h (ABI 109)
     kernel_ms::Float64
     launches::Int32
     threads_per_window::Int32
@@ -113,6 +114,21 @@ struct hmcg_predictive                # include/hmcg.h: predictive CDFs of the r
     flags::Int32
     reserved::Int32
 end
+
+const HMCG_BIAS_ROUND5 = Int32(1)
+struct hmcg_bias                      # include/hmcg.h: uncertainty-bias moments of the draws (bias_calcs.jl)
+    struct_size::Int32
+    W::Int32
+    K::Int32
+    device::Int32
+    nd::Int64
+    nd_ld::Int64
+    horizon::Int32
+    H::Int32
+    flags::Int32
+    reserved::Int32
+end
+bias_stride(K::Integer) = 2 + 2K + 4K^2     # HMCG_BIAS_STRIDE
 
 last_error() = unsafe_string(ccall((:hmcg_last_error, LIBHMCG), Cstring, ()))
 device_count() = Int(ccall((:hmcg_device_count, LIBHMCG), Cint, ()))
@@ -316,6 +332,66 @@ function calccdfs(opts::Vector{estopt}, ys=-5:.25:15; horizons=[0], device::Inte
     μ, σ, πe = cat3(s -> s.μ), cat3(s -> s.σ), cat3(s -> s.πb[:, 1, :])
     A = any(h -> h > 0, horizons) ? cat((s.A for s in samples)...; dims=4) : nothing
     return [enddate(o) for o in opts], collect(ys), predictive_cdf(μ, σ, πe, A, ys; horizons=horizons, device=device)
+end
+
+# ---- uncertainty-bias moments (code/hassan_cdfs/bias_calcs.jl:40-53) ---------------------------------------------------
+_bias(W, K, nd, ld, horizon, H, device, round5) =
+    hmcg_bias(Int32(sizeof(hmcg_bias)), Int32(W), Int32(K), Int32(device), Int64(nd), Int64(ld), Int32(horizon), Int32(H),
+              round5 ? HMCG_BIAS_ROUND5 : Int32(0), Int32(0))
+
+"""
+    bias_moments(μ, πe, A, forecasts; horizon=12, device=0, round5=true) -> (uncerbias (W), totalbias (W), mean (2K, W), cov (2K, 2K, W))
+
+hmcg_bias_moments over host draw arrays in the layouts estimatewindows fills -- μ, πe (nrun, K, W), A (nrun, K, K, W)
+(`nothing` when horizon is 0), forecasts (nrun, 2H, W) or `nothing`: per window `nab * covv * nab'` with
+covv = cov(hcat(futstate, means)), nab = mean(hcat(means, futstate), dims=1), futstate = πe A^horizon per draw (the two column
+orders differ upstream, bias_calcs.jl:49-51, and are kept), and the mean of forecasts[:, 2] (`totalbias`; NaN without
+forecasts).  mean and cov are those of [futstate | means].
+"""
+function bias_moments(μ::Array{Float64,3}, πe::Array{Float64,3}, A, forecasts; horizon::Integer=12, device::Integer=0,
+                      round5::Bool=true)
+    nrun, K, W = size(μ)
+    H = forecasts === nothing ? 0 : size(forecasts, 2) ÷ 2
+    out = Array{Float64}(undef, bias_stride(K), W)
+    pa = A === nothing ? Ptr{Float64}(C_NULL) : pointer(A)
+    pf = forecasts === nothing ? Ptr{Float64}(C_NULL) : pointer(forecasts)
+    rc = GC.@preserve μ πe A forecasts out ccall((:hmcg_bias_moments, LIBHMCG), Cint,
+        (Ref{hmcg_bias}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}),
+        _bias(W, K, nrun, nrun, horizon, H, device, round5), μ, πe, pa, pf, out, C_NULL)
+    rc == 0 || error("libhmcgibbs rc=$rc: $(last_error())")
+    # the C block holds cov row-major; it is symmetric bit for bit, so the column-major reshape is the same matrix
+    return out[1, :], out[2, :], out[3:2+2K, :], reshape(out[3+2K:end, :], 2K, 2K, W)
+end
+
+"""
+    bias_moments_device(W, K, nd, ld, dμ, dπe, dA, dforecasts, H, dout; horizon=12, device=0, round5=true, stream=C_NULL)
+
+hmcg_bias_moments_device over device pointers (dA = C_NULL when horizon is 0, dforecasts = C_NULL for no totalbias);
+dout holds W * bias_stride(K) doubles; enqueued on `stream` (C_NULL: the library's own) and not waited for.
+"""
+function bias_moments_device(W, K, nd, ld, dμ::Ptr{Float64}, dπe::Ptr{Float64}, dA::Ptr{Float64}, dforecasts::Ptr{Float64}, H,
+                             dout::Ptr{Float64}; horizon::Integer=12, device::Integer=0, round5::Bool=true,
+                             stream::Ptr{Cvoid}=C_NULL)
+    rc = ccall((:hmcg_bias_moments_device, LIBHMCG), Cint,
+               (Ref{hmcg_bias}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}, Ptr{Cvoid}),
+               _bias(W, K, nd, ld, horizon, H, device, round5), dμ, dπe, dA, dforecasts, dout, stream, C_NULL)
+    rc == 0 || error("libhmcgibbs rc=$rc: $(last_error())")
+    return nothing
+end
+
+"""
+    calcbias(opts; horizon=12, device=0) -> (dates, uncerbias, totalbias)
+
+bias_calcs.jl without the per-draw files and the plot: estimates the windows and takes both numbers from their draws on
+the device.
+"""
+function calcbias(opts::Vector{estopt}; horizon::Integer=12, device::Integer=0)
+    samples, _, _ = estimatewindows(opts; device=device)
+    cat3(f) = cat((f(s) for s in samples)...; dims=3)
+    μ, πe, fc = cat3(s -> s.μ), cat3(s -> s.πb[:, 1, :]), cat3(s -> s.forecasts)
+    A = horizon > 0 ? cat((s.A for s in samples)...; dims=4) : nothing
+    unc, tot, _, _ = bias_moments(μ, πe, A, size(fc, 2) > 0 ? fc : nothing; horizon=horizon, device=device)
+    return [enddate(o) for o in opts], unc, tot
 end
 
 """

@@ -25,6 +25,9 @@
  *                                  regime mixture's normal CDF on a grid of points (`expectationsbar`), taken from the
  *                                  draw arrays instead of the three per-draw CSV files it reads back; with horizons > 0
  *                                  the same mixture under the h-step state law pi_end * A^h of forecast (src/Hmc.jl:662-663).
+ *   hmcg_bias_moments[_device]     code/hassan_cdfs/bias_calcs.jl:40-53 (calcbias): per end date the mean and covariance over
+ *                                  the draws of [pi_end * A^12 | mu] and the two numbers it reduces them to (uncerbias,
+ *                                  totalbias), taken from the draw arrays instead of the four per-draw CSV files it reads back.
  *
  * Conventions: plain C structs, fixed-width ints, no C++ types or exceptions cross
  * the boundary.  Return 0 on success, negative on API misuse (HMCG_E_*), positive
@@ -57,7 +60,7 @@
 extern "C" {
 #endif
 
-#define HMCG_VERSION 108
+#define HMCG_VERSION 109
 #define HMCG_MAXH 8
 #define HMCG_MAXTAIL 256        /* most signal steps past the end date (sigLen, src/Hmc.jl:888) */
 #define HMCG_MAXK 8
@@ -280,6 +283,47 @@ int hmcg_predictive_cdf_device(const hmcg_predictive* p, const double* dmu, cons
  * kernel of the one before. */
 int hmcg_predictive_cdf(const hmcg_predictive* p, const double* mu, const double* sig2, const double* pi_end,
                         const double* A, const double* grid, double* cdf, hmcg_timing* timing);
+
+/* ---- uncertainty-bias moments of the draws (bias_calcs.jl) ------------------------------------------------------------------
+ * Per window, over its nd draws d (code/hassan_cdfs/bias_calcs.jl:40-53, `calcbias`):
+ *   futstate_d = pi_end_d * A_d^horizon   h successive row-vector x matrix products, k ascending in every dot product: the same
+ *                                         bits as the weights of hmcg_predictive_cdf (upstream: states[i,:]' * reshape(trans[i,:],3,3)^12)
+ *   v_d        = [futstate_d | mu_d]      2K columns
+ *   mean       = mean over d of v_d;  cov = cov(v), divisor nd - 1 (`covv = cov(hcat(futstate, means))`)
+ *   nab        = [mean of mu | mean of futstate]           (`nab = mean(hcat(means, futstate), dims=1)`: the OTHER column order)
+ *   uncbias    = nab * cov * nab'     exactly as upstream writes it: nab is ordered means | futstate while cov is ordered
+ *                                     futstate | means.  The mismatch is upstream's and is kept; `mean` and `cov` are returned
+ *                                     too, so a caller who wants the aligned quadratic form can take it from those.
+ *   totalbias  = mean over d of fcast[d, 1, w]   (`forecasts[:, 3]`: forecast_error of the first horizon); NaN when fcast is NULL.
+ * out[w] holds HMCG_BIAS_STRIDE(K) doubles: uncbias, totalbias, mean[2K] (futstate | means), cov[2K][2K] (same order, symmetric,
+ * both triangles written, bit-equal).  Draw arrays: the layouts and the nd_ld rule of the predictive entries; fcast is
+ * (nd_ld, 2H, W).  HMCG_BIAS_ROUND5: every input is first rounded as a CSV cell is (as HMCG_PRED_ROUND5).
+ * Second moments are taken about the window's draw 0 (S1_a = sum(v_a - p_a), S2_ab = sum (v_a - p_a)(v_b - p_b)), so a large
+ * common offset costs no digits; cov_ab = (S2_ab - S1_a S1_b / nd) / (nd - 1).  nd = 1 gives a finite mean and NaN cov and
+ * uncbias (0/0, as Statistics.cov).  NaN inputs propagate; nothing is special-cased.
+ * Deterministic: draws are reduced in slabs of 1024 (the predictive entries' cut), inside a slab in an order that depends on
+ * the draw index alone, the slabs in slab order, no floating-point atomics: bit-identical from run to run, from both entries
+ * and for every chunking of the host entry's upload (HMCG_CHUNK_DRAWS under HMCG_DIAG=1).
+ * Misuse (HMCG_E_BADARG, checked before any HIP call): struct_size, K outside 2..HMCG_MAXK, horizon outside 0..HMCG_PRED_MAXH,
+ * W < 1, nd < 1, nd_ld < nd, a NULL mu / pi_end / out, NULL A with horizon > 0, fcast given with H outside 1..HMCG_MAXH. */
+#define HMCG_BIAS_ROUND5 1
+#define HMCG_BIAS_STRIDE(K) (2 + 2 * (K) + 4 * (K) * (K))
+typedef struct hmcg_bias {
+    int32_t struct_size, W, K, device;
+    int64_t nd, nd_ld;                 /* draws per window; leading dimension of the draw arrays (>= nd) */
+    int32_t horizon;                   /* 0..HMCG_PRED_MAXH; bias_calcs.jl uses 12 */
+    int32_t H;                         /* fcast has 2H columns per window; 0 when fcast is NULL */
+    int32_t flags, reserved;
+} hmcg_bias;
+/* Device entry: every data pointer is HBM-resident on p->device; enqueued on `stream` (NULL: the library's own) behind the
+ * library's earlier work there; returns after enqueueing unless `timing` is given (kernel_ms: HIP events around the kernels). */
+int hmcg_bias_moments_device(const hmcg_bias* p, const double* dmu, const double* dpi_end, const double* dA /* NULL iff horizon is 0 */,
+                             const double* dfcast /* may be NULL */, double* dout /* [W][HMCG_BIAS_STRIDE(K)] */, void* stream,
+                             hmcg_timing* timing);
+/* Host entry (blocking): uploads the draws in chunks of whole slabs through pinned staging, the copy of one chunk beside the
+ * kernel of the one before. */
+int hmcg_bias_moments(const hmcg_bias* p, const double* mu, const double* pi_end, const double* A, const double* fcast, double* out,
+                      hmcg_timing* timing);
 
 /* ---- per-draw CSV output (host code, no GPU): basicsave / saveresults, src/Hmc.jl:707-748 ------------------------------
  * The five per-window files `filtered_means_<date>.csv`, `filtered_variances_<date>.csv`, `filtered_state_probs_<date>.csv`,
