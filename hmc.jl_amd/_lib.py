@@ -26,13 +26,17 @@ HMCG_MAXTAIL = 256
 EXPORTS = ("hmcg_version", "hmcg_device_count", "hmcg_last_error", "hmcg_shutdown",
            "hmcg_estimate_batch", "hmcg_estimate_batch_device", "hmcg_estimate_batch_multi",
            "hmcg_save_results_csv", "hmcg_write_table_csv", "hmcg_format_float",
-           "hmcg_predictive_cdf", "hmcg_predictive_cdf_device", "hmcg_bias_moments", "hmcg_bias_moments_device")
+           "hmcg_predictive_cdf", "hmcg_predictive_cdf_device", "hmcg_bias_moments", "hmcg_bias_moments_device",
+           "hmcg_mixture_moments", "hmcg_mixture_moments_device")
 HMCG_MAXDEV = 16
 PRED_ROUND5 = 1
 HMCG_MAXGRID = 4096
 HMCG_PRED_MAXH = 1024           # largest horizon of the predictive CDFs
 PRED_SLAB = 1024                # draws per reduction slab (csrc/predictive_plan.hpp): the host entry uploads whole slabs
 BIAS_ROUND5 = 1
+MIX_ROUND5 = 1
+MIX_STRIDE = 8                  # HMCG_MIX_STRIDE: doubles per (window, horizon) of the mixture-moment output
+MIX_FIELDS = ("mean", "variance", "skewness", "kurtosis", "within", "between", "draw_skewness", "weight")
 
 
 def bias_stride(K):
@@ -80,6 +84,12 @@ class Bias(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("W", C.c_int32), ("K", C.c_int32), ("device", C.c_int32),
                 ("nd", C.c_int64), ("nd_ld", C.c_int64), ("horizon", C.c_int32), ("H", C.c_int32),
                 ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class MixMom(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("W", C.c_int32), ("K", C.c_int32), ("device", C.c_int32),
+                ("nd", C.c_int64), ("nd_ld", C.c_int64), ("n_h", C.c_int32), ("flags", C.c_int32),
+                ("horizons", C.c_int32 * HMCG_MAXH)]
 
 
 _LIB = None
@@ -144,6 +154,8 @@ def load():
         L.hmcg_predictive_cdf_device.restype = C.c_int
         L.hmcg_bias_moments.restype = C.c_int
         L.hmcg_bias_moments_device.restype = C.c_int
+        L.hmcg_mixture_moments.restype = C.c_int
+        L.hmcg_mixture_moments_device.restype = C.c_int
         _LIB = L
     return _LIB
 
@@ -498,6 +510,65 @@ def bias_moments_device(bias, dmu, dpi_end, dA, dfcast, dout, stream=None, timed
 
     _check(load().hmcg_bias_moments_device(C.byref(bias), vp(dmu), vp(dpi_end), vp(dA), vp(dfcast), vp(dout), vp(stream),
                                            C.byref(tm) if timed else None))
+    return tm
+
+
+def make_mixmom(W, K, nd, nd_ld, horizons=(0,), device=0, round5=True):
+    """hmcg_mixmom of a call.  More than HMCG_MAXH horizons raise here; every other rule is the library's (HMCG_E_BADARG)."""
+    if len(horizons) > HMCG_MAXH:
+        raise ValueError("at most %d horizons" % HMCG_MAXH)
+    p = MixMom()
+    p.struct_size = C.sizeof(MixMom)
+    p.W, p.K, p.device, p.nd, p.nd_ld, p.n_h = int(W), int(K), int(device), int(nd), int(nd_ld), len(horizons)
+    for i, h in enumerate(horizons):
+        p.horizons[i] = int(h)
+    p.flags = MIX_ROUND5 if round5 else 0
+    return p
+
+
+def unpack_mixture_moments(out):
+    """The (W, n_h, HMCG_MIX_STRIDE) output block as a dict of (W, n_h) arrays: mean, variance, skewness, kurtosis (excess) of
+    the pooled predictive mixture, within (mean per-draw variance), between (variance over the draws of the per-draw mean,
+    divisor nd), draw_skewness (mean per-draw skewness), weight (mean of sum_k omega_k)."""
+    out = np.asarray(out)
+    return {name: out[:, :, i].copy() for i, name in enumerate(MIX_FIELDS)}
+
+
+def mixture_moments_host(mu, sig2, pi_end, A, horizons=(0,), device=0, round5=True, timing=None):
+    """hmcg_mixture_moments over host (numpy) draw arrays in the C-ABI layouts -- mu/sig2/pi_end (W, K, nd), A (W, K, K, nd) with
+    A[w, j, i, d] = draw d of A[i, j] (None when every horizon is 0) -- as estimate_batch_host returns them.  Returns the
+    (W, n_h, 8) block (unpack_mixture_moments names its parts): per window and horizon the moments of the predictive law
+    sum_k omega_k N(mu_k, sig2_k), omega = pi_end A^h, pooled over the draws in closed form (skewness.jl and alt_forecasts.jl
+    asked of the draws), and its within- / between-draw split.  round5 (default): every input is first rounded to 5 digits, as
+    the cells of the per-draw CSV files are.  timing: a Timing to fill."""
+    mu = np.ascontiguousarray(mu, dtype=np.float64)
+    W, K, nd = mu.shape
+    sig2 = np.ascontiguousarray(sig2, dtype=np.float64)
+    pi_end = np.ascontiguousarray(pi_end, dtype=np.float64)
+    if sig2.shape != mu.shape or pi_end.shape != mu.shape:
+        raise ValueError("mu, sig2 and pi_end must share the shape (W, K, nd)")
+    if A is not None:
+        A = np.ascontiguousarray(A, dtype=np.float64)
+        if A.shape != (W, K, K, nd):
+            raise ValueError("A must have the shape (W, K, K, nd)")
+    p = make_mixmom(W, K, nd, nd, horizons, device, round5)
+    out = np.zeros((W, len(horizons), MIX_STRIDE))
+    _check(load().hmcg_mixture_moments(C.byref(p), _np_ptr(mu), _np_ptr(sig2), _np_ptr(pi_end), _np_ptr(A), _np_ptr(out),
+                                       C.byref(timing) if timing is not None else None))
+    return out
+
+
+def mixture_moments_device(mix, dmu, dsig2, dpi_end, dA, dout, stream=None, timed=False):
+    """hmcg_mixture_moments_device over raw device pointers (ints, e.g. torch tensor.data_ptr(); dA 0 / None when every horizon
+    is 0); mix: make_mixmom(...).  Enqueued on `stream` (None: the library's own).  Returns the Timing struct when timed (the
+    call then waits for completion), else None."""
+    tm = Timing() if timed else None
+
+    def vp(x):
+        return None if not x else C.c_void_p(int(x))
+
+    _check(load().hmcg_mixture_moments_device(C.byref(mix), vp(dmu), vp(dsig2), vp(dpi_end), vp(dA), vp(dout), vp(stream),
+                                              C.byref(tm) if timed else None))
     return tm
 
 

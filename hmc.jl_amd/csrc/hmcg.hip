@@ -34,6 +34,7 @@
 #include "plan.hpp"
 #include "predictive.hpp"
 #include "bias.hpp"
+#include "mixmoments.hpp"
 
 namespace {
 
@@ -119,6 +120,7 @@ struct DeviceCtx {
     Arena ord;                     // device entry: the bucketed dispatch's window lists (bucket_lists_kernel)
     Arena pred;                    // device entry of the predictive CDFs: the slab sums
     Arena bias;                    // device entry of the uncertainty-bias moments: the slab sums and pivots
+    Arena mix;                     // device entry of the predictive-mixture moments: the slab sums and pivots
     hmcg_hostutil::ScatterPool pool;              // host entries: helpers for the scatter into the caller's arrays
 };
 DeviceCtx g_ctx[HMCG_MAXDEV];
@@ -217,6 +219,7 @@ void destroy_context(DeviceCtx& c)
     c.ord.release();
     c.pred.release();
     c.bias.release();
+    c.mix.release();
     c.pool.stop();
     c.stream = c.copy = nullptr;
     c.ready = false;
@@ -1207,6 +1210,126 @@ int bias_host(DeviceCtx& c, const hmcg_bias* p, const double* mu, const double* 
     return 0;
 }
 
+// ---- predictive-mixture moments of the draws (mixmoments.hip; argument rules and the walk: mixmoments_plan.hpp; slab / chunk cut:
+// predictive_plan.hpp) -----------------------------------------------------------------------------------------------------------
+
+void fill_mix_timing(hmcg_timing* t, const hmcg_mixmom* p, const DeviceCtx& c, double kernel_ms, int launches, double call_ms)
+{
+    memset(t, 0, sizeof *t);
+    t->kernel_ms = kernel_ms; t->launches = launches; t->call_ms = call_ms;
+    t->device = c.device; t->windows = p->W; t->buckets = 1; t->threads_per_window = 256;
+}
+
+// Caller holds c.mu and has made c.device current.  The slab sums live in a context-owned arena (as those of the predictive CDFs do).
+int mix_device(DeviceCtx& c, const hmcg_mixmom* p, const double* dmu, const double* dsig2, const double* dpi_end, const double* dA,
+               double* dout, hipStream_t stream, hmcg_timing* timing)
+{
+    int rc = grow_shared(c, c.mix, sizeof(double) * mix_part_doubles(p->W, p->nd, p->n_h));
+    if (rc) return rc;
+    HIP_TRY(hipStreamWaitEvent(stream, c.ev_scr, 0));
+    if (timing) HIP_TRY(hipEventRecord(c.ev0, stream));
+    hmcg_host::MixArgs a{};
+    a.W = p->W; a.K = p->K; a.n_h = p->n_h; a.walk = mix_walk(*p); a.round5 = (p->flags & HMCG_MIX_ROUND5) != 0;
+    a.mu = dmu; a.sig2 = dsig2; a.pi_end = dpi_end; a.A = dA;
+    a.part = reinterpret_cast<double*>(c.mix.base);
+    a.nd = p->nd; a.nd_ld = p->nd_ld; a.slab0 = 0; a.nslab_total = pred_slabs(p->nd);
+    HIP_TRY(launch_mixmoments(a, stream));
+    HIP_TRY(launch_mixmoments_finalize(a.part, dout, p->W, p->n_h, p->nd, stream));
+    HIP_TRY(hipEventRecord(c.ev_scr, stream));
+    if (timing) {
+        HIP_TRY(hipEventRecord(c.ev1, stream));
+        HIP_TRY(hipEventSynchronize(c.ev1));
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, c.ev0, c.ev1));
+        fill_mix_timing(timing, p, c, ms, 2, 0.0);
+    }
+    return 0;
+}
+
+// Host entry on one device, as bias_host: whole-slab chunks packed window by window, column by column into pinned staging
+// (mu | sig2 | pi_end | A, leading dimension = the chunk's draws), RING buffers deep, the copy of chunk c + 1 beside the kernel of
+// chunk c; every chunk files its slabs' sums in the same table (the first one the pivots too); one finalize at the end.
+int mix_host(DeviceCtx& c, const hmcg_mixmom* p, const double* mu, const double* sig2, const double* pi_end, const double* A, double* out,
+             hmcg_timing* timing)
+{
+    const auto t_call = std::chrono::steady_clock::now();
+    const int K = p->K, W = p->W;
+    const bool with_A = mix_max_horizon(*p) > 0;
+    const int ncol = mix_columns(*p);
+    long long cap = 0;
+    if (const char* cenv = diag_env("HMCG_CHUNK_DRAWS")) cap = atoll(cenv);
+    const long long cdraws = pred_chunk_draws(p->nd, W, ncol, cap);
+    const std::vector<PredChunk> chunks = pred_chunks(p->nd, cdraws);
+    const size_t nout = (size_t)W * (size_t)p->n_h * (size_t)HMCG_MIX_STRIDE;
+    auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
+    const size_t b_chunk = up(sizeof(double) * (size_t)W * (size_t)ncol * (size_t)cdraws);
+    const size_t b_out = up(sizeof(double) * nout);
+    const size_t b_part = up(sizeof(double) * mix_part_doubles(W, p->nd, p->n_h));
+    const int nbuf = (int)std::min<size_t>(RING, chunks.size());
+    if (c.dev.ensure(b_out + b_part + b_chunk * (size_t)nbuf) || c.pin.ensure(b_out + b_chunk * (size_t)nbuf)) {
+        set_err("workspace allocation failed (%zu B device, %zu B pinned)", b_out + b_part + b_chunk * (size_t)nbuf,
+                b_out + b_chunk * (size_t)nbuf);
+        return HMCG_E_NOMEM;
+    }
+    double* dout = reinterpret_cast<double*>(c.dev.base);
+    double* dpart = reinterpret_cast<double*>(c.dev.base + b_out);
+    char* dchunk = c.dev.base + b_out + b_part;
+    double* pout = reinterpret_cast<double*>(c.pin.base);
+    char* pchunk = c.pin.base + b_out;
+
+    struct Events {
+        std::vector<hipEvent_t> ev;
+        ~Events() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+    } tev;                                       // two per chunk, around its kernel (created only when timing is asked for)
+    if (timing) {
+        tev.ev.assign(2 * chunks.size(), nullptr);
+        for (hipEvent_t& e : tev.ev) HIP_TRY(hipEventCreate(&e));
+    }
+    hmcg_host::MixArgs a{};
+    a.W = W; a.K = K; a.n_h = p->n_h; a.walk = mix_walk(*p); a.round5 = (p->flags & HMCG_MIX_ROUND5) != 0;
+    a.part = dpart; a.nslab_total = pred_slabs(p->nd);
+    for (size_t ci = 0; ci < chunks.size(); ++ci) {
+        const PredChunk& ch = chunks[ci];
+        const int b = (int)(ci % (size_t)nbuf);
+        if (ci >= (size_t)nbuf) HIP_TRY(hipEventSynchronize(c.evk[b]));       // the kernel that read this buffer pair is done
+        double* pb = reinterpret_cast<double*>(pchunk + b_chunk * (size_t)b);
+        double* db = reinterpret_cast<double*>(dchunk + b_chunk * (size_t)b);
+        // packed chunk: mu | sig2 | pi_end | A, each [W][columns][ch.n]
+        const size_t n = (size_t)ch.n, o_col = (size_t)W * K * n;
+        auto pack = [&](const double* src, size_t cols, double* dst) {
+            for (size_t q = 0; q < (size_t)W * cols; ++q) memcpy(dst + q * n, src + q * (size_t)p->nd_ld + (size_t)ch.d0, sizeof(double) * n);
+        };
+        pack(mu, (size_t)K, pb);
+        pack(sig2, (size_t)K, pb + o_col);
+        pack(pi_end, (size_t)K, pb + 2 * o_col);
+        if (with_A) pack(A, (size_t)K * K, pb + 3 * o_col);
+        HIP_TRY(hipMemcpyAsync(db, pb, sizeof(double) * (size_t)W * (size_t)ncol * n, hipMemcpyHostToDevice, c.copy));
+        HIP_TRY(hipEventRecord(c.evc[b], c.copy));
+        HIP_TRY(hipStreamWaitEvent(c.stream, c.evc[b], 0));
+        a.mu = db; a.sig2 = db + o_col; a.pi_end = db + 2 * o_col; a.A = with_A ? db + 3 * o_col : nullptr;
+        a.nd = ch.n; a.nd_ld = ch.n; a.slab0 = ch.d0 / PRED_SLAB;
+        if (timing) HIP_TRY(hipEventRecord(tev.ev[2 * ci], c.stream));
+        HIP_TRY(launch_mixmoments(a, c.stream));
+        if (timing) HIP_TRY(hipEventRecord(tev.ev[2 * ci + 1], c.stream));
+        HIP_TRY(hipEventRecord(c.evk[b], c.stream));
+    }
+    HIP_TRY(launch_mixmoments_finalize(dpart, dout, W, p->n_h, p->nd, c.stream));
+    HIP_TRY(hipMemcpyAsync(pout, dout, sizeof(double) * nout, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    memcpy(out, pout, sizeof(double) * nout);
+    if (timing) {
+        double kernel_ms = 0.0;
+        for (size_t ci = 0; ci < chunks.size(); ++ci) {
+            float ms = 0.f;
+            HIP_TRY(hipEventElapsedTime(&ms, tev.ev[2 * ci], tev.ev[2 * ci + 1]));
+            kernel_ms += ms;
+        }
+        const double call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+        fill_mix_timing(timing, p, c, kernel_ms, (int)chunks.size() + 1, call_ms);
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1372,6 +1495,36 @@ int hmcg_bias_moments(const hmcg_bias* p, const double* mu, const double* pi_end
     std::lock_guard<std::mutex> lk(c->mu);
     HIP_TRY(hipSetDevice(c->phys));
     return bias_host(*c, p, mu, pi_end, A, fcast, out, timing);
+}
+
+int hmcg_mixture_moments_device(const hmcg_mixmom* p, const double* dmu, const double* dsig2, const double* dpi_end, const double* dA,
+                                double* dout, void* stream, hmcg_timing* timing)
+{
+    g_err[0] = 0;
+    char msg[160];
+    int rc = check_mixmom(p, dmu, dsig2, dpi_end, dA, dout, msg, sizeof msg);
+    if (rc) { set_err("%s", msg); return rc; }
+    DeviceCtx* c = nullptr;
+    rc = get_context(p->device, &c);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->phys));
+    return mix_device(*c, p, dmu, dsig2, dpi_end, dA, dout, stream ? (hipStream_t)stream : c->stream, timing);
+}
+
+int hmcg_mixture_moments(const hmcg_mixmom* p, const double* mu, const double* sig2, const double* pi_end, const double* A, double* out,
+                         hmcg_timing* timing)
+{
+    g_err[0] = 0;
+    char msg[160];
+    int rc = check_mixmom(p, mu, sig2, pi_end, A, out, msg, sizeof msg);
+    if (rc) { set_err("%s", msg); return rc; }
+    DeviceCtx* c = nullptr;
+    rc = get_context(p->device, &c);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->phys));
+    return mix_host(*c, p, mu, sig2, pi_end, A, out, timing);
 }
 
 }  // extern "C"

@@ -115,6 +115,24 @@ class DevicePanel:
             self.last_timing = tm
         return out
 
+    def mixture_moments(self, horizons=(0,), timed=False, round5=True):
+        """Moments of the predictive regime mixture from the panel's own HBM draws (hmcg_mixture_moments_device; skewness.jl
+        and alt_forecasts.jl asked of the draws): a (W, n_h, 8) tensor, per window and horizon mean, variance, skewness and
+        excess kurtosis of sum_k omega_k N(mu_k, sig2_k), omega = pi_end A^h, pooled over the kept draws, then the mean
+        within-draw variance, the variance of the per-draw mean, the mean per-draw skewness and the mean weight
+        (_lib.unpack_mixture_moments names the parts of its numpy copy).  Enqueued on the library stream behind `run`; with
+        timed=True the call waits and last_timing holds the HIP-event time, otherwise call sync() before reading the tensor."""
+        if self.mu is None:
+            raise _lib.HmcgError("mixture_moments needs the draws in HBM: the panel was built with keep_draws=False")
+        hz = tuple(int(h) for h in horizons)
+        out = self.torch.empty((self.W, len(hz), _lib.MIX_STRIDE), dtype=self.torch.float64, device=self.dev)
+        mix = _lib.make_mixmom(self.W, self.K, self.nrun, self.nrun, hz, self.device_index, round5)
+        tm = _lib.mixture_moments_device(mix, self.mu.data_ptr(), self.sig2.data_ptr(), self.pi_end.data_ptr(),
+                                         self.A.data_ptr() if any(h > 0 for h in hz) else 0, out.data_ptr(), None, timed)
+        if timed:
+            self.last_timing = tm
+        return out
+
     def sync(self):
         """Wait for the library stream (untimed runs are asynchronous)."""
         self.torch.cuda.synchronize(self.dev)

@@ -15,6 +15,9 @@ ABI.  Names, argument meaning and result layout follow the reference:
     calccorr            src/Hmc.jl:1094-1163 (correlations.xlsx; matrices from the files or from the device)
     calccdfs            code/hassan_cdfs/calc_cdfs.jl:31-42 (predictive CDFs; from the files or from the device)
     calcbias            code/hassan_cdfs/bias_calcs.jl:40-53 (uncerbias / totalbias; from the files or from the device)
+    calcskewness        code/skewness.jl:22-43 (the plug-in mixture's skewness, in closed form instead of 10 000 000 variates)
+    altforecasts        code/alt_forecasts.jl:23-39 (plug-in against proper 12-month forecast; forecast_comparision.csv)
+    calcmoments         both questions asked of the draws: moments of the predictive mixture (from the files or from the device)
 
 New (the reference batches by launching one SLURM task per window,
 slurmscripts/base_estimation.sh:5): `estimatewindows`, one call for many windows.
@@ -349,6 +352,17 @@ class BiasMoments:
         self.horizon, self.uncerbias, self.totalbias, self.mean, self.cov = int(horizon), uncerbias, totalbias, mean, cov
 
 
+class MixtureMoments:
+    """Moments of the predictive law sum_k omega_k N(mu_k, sig2_k), omega = pi_end A^h, pooled over a window's draws: (W, n_h)
+    arrays mean, variance, skewness, kurtosis (excess), within (mean per-draw variance), between (variance over the draws of
+    the per-draw mean), draw_skewness (mean per-draw skewness), weight (mean of sum_k omega_k); horizons: the n_h horizons."""
+
+    def __init__(self, horizons, parts):
+        self.horizons = tuple(int(h) for h in horizons)
+        for name in _lib.MIX_FIELDS:
+            setattr(self, name, parts[name])
+
+
 class BatchResult:
     """Result of estimatewindows: per-window posterior summaries (+ optional draws)."""
 
@@ -362,6 +376,7 @@ class BatchResult:
         self.cdf_grid = res.get("cdf_grid")
         self.cdf_horizons = res.get("cdf_horizons")
         self.bias = res.get("bias")            # with bias_horizon: BiasMoments (uncerbias, totalbias, mean, cov) per window
+        self.moments = res.get("moments")      # with moment_horizons: MixtureMoments, (W, n_h) arrays
         self._res = res if keep_draws else None
 
     def samples(self, w):
@@ -372,7 +387,7 @@ class BatchResult:
 
 
 def estimatewindows(rawdata, dates, endIndices, startIndex=1, keep_draws=False, device=0, window_ids=None, corr=False,
-                    cdf_grid=None, cdf_horizons=(0,), bias_horizon=None, **kwargs):
+                    cdf_grid=None, cdf_horizons=(0,), bias_horizon=None, moment_horizons=None, **kwargs):
     """Batched estimatemodel over many expanding windows (one GPU call).
 
     Window w uses sampleRange = startIndex:endIndices[w], endIndex = endIndices[w]; the
@@ -385,7 +400,10 @@ def estimatewindows(rawdata, dates, endIndices, startIndex=1, keep_draws=False, 
     dropped again unless keep_draws.
     bias_horizon: h (upstream: 12) -> BatchResult.bias, the BiasMoments of bias_calcs.jl's calcbias per window (uncerbias,
     totalbias, mean, cov), computed on the device from the 5-digit-rounded draws (_lib.bias_moments_host); its draw arrays are
-    fetched and dropped likewise."""
+    fetched and dropped likewise.
+    moment_horizons: horizons (0 = the end date, as skewness.jl; 12 as alt_forecasts.jl) -> BatchResult.moments, the
+    MixtureMoments of the predictive regime mixture per window and horizon, computed on the device from the 5-digit-rounded
+    draws (_lib.mixture_moments_host); its draw arrays are fetched and dropped likewise."""
     if startIndex != 1:
         raise ValueError("windows must start at index 1 (see estopt)")
     rawdata = np.asarray(rawdata, dtype=np.float64)
@@ -410,6 +428,8 @@ def estimatewindows(rawdata, dates, endIndices, startIndex=1, keep_draws=False, 
             want += ("mu", "sig2", "pi_end") + (("A",) if any(int(h) > 0 for h in cdf_horizons) else ())
         if bias_horizon is not None:
             want += ("mu", "pi_end") + (("A",) if int(bias_horizon) > 0 else ()) + (("fcast",) if len(o0.horizons) else ())
+        if moment_horizons is not None:
+            want += ("mu", "sig2", "pi_end") + (("A",) if any(int(h) > 0 for h in moment_horizons) else ())
         want = tuple(k for k in _lib.DRAW_KEYS if k in want) or False
     res = _lib.estimate_batch_host(Y, Tw, o0.D, o0.burnin, o0.Nrun, tuple(o0.horizons), yreal, seed=o0.seed,
                                    device=device, want_draws=want, window_ids=window_ids, want_corr=corr)
@@ -424,6 +444,11 @@ def estimatewindows(rawdata, dates, endIndices, startIndex=1, keep_draws=False, 
         b = _lib.unpack_bias(_lib.bias_moments_host(res["mu"], res["pi_end"], res.get("A") if h > 0 else None,
                                                     res.get("fcast") if len(o0.horizons) else None, h, device=device), o0.D)
         res["bias"] = BiasMoments(h, b["uncerbias"], b["totalbias"], b["mean"], b["cov"])
+    if moment_horizons is not None:
+        hz = tuple(int(h) for h in moment_horizons)
+        out = _lib.mixture_moments_host(res["mu"], res["sig2"], res["pi_end"], res.get("A") if any(h > 0 for h in hz) else None,
+                                        hz, device=device)
+        res["moments"] = MixtureMoments(hz, _lib.unpack_mixture_moments(out))
     return BatchResult(opts, res, keep_draws)
 
 
@@ -1014,4 +1039,134 @@ def write_biases(path, dates, uncerbias, totalbias):
     plots these numbers (bias_calcs.jl:63-64), so this layout is this project's own."""
     rows = [[str(d), _fmt(u), _fmt(t)] for d, u, t in zip(dates, uncerbias, totalbias)]
     _write_csv(path, ["date", "uncerbias", "totalbias"], rows)
+    return path
+
+
+# ------------------------------------------------ skewness.jl, alt_forecasts.jl --
+
+def _moments_from_cells(means, vars_, pis, trans, horizons):
+    """The (n_h, 8) block of include/hmcg.h's table from the cells of one date's files: (n, K) each, trans (n, K * K) in the
+    file's column order.  The library's algebra in numpy: per-draw closed-form moments about the pivot c = the mixture mean of
+    draw 0, summed over the draws."""
+    n, K = means.shape
+    A = None if trans is None else trans.reshape(n, K, K).transpose(0, 2, 1)               # columns trans_i_j, i fastest -> A[d, i, j]
+    out = np.empty((len(horizons), _lib.MIX_STRIDE))
+    for j, h in enumerate(horizons):
+        w = pis.copy()
+        for _ in range(h):                                                                  # pi_end * A^h, one product at a time
+            nw = w[:, 0, None] * A[:, 0, :]
+            for i in range(1, K):
+                nw = nw + w[:, i, None] * A[:, i, :]
+            w = nw
+        with np.errstate(invalid="ignore", divide="ignore"):
+            s = w.sum(axis=1)
+            c = (w[0] * means[0]).sum() / s[0]
+            d = means - c
+            d2 = d * d
+            P = [s.sum(), (w * d).sum(), (w * (d2 + vars_)).sum(), (w * d * (d2 + 3.0 * vars_)).sum(),
+                 (w * (d2 * d2 + 6.0 * d2 * vars_ + 3.0 * vars_ * vars_)).sum()]
+            a = (w * d).sum(axis=1) / s
+            e = d - a[:, None]
+            var_d = (w * (e * e + vars_)).sum(axis=1) / s
+            skew_d = (w * e * (e * e + 3.0 * vars_)).sum(axis=1) / s / (var_d * np.sqrt(var_d))
+            b = a - a[0]
+            m1, m2, m3, m4 = (p / P[0] for p in P[1:])
+            var = m2 - m1 * m1
+            out[j] = [c + m1, var, (m3 - 3.0 * m1 * m2 + 2.0 * m1 ** 3) / (var * np.sqrt(var)),
+                      (m4 - 4.0 * m1 * m3 + 6.0 * m1 * m1 * m2 - 3.0 * m1 ** 4) / (var * var) - 3.0,
+                      var_d.sum() / n, (b * b).sum() / n - (b.sum() / n) ** 2, skew_d.sum() / n, P[0] / n]
+    return out
+
+
+def _moments_from_files(datadir, date, horizons):
+    def cells(stem):
+        _, rows = _read_csv(os.path.join(datadir, "%s_%s.csv" % (stem, date)))
+        return np.array([[float(x) for x in r[1:]] for r in rows])
+    means, vars_, pis = cells("filtered_means"), cells("filtered_variances"), cells("filtered_state_probs")
+    trans = cells("filtered_trans_probs") if any(h > 0 for h in horizons) else None
+    return _moments_from_cells(means, vars_, pis, trans, horizons)
+
+
+def calcmoments(datadir, dates, horizons=(0,), result=None):
+    """What code/skewness.jl and code/alt_forecasts.jl ask of the posterior-summary rows, asked of the draws: per end date and
+    horizon h the moments of the predictive law y_{T+h} ~ sum_k omega_k N(mu_k, sig2_k), omega = pi_end A^h, pooled over the
+    draws in closed form -- mean (the proper forecast alt_forecasts.jl sets its plug-in against), variance, skewness (what
+    skewness.jl samples for, with the parameter uncertainty in), excess kurtosis -- and the split a plug-in hides: `within`
+    (mean per-draw variance), `between` (variance over the draws of the per-draw mean), `draw_skewness`, `weight`.
+
+    result=None: every date's `filtered_means_`, `filtered_variances_`, `filtered_state_probs_<date>.csv` (and
+    `filtered_trans_probs_<date>.csv` with a horizon > 0) are read back and evaluated on the host in numpy; no GPU is touched.
+    result = a BatchResult of estimatewindows(..., moment_horizons=horizons): the sums were taken on the device from the
+    rounded draws; every date must be one of the result's end dates.
+    Returns (dates, moments): a dict of (n_dates, n_h) arrays under the names of _lib.MIX_FIELDS."""
+    dates = [str(d) for d in dates]
+    horizons = tuple(int(h) for h in horizons)
+    if result is None:
+        block = np.array([_moments_from_files(datadir, d, horizons) for d in dates]).reshape(len(dates), len(horizons), _lib.MIX_STRIDE)
+        return dates, _lib.unpack_mixture_moments(block)
+    m = getattr(result, "moments", None)
+    if m is None:
+        raise ValueError("result carries no mixture moments (estimatewindows(..., moment_horizons=hs))")
+    if m.horizons != horizons:
+        raise ValueError("result was computed for other horizons")
+    by_date = {str(enddate(o)): w for w, o in enumerate(result.opts)}
+    for d in dates:
+        if d not in by_date:
+            raise ValueError("no window ends on %s" % d)
+    idx = [by_date[d] for d in dates]
+    return dates, {name: getattr(m, name)[idx] for name in _lib.MIX_FIELDS}
+
+
+def _summary_rows(datadir, stem):
+    """`<stem>_summary.csv` of runaggregate: (header, dates, cells (n_dates, n_columns))."""
+    header, rows = _read_csv(os.path.join(datadir, stem + "_summary.csv"))
+    return header, [r[0] for r in rows], np.array([[float(x) for x in r[1:]] for r in rows])
+
+
+def calcskewness(datadir, date=None):
+    """code/skewness.jl:22-43 in closed form.  Upstream builds the mixture sum_k p_k N(mu_k, sqrt(var_k)) from the row of the
+    latest date in `filtered_means_`, `filtered_variances_` and `filtered_state_probs_summary.csv` (p normalised to sum 1, :33),
+    draws 10 000 000 variates and averages ((x - mean(f)) / std(f))^3; that average estimates
+    sum_k p_k e_k (e_k^2 + 3 var_k) / std^3, e_k = mu_k - mean, which is returned here.  date: another row's date (default: the
+    latest, as upstream).  Returns (date, mean, std, skewness)."""
+    _, dates, mu = _summary_rows(datadir, "filtered_means")
+    _, dv, var = _summary_rows(datadir, "filtered_variances")
+    _, dp, p = _summary_rows(datadir, "filtered_state_probs")
+    date = max(dates) if date is None else str(date)
+    mu, var, p = mu[dates.index(date)], var[dv.index(date)], p[dp.index(date)]
+    p = p / p.sum()
+    mean = float(np.dot(p, mu))
+    e = mu - mean
+    v = float(np.dot(p, e * e + var))
+    return date, mean, math.sqrt(v), float(np.dot(p, e * (e * e + 3.0 * var))) / (v * math.sqrt(v))
+
+
+def altforecasts(datadir, horizon=12):
+    """code/alt_forecasts.jl:23-38: per row of the summary files the plug-in forecast `forecast_post` = dot(pi' * A^12, mu) from
+    the posterior means of `filtered_means_`, `filtered_state_probs_` and `filtered_trans_probs_summary.csv` -- A is
+    reshape(row, K, K), column-major, whatever the header calls the columns (:33) -- beside `forecast_proper`, the
+    `forecast_12_mean` column of `forecasts_summary.csv` (the draw mean of the forecast), row by row as upstream pairs them.
+    Returns (dates, forecast_post, forecast_proper)."""
+    _, dates, mu = _summary_rows(datadir, "filtered_means")
+    _, _, pis = _summary_rows(datadir, "filtered_state_probs")
+    _, _, trans = _summary_rows(datadir, "filtered_trans_probs")
+    hf, _, fc = _summary_rows(datadir, "forecasts")
+    n, K = mu.shape
+    A = trans.reshape(n, K, K).transpose(0, 2, 1)                                           # A[r, i, j] = row[i + K j]
+    w = pis.copy()
+    for _ in range(int(horizon)):
+        nw = w[:, 0, None] * A[:, 0, :]
+        for i in range(1, K):
+            nw = nw + w[:, i, None] * A[:, i, :]
+        w = nw
+    post = w[:, 0] * mu[:, 0]
+    for k in range(1, K):
+        post = post + w[:, k] * mu[:, k]
+    return dates, post, fc[:, hf.index("forecast_%d_mean" % int(horizon)) - 1]
+
+
+def write_forecast_comparison(path, dates, forecast_post, forecast_proper):
+    """alt_forecasts.jl:28,39: `date,forecast_post,forecast_proper`, one row per end date, float text as in the other files (_fmt)."""
+    rows = [[str(d), _fmt(a), _fmt(b)] for d, a, b in zip(dates, forecast_post, forecast_proper)]
+    _write_csv(path, ["date", "forecast_post", "forecast_proper"], rows)
     return path

@@ -17,7 +17,9 @@
 # through the C ABI and the Python host layer): checkpoint/resume, the smoothed-probability output, the correlation
 # workbook writer (calccorr's matrices themselves: estimatewindows(...; corr=true)).  calccdfs / predictive_cdf: the
 # predictive CDFs of code/hassan_cdfs/calc_cdfs.jl from the draws, on the device (hmcg_predictive_cdf).  calcbias /
-# bias_moments: uncerbias and totalbias of code/hassan_cdfs/bias_calcs.jl likewise (hmcg_bias_moments).  runaggregate /
+# bias_moments: uncerbias and totalbias of code/hassan_cdfs/bias_calcs.jl likewise (hmcg_bias_moments).  calcmoments /
+# mixture_moments: what code/skewness.jl and code/alt_forecasts.jl ask of the summary rows, asked of the draws
+# (hmcg_mixture_moments); calcskewness / altforecasts: the two scripts themselves, in closed form.  runaggregate /
 # calcdispersion of the reference work unchanged on the files written here (same names, columns and float text).
 #
 # Reference lines mirrored: estopt src/Hmc.jl:17-73, accessors :85-107, makedate :573-582,
@@ -129,6 +131,20 @@ struct hmcg_bias                      # include/hmcg.h: uncertainty-bias moments
     reserved::Int32
 end
 bias_stride(K::Integer) = 2 + 2K + 4K^2     # HMCG_BIAS_STRIDE
+
+const HMCG_MIX_ROUND5 = Int32(1)
+const HMCG_MIX_STRIDE = 8
+struct hmcg_mixmom                    # include/hmcg.h: predictive mixture moments of the draws (skewness.jl, alt_forecasts.jl)
+    struct_size::Int32
+    W::Int32
+    K::Int32
+    device::Int32
+    nd::Int64
+    nd_ld::Int64
+    n_h::Int32
+    flags::Int32
+    horizons::NTuple{HMCG_MAXH,Int32}
+end
 
 last_error() = unsafe_string(ccall((:hmcg_last_error, LIBHMCG), Cstring, ()))
 device_count() = Int(ccall((:hmcg_device_count, LIBHMCG), Cint, ()))
@@ -402,6 +418,124 @@ end
 estimatemodel(opt::estopt; device::Integer=0) = estimatewindows([opt]; device=device)[1][1]
 
 # One window on the signal path: n_samples chained noise samples of (burnin + nrun) sweeps (src/Hmc.jl:889-912).
+# ---- predictive mixture moments (code/skewness.jl, code/alt_forecasts.jl) ----------------------------------------------
+_mixmom(W, K, nd, ld, horizons, device, round5) =
+    hmcg_mixmom(Int32(sizeof(hmcg_mixmom)), Int32(W), Int32(K), Int32(device), Int64(nd), Int64(ld), Int32(length(horizons)),
+                round5 ? HMCG_MIX_ROUND5 : Int32(0), ntuple(i -> i <= length(horizons) ? Int32(horizons[i]) : Int32(0), HMCG_MAXH))
+
+"""
+    mixture_moments(μ, σ, πe, A; horizons=[0], device=0, round5=true) -> Array (8, n_h, W)
+
+hmcg_mixture_moments over host draw arrays in the layouts estimatewindows fills -- μ, σ, πe (nrun, K, W), A (nrun, K, K, W),
+`nothing` when every horizon is 0: per window and horizon the moments of the predictive law Σ_k ω[k] N(μ[k], σ[k]), ω = πe A^h,
+pooled over the draws in closed form.  Rows: mean, variance, skewness, excess kurtosis, mean within-draw variance, variance
+over the draws of the per-draw mean, mean per-draw skewness, mean weight.
+"""
+function mixture_moments(μ::Array{Float64,3}, σ::Array{Float64,3}, πe::Array{Float64,3}, A; horizons=[0], device::Integer=0,
+                         round5::Bool=true)
+    nrun, K, W = size(μ)
+    out = Array{Float64}(undef, HMCG_MIX_STRIDE, length(horizons), W)
+    pa = A === nothing ? Ptr{Float64}(C_NULL) : pointer(A)
+    rc = GC.@preserve μ σ πe A out ccall((:hmcg_mixture_moments, LIBHMCG), Cint,
+        (Ref{hmcg_mixmom}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}),
+        _mixmom(W, K, nrun, nrun, horizons, device, round5), μ, σ, πe, pa, out, C_NULL)
+    rc == 0 || error("libhmcgibbs rc=$rc: $(last_error())")
+    return out
+end
+
+"""
+    mixture_moments_device(W, K, nd, ld, dμ, dσ, dπe, dA, dout; horizons=[0], device=0, round5=true, stream=C_NULL)
+
+hmcg_mixture_moments_device over device pointers (dA = C_NULL when every horizon is 0); dout holds W * n_h * 8 doubles;
+enqueued on `stream` (C_NULL: the library's own) and not waited for.
+"""
+function mixture_moments_device(W, K, nd, ld, dμ::Ptr{Float64}, dσ::Ptr{Float64}, dπe::Ptr{Float64}, dA::Ptr{Float64},
+                                dout::Ptr{Float64}; horizons=[0], device::Integer=0, round5::Bool=true, stream::Ptr{Cvoid}=C_NULL)
+    rc = ccall((:hmcg_mixture_moments_device, LIBHMCG), Cint,
+               (Ref{hmcg_mixmom}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}, Ptr{Cvoid}),
+               _mixmom(W, K, nd, ld, horizons, device, round5), dμ, dσ, dπe, dA, dout, stream, C_NULL)
+    rc == 0 || error("libhmcgibbs rc=$rc: $(last_error())")
+    return nothing
+end
+
+"""
+    calcmoments(opts; horizons=[0], device=0) -> (dates, moments (8, n_h, W))
+
+skewness.jl's and alt_forecasts.jl's question asked of the draws: estimates the windows and takes the moments of the predictive
+mixture from their draws on the device.
+"""
+function calcmoments(opts::Vector{estopt}; horizons=[0], device::Integer=0)
+    samples, _, _ = estimatewindows(opts; device=device)
+    cat3(f) = cat((f(s) for s in samples)...; dims=3)
+    μ, σ, πe = cat3(s -> s.μ), cat3(s -> s.σ), cat3(s -> s.πb[:, 1, :])
+    A = any(h -> h > 0, horizons) ? cat((s.A for s in samples)...; dims=4) : nothing
+    return [enddate(o) for o in opts], mixture_moments(μ, σ, πe, A; horizons=horizons, device=device)
+end
+
+function _summary_rows(datadir, stem)
+    lines = readlines(joinpath(datadir, stem * "_summary.csv"))
+    cells = [split(l, ',') for l in lines[2:end]]
+    return split(lines[1], ','), [String(c[1]) for c in cells], [parse(Float64, c[j]) for c in cells, j in 2:length(cells[1])]
+end
+
+"""
+    calcskewness(datadir; date=nothing) -> (date, mean, std, skewness)
+
+code/skewness.jl:22-43 in closed form: the mixture Σ_k p_k N(μ_k, sqrt(var_k)) of the latest date's row (or `date`'s) of the
+three `*_summary.csv` files, p normalised (:33); Σ_k p_k e_k (e_k² + 3 var_k) / std³ with e_k = μ_k - mean is what upstream's
+10 000 000 variates estimate.
+"""
+function calcskewness(datadir; date=nothing)
+    _, dates, μ = _summary_rows(datadir, "filtered_means")
+    _, dv, v = _summary_rows(datadir, "filtered_variances")
+    _, dp, p = _summary_rows(datadir, "filtered_state_probs")
+    d = date === nothing ? maximum(dates) : string(date)
+    m, vr, pr = μ[findfirst(==(d), dates), :], v[findfirst(==(d), dv), :], p[findfirst(==(d), dp), :]
+    pr = pr ./ sum(pr)
+    mean = sum(pr .* m)
+    e = m .- mean
+    var = sum(pr .* (e .^ 2 .+ vr))
+    return d, mean, sqrt(var), sum(pr .* e .* (e .^ 2 .+ 3 .* vr)) / (var * sqrt(var))
+end
+
+"""
+    altforecasts(datadir; horizon=12) -> (dates, forecast_post, forecast_proper)
+
+code/alt_forecasts.jl:23-38: per summary row the plug-in forecast dot(π' * A^12, μ), A = reshape(row, K, K) (column-major,
+whatever the header calls the columns), beside the `forecast_12_mean` column of forecasts_summary.csv.
+"""
+function altforecasts(datadir; horizon::Integer=12)
+    _, dates, μ = _summary_rows(datadir, "filtered_means")
+    _, _, π = _summary_rows(datadir, "filtered_state_probs")
+    _, _, tr = _summary_rows(datadir, "filtered_trans_probs")
+    hf, _, fc = _summary_rows(datadir, "forecasts")
+    K = size(μ, 2)
+    post = map(1:size(μ, 1)) do i
+        A = reshape(tr[i, :], K, K)
+        w = π[i, :]'
+        for _ in 1:horizon
+            w = w * A
+        end
+        sum(w' .* μ[i, :])
+    end
+    return dates, post, fc[:, findfirst(==("forecast_$(horizon)_mean"), hf) - 1]
+end
+
+"""
+    write_forecast_comparison(path, dates, forecast_post, forecast_proper)
+
+alt_forecasts.jl:28,39: `date,forecast_post,forecast_proper`, float text as in the other files.
+"""
+function write_forecast_comparison(path, dates, forecast_post, forecast_proper)
+    open(path, "w") do io
+        println(io, "date,forecast_post,forecast_proper")
+        for (d, a, b) in zip(dates, forecast_post, forecast_proper)
+            println(io, d, ",", _fmt(Float64(a)), ",", _fmt(Float64(b)))
+        end
+    end
+    return path
+end
+
 function _signal_call(opt::estopt, burnin, nrun, n_samples, σsignal, κ, α, ν, devh::Vector{Int}, blend::Integer, endpos; device::Integer=0)
     Y = makey(opt); T = Int32[length(Y)]; K = opt.D; H = length(opt.horizons); nd = n_samples * nrun
     hz = ntuple(i -> i <= H ? Int32(devh[i]) : Int32(0), HMCG_MAXH)

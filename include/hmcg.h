@@ -28,6 +28,12 @@
  *   hmcg_bias_moments[_device]     code/hassan_cdfs/bias_calcs.jl:40-53 (calcbias): per end date the mean and covariance over
  *                                  the draws of [pi_end * A^12 | mu] and the two numbers it reduces them to (uncerbias,
  *                                  totalbias), taken from the draw arrays instead of the four per-draw CSV files it reads back.
+ *   hmcg_mixture_moments[_device]  code/skewness.jl:31-43 and code/alt_forecasts.jl:30-35, asked of the draws instead of the
+ *                                  summary rows: mean, variance, skewness and excess kurtosis of the predictive law
+ *                                  sum_k omega_k N(mu_k, sig2_k), omega = pi_end * A^h, pooled over the draws in closed form
+ *                                  (skewness.jl estimates one third moment from 10 000 000 variates of the plug-in mixture;
+ *                                  alt_forecasts.jl sets the plug-in mean beside the draw mean), and what a plug-in hides:
+ *                                  the within- and between-draw shares of the variance and the mean per-draw skewness.
  *
  * Conventions: plain C structs, fixed-width ints, no C++ types or exceptions cross
  * the boundary.  Return 0 on success, negative on API misuse (HMCG_E_*), positive
@@ -324,6 +330,50 @@ int hmcg_bias_moments_device(const hmcg_bias* p, const double* dmu, const double
  * kernel of the one before. */
 int hmcg_bias_moments(const hmcg_bias* p, const double* mu, const double* pi_end, const double* A, const double* fcast, double* out,
                       hmcg_timing* timing);
+
+/* ---- predictive mixture moments of the draws (skewness.jl, alt_forecasts.jl) -------------------------------------------------
+ * The predictive law of window w at horizon h_j is the mixture of all nd * K components omega_{d,k} N(mu_{d,k}, sig2_{d,k}),
+ * omega_d = pi_end_d * A_d^h_j (h_j successive row-vector x matrix products, k ascending in every dot product: the same bits as
+ * the weights of hmcg_predictive_cdf and hmcg_bias_moments; horizons may come unsorted and repeated, equal horizons give equal
+ * bits).  Its moments are draw sums of per-draw closed forms.  With s_d = sum_k omega_k, delta_k = mu_k - c, v_k = sig2_k and
+ * the pivot c = the mixture mean of the window's draw 0 at that horizon:
+ *   P0 = sum_d s_d                                    P1 = sum_d sum_k omega delta
+ *   P2 = sum sum omega (delta^2 + v)                  P3 = sum sum omega delta (delta^2 + 3 v)
+ *   P4 = sum sum omega (delta^4 + 6 delta^2 v + 3 v^2)
+ * and per draw, normalised by s_d as skewness.jl:33 normalises p:  a_d = (sum_k omega delta) / s_d,  e_k = delta_k - a_d,
+ *   var_d = sum omega (e^2 + v) / s_d,  skew_d = [sum omega e (e^2 + 3 v) / s_d] / (var_d sqrt(var_d)),  b_d = a_d - a_0:
+ *   Q1 = sum b_d,  Q2 = sum b_d^2,  VW = sum var_d,  SK = sum skew_d.
+ * out[w][j] holds HMCG_MIX_STRIDE doubles, m_i = P_i / P0:
+ *   0 mean c + m1                        1 variance m2 - m1^2
+ *   2 skewness (m3 - 3 m1 m2 + 2 m1^3) / variance^1.5
+ *   3 excess kurtosis (m4 - 4 m1 m3 + 6 m1^2 m2 - 3 m1^4) / variance^2 - 3
+ *   4 mean within-draw variance VW / nd  5 variance over the draws of the per-draw mean, Q2 / nd - (Q1 / nd)^2 (divisor nd)
+ *   6 mean per-draw skewness SK / nd     7 mean weight P0 / nd
+ * Draw arrays: the layouts and the nd_ld rule of the predictive entries.  HMCG_MIX_ROUND5: every input is first rounded as a CSV
+ * cell is (as HMCG_PRED_ROUND5).  Nothing is special-cased: NaN propagates, a zero variance is v = 0, a zero pooled variance
+ * gives NaN skewness and kurtosis (0/0).
+ * Deterministic: draws are reduced in slabs of 1024 (the predictive entries' cut), inside a slab in an order that depends on
+ * the draw index alone, the slabs in slab order, no floating-point atomics: bit-identical from run to run, from both entries
+ * and for every chunking of the host entry's upload (HMCG_CHUNK_DRAWS under HMCG_DIAG=1).
+ * Misuse (HMCG_E_BADARG, checked before any HIP call): struct_size, K outside 2..HMCG_MAXK, n_h outside 1..HMCG_MAXH, a horizon
+ * outside 0..HMCG_PRED_MAXH, W < 1, nd < 1, nd_ld < nd, a NULL mu / sig2 / pi_end / out, NULL A with a horizon > 0. */
+#define HMCG_MIX_ROUND5 1
+#define HMCG_MIX_STRIDE 8
+typedef struct hmcg_mixmom {
+    int32_t struct_size, W, K, device;
+    int64_t nd, nd_ld;                 /* draws per window; leading dimension of the draw arrays (>= nd) */
+    int32_t n_h, flags;                /* horizons 1..HMCG_MAXH */
+    int32_t horizons[HMCG_MAXH];       /* 0 = the end date itself (skewness.jl); alt_forecasts.jl uses 12 */
+} hmcg_mixmom;
+/* Device entry: every data pointer is HBM-resident on p->device; enqueued on `stream` (NULL: the library's own) behind the
+ * library's earlier work there; returns after enqueueing unless `timing` is given (kernel_ms: HIP events around the kernels). */
+int hmcg_mixture_moments_device(const hmcg_mixmom* p, const double* dmu, const double* dsig2, const double* dpi_end,
+                                const double* dA /* NULL iff every horizon is 0 */, double* dout /* [W][n_h][HMCG_MIX_STRIDE] */,
+                                void* stream, hmcg_timing* timing);
+/* Host entry (blocking): uploads the draws in chunks of whole slabs through pinned staging, the copy of one chunk beside the
+ * kernel of the one before. */
+int hmcg_mixture_moments(const hmcg_mixmom* p, const double* mu, const double* sig2, const double* pi_end, const double* A,
+                         double* out, hmcg_timing* timing);
 
 /* ---- per-draw CSV output (host code, no GPU): basicsave / saveresults, src/Hmc.jl:707-748 ------------------------------
  * The five per-window files `filtered_means_<date>.csv`, `filtered_variances_<date>.csv`, `filtered_state_probs_<date>.csv`,
