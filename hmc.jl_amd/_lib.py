@@ -27,7 +27,7 @@ EXPORTS = ("hmcg_version", "hmcg_device_count", "hmcg_last_error", "hmcg_shutdow
            "hmcg_estimate_batch", "hmcg_estimate_batch_device", "hmcg_estimate_batch_multi",
            "hmcg_save_results_csv", "hmcg_write_table_csv", "hmcg_format_float",
            "hmcg_predictive_cdf", "hmcg_predictive_cdf_device", "hmcg_bias_moments", "hmcg_bias_moments_device",
-           "hmcg_mixture_moments", "hmcg_mixture_moments_device")
+           "hmcg_mixture_moments", "hmcg_mixture_moments_device", "hmcg_chain_density", "hmcg_chain_density_device")
 HMCG_MAXDEV = 16
 PRED_ROUND5 = 1
 HMCG_MAXGRID = 4096
@@ -37,6 +37,10 @@ BIAS_ROUND5 = 1
 MIX_ROUND5 = 1
 MIX_STRIDE = 8                  # HMCG_MIX_STRIDE: doubles per (window, horizon) of the mixture-moment output
 MIX_FIELDS = ("mean", "variance", "skewness", "kurtosis", "within", "between", "draw_skewness", "weight")
+DENS_ROUND5 = 1
+DENS_MAXBINS = 512              # HMCG_DENS_MAXBINS
+DENS_MAXTRACE = 65536           # HMCG_DENS_MAXTRACE
+DENS_FIELDS = ("counts", "below", "above", "nan", "range", "mean", "variance", "trace")
 
 
 def bias_stride(K):
@@ -84,6 +88,12 @@ class Bias(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("W", C.c_int32), ("K", C.c_int32), ("device", C.c_int32),
                 ("nd", C.c_int64), ("nd_ld", C.c_int64), ("horizon", C.c_int32), ("H", C.c_int32),
                 ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+class Density(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("device", C.c_int32),
+                ("nd", C.c_int64), ("nd_ld", C.c_int64), ("B", C.c_int32), ("n_cuts", C.c_int32),
+                ("cuts", C.c_int64 * HMCG_MAXH), ("trace_len", C.c_int32), ("flags", C.c_int32), ("trace_stride", C.c_int64)]
 
 
 class MixMom(C.Structure):
@@ -156,6 +166,8 @@ def load():
         L.hmcg_bias_moments_device.restype = C.c_int
         L.hmcg_mixture_moments.restype = C.c_int
         L.hmcg_mixture_moments_device.restype = C.c_int
+        L.hmcg_chain_density.restype = C.c_int
+        L.hmcg_chain_density_device.restype = C.c_int
         _LIB = L
     return _LIB
 
@@ -569,6 +581,76 @@ def mixture_moments_device(mix, dmu, dsig2, dpi_end, dA, dout, stream=None, time
 
     _check(load().hmcg_mixture_moments_device(C.byref(mix), vp(dmu), vp(dsig2), vp(dpi_end), vp(dA), vp(dout), vp(stream),
                                               C.byref(tm) if timed else None))
+    return tm
+
+
+def make_density(W, Cn, nd, nd_ld, cuts=None, bins=64, trace=(0, 1), device=0, round5=True):
+    """hmcg_density of a call over a draw array of Cn columns per window.  cuts: ascending prefix lengths (None: the whole
+    chain, (nd,)); trace = (length, stride) of the running mean.  More than HMCG_MAXH cuts raise here; every other rule is the
+    library's (HMCG_E_BADARG)."""
+    cuts = (int(nd),) if cuts is None else tuple(int(c) for c in cuts)
+    if len(cuts) > HMCG_MAXH:
+        raise ValueError("at most %d cuts" % HMCG_MAXH)
+    p = Density()
+    p.struct_size = C.sizeof(Density)
+    p.W, p.C, p.device, p.nd, p.nd_ld, p.B, p.n_cuts = int(W), int(Cn), int(device), int(nd), int(nd_ld), int(bins), len(cuts)
+    for i, c in enumerate(cuts):
+        p.cuts[i] = c
+    p.trace_len, p.trace_stride = int(trace[0]), int(trace[1])
+    p.flags = DENS_ROUND5 if round5 else 0
+    return p
+
+
+def unpack_chain_density(range_, counts, stats, trace):
+    """The four output blocks of hmcg_chain_density -- range (W, C, 2), counts (W, C, n_cuts, B + 3), stats (W, C, n_cuts, 2),
+    trace (W, C, trace_len) -- as a dict: counts (W, C, n_cuts, B) int64 bins of the prefix d < cuts[j], below / above / nan
+    (W, C, n_cuts) the draws under lo, over hi and NaN, range (W, C, 2) = (lo, hi), mean / variance (W, C, n_cuts) of the prefix
+    (divisor n - 1), trace (W, C, trace_len) the running mean."""
+    counts, stats = np.asarray(counts), np.asarray(stats)
+    B = counts.shape[3] - 3
+    return {"counts": counts[..., :B].copy(), "below": counts[..., B].copy(), "above": counts[..., B + 1].copy(),
+            "nan": counts[..., B + 2].copy(), "range": np.asarray(range_).copy(), "mean": stats[..., 0].copy(),
+            "variance": stats[..., 1].copy(), "trace": np.asarray(trace).copy()}
+
+
+def chain_density(x, cuts=None, bins=64, lo_hi=None, trace=(0, 1), nd=None, device=0, round5=True, timing=None):
+    """hmcg_chain_density over ONE host (numpy) draw array in a C-ABI layout with the draw index last -- mu / sig2 / pi_end
+    (W, K, nd), A (W, K, K, nd), fcast (W, 2H, nd); every axis between the first and the last counts as columns -- over its
+    first nd draws (default: all).  Per window and column: binned counts of the nested prefixes d < cuts[j] on bins equal
+    widths between lo and hi (lo_hi (W, C, 2), default: the range of the finite draws), mean and variance of each prefix, and
+    the running mean at (i + 1) * trace[1] draws, i < trace[0] (plots/mcplots.jl's plotchain and plotchainmean up to the
+    drawing).  round5 (default): every value is first rounded to 5 digits, as the cells of the per-draw CSV files are.
+    Returns the dict of unpack_chain_density, the column axis flattened.  timing: a Timing to fill."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    W, ld = x.shape[0], x.shape[-1]
+    Cn = int(np.prod(x.shape[1:-1], dtype=np.int64))
+    nd = ld if nd is None else int(nd)
+    p = make_density(W, Cn, nd, ld, cuts, bins, trace, device, round5)
+    if lo_hi is not None:
+        lo_hi = np.ascontiguousarray(lo_hi, dtype=np.float64)
+        if lo_hi.shape != (W, Cn, 2):
+            raise ValueError("lo_hi must have the shape (W, C, 2)")
+    nc, B, tl = p.n_cuts, max(int(bins), 0), max(int(trace[0]), 0)
+    rng = np.zeros((W, Cn, 2))
+    counts = np.zeros((W, Cn, nc, B + 3), dtype=np.int64)
+    stats = np.zeros((W, Cn, nc, 2))
+    tr = np.zeros((W, Cn, tl))
+    _check(load().hmcg_chain_density(C.byref(p), _np_ptr(x), _np_ptr(lo_hi), _np_ptr(rng), _np_ptr(counts), _np_ptr(stats),
+                                     _np_ptr(tr) if tl else None, C.byref(timing) if timing is not None else None))
+    return unpack_chain_density(rng, counts, stats, tr)
+
+
+def chain_density_device(dens, dx, dlo_hi, drange, dcounts, dstats, dtrace, stream=None, timed=False):
+    """hmcg_chain_density_device over raw device pointers (ints, e.g. torch tensor.data_ptr(); dlo_hi 0 / None for the automatic
+    range, dtrace 0 / None with no trace); dens: make_density(...).  Enqueued on `stream` (None: the library's own).  Returns
+    the Timing struct when timed (the call then waits for completion), else None."""
+    tm = Timing() if timed else None
+
+    def vp(x):
+        return None if not x else C.c_void_p(int(x))
+
+    _check(load().hmcg_chain_density_device(C.byref(dens), vp(dx), vp(dlo_hi), vp(drange), vp(dcounts), vp(dstats), vp(dtrace),
+                                            vp(stream), C.byref(tm) if timed else None))
     return tm
 
 

@@ -35,6 +35,7 @@
 #include "predictive.hpp"
 #include "bias.hpp"
 #include "mixmoments.hpp"
+#include "density.hpp"
 
 namespace {
 
@@ -121,6 +122,7 @@ struct DeviceCtx {
     Arena pred;                    // device entry of the predictive CDFs: the slab sums
     Arena bias;                    // device entry of the uncertainty-bias moments: the slab sums and pivots
     Arena mix;                     // device entry of the predictive-mixture moments: the slab sums and pivots
+    Arena dens;                    // device entry of the chain densities: the piece sums, pivots and range keys
     hmcg_hostutil::ScatterPool pool;              // host entries: helpers for the scatter into the caller's arrays
 };
 DeviceCtx g_ctx[HMCG_MAXDEV];
@@ -220,6 +222,7 @@ void destroy_context(DeviceCtx& c)
     c.pred.release();
     c.bias.release();
     c.mix.release();
+    c.dens.release();
     c.pool.stop();
     c.stream = c.copy = nullptr;
     c.ready = false;
@@ -1330,6 +1333,164 @@ int mix_host(DeviceCtx& c, const hmcg_mixmom* p, const double* mu, const double*
     return 0;
 }
 
+// ---- chain densities and running means of the draws (density.hip; argument rules, pieces and column groups: density_plan.hpp;
+// chunk cut: predictive_plan.hpp) -------------------------------------------------------------------------------------------------
+
+void fill_dens_timing(hmcg_timing* t, const hmcg_density* p, const DeviceCtx& c, double kernel_ms, int launches, double call_ms)
+{
+    memset(t, 0, sizeof *t);
+    t->kernel_ms = kernel_ms; t->launches = launches; t->call_ms = call_ms;
+    t->device = c.device; t->windows = p->W; t->buckets = 1; t->threads_per_window = 256;
+}
+
+hmcg_host::DensArgs dens_args(const hmcg_density* p)
+{
+    hmcg_host::DensArgs a{};
+    a.W = p->W; a.C = p->C; a.B = p->B; a.n_cuts = p->n_cuts; a.trace_len = p->trace_len; a.trace_stride = p->trace_stride;
+    for (int j = 0; j < HMCG_MAXH; ++j) a.cuts[j] = j < p->n_cuts ? p->cuts[j] : 0;
+    a.nd = p->nd; a.round5 = (p->flags & HMCG_DENS_ROUND5) != 0;
+    return a;
+}
+
+// Caller holds c.mu and has made c.device current.  The piece sums live in a context-owned arena (as the slab sums of the siblings do).
+int dens_device(DeviceCtx& c, const hmcg_density* p, const double* dx, const double* dlo_hi, double* drange, int64_t* dcounts,
+                double* dstats, double* dtrace, hipStream_t stream, hmcg_timing* timing)
+{
+    int rc = grow_shared(c, c.dens, dens_work_bytes(p->W, p->C, p->nd, p->cuts, p->n_cuts));
+    if (rc) return rc;
+    HIP_TRY(hipStreamWaitEvent(stream, c.ev_scr, 0));
+    if (timing) HIP_TRY(hipEventRecord(c.ev0, stream));
+    hmcg_host::DensArgs a = dens_args(p);
+    a.x = dx; a.work = c.dens.base; a.range = drange; a.counts = reinterpret_cast<unsigned long long*>(dcounts);
+    a.stats = dstats; a.trace = dtrace; a.d_origin = 0; a.n = p->nd; a.nd_ld = p->nd_ld;
+    HIP_TRY(launch_density_clear(a, stream));
+    if (!dlo_hi) HIP_TRY(launch_density_range(a, stream));
+    HIP_TRY(launch_density_resolve(a, dlo_hi, stream));
+    HIP_TRY(launch_density_accumulate(a, stream));
+    HIP_TRY(launch_density_finalize(a, stream));
+    HIP_TRY(hipEventRecord(c.ev_scr, stream));
+    if (timing) {
+        HIP_TRY(hipEventRecord(c.ev1, stream));
+        HIP_TRY(hipEventSynchronize(c.ev1));
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, c.ev0, c.ev1));
+        fill_dens_timing(timing, p, c, ms, dlo_hi ? 3 : 4, 0.0);
+    }
+    return 0;
+}
+
+// Host entry on one device, as mix_host: whole-slab chunks packed window by window, column by column into pinned staging
+// (leading dimension = the chunk's draws), RING buffers deep, the copy of chunk c + 1 beside the kernel of chunk c.  Without
+// lo_hi the bins need the range of ALL draws first: one pass of uploads for the range kernel, a second one for the counts and
+// sums (chunks that lie wholly beyond the last cut and the running mean are not uploaded again); with lo_hi the second pass alone.
+int dens_host(DeviceCtx& c, const hmcg_density* p, const double* x, const double* lo_hi, double* range, int64_t* counts, double* stats,
+              double* trace, hmcg_timing* timing)
+{
+    const auto t_call = std::chrono::steady_clock::now();
+    const int W = p->W, C = p->C;
+    long long cap = 0;
+    if (const char* cenv = diag_env("HMCG_CHUNK_DRAWS")) cap = atoll(cenv);
+    const long long cdraws = pred_chunk_draws(p->nd, W, C, cap);
+    const std::vector<PredChunk> chunks = pred_chunks(p->nd, cdraws);
+    const size_t wc = (size_t)W * (size_t)C;
+    const size_t n_range = wc * 2, n_counts = wc * (size_t)p->n_cuts * (size_t)(p->B + DENS_SLOTS), n_stats = wc * (size_t)p->n_cuts * 2,
+                 n_trace = wc * (size_t)p->trace_len;
+    auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
+    const size_t b_range = up(8 * n_range), b_counts = up(8 * n_counts), b_stats = up(8 * n_stats), b_trace = up(8 * n_trace);
+    const size_t b_out = b_range + b_counts + b_stats + b_trace;
+    const size_t b_lohi = up(8 * n_range);
+    const size_t b_work = up(dens_work_bytes(W, C, p->nd, p->cuts, p->n_cuts));
+    const size_t b_chunk = up(sizeof(double) * wc * (size_t)cdraws);
+    const int nbuf = (int)std::min<size_t>(RING, chunks.size());
+    const size_t need_dev = b_out + b_lohi + b_work + b_chunk * (size_t)nbuf, need_pin = b_out + b_lohi + b_chunk * (size_t)nbuf;
+    if (c.dev.ensure(need_dev) || c.pin.ensure(need_pin)) {
+        set_err("workspace allocation failed (%zu B device, %zu B pinned)", need_dev, need_pin);
+        return HMCG_E_NOMEM;
+    }
+    char* dout = c.dev.base;
+    double* dlohi = reinterpret_cast<double*>(c.dev.base + b_out);
+    char* dwork = c.dev.base + b_out + b_lohi;
+    char* dchunk = dwork + b_work;
+    char* pout = c.pin.base;
+    double* plohi = reinterpret_cast<double*>(c.pin.base + b_out);
+    char* pchunk = c.pin.base + b_out + b_lohi;
+
+    hmcg_host::DensArgs a = dens_args(p);
+    a.work = dwork;
+    a.range = reinterpret_cast<double*>(dout);
+    a.counts = reinterpret_cast<unsigned long long*>(dout + b_range);
+    a.stats = reinterpret_cast<double*>(dout + b_range + b_counts);
+    a.trace = reinterpret_cast<double*>(dout + b_range + b_counts + b_stats);
+    // draws a second-pass chunk must reach below to matter: the last cut and the end of the running mean
+    const long long reach = std::max<long long>(p->cuts[p->n_cuts - 1], (long long)p->trace_len * p->trace_stride);
+
+    struct Events {
+        std::vector<hipEvent_t> ev;
+        ~Events() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+    } tev;                                       // two per chunk and pass, around its kernel (created only when timing is asked for)
+    size_t n_timed = 0;
+    if (timing) {
+        tev.ev.assign(4 * chunks.size(), nullptr);
+        for (hipEvent_t& e : tev.ev) HIP_TRY(hipEventCreate(&e));
+    }
+    int launches = 0;
+    // the calls below must be enqueued on c.stream behind each other: clear, [range per chunk], resolve, accumulate per chunk, finalize
+    a.x = reinterpret_cast<double*>(dchunk); a.d_origin = 0; a.n = chunks[0].n; a.nd_ld = chunks[0].n;
+    HIP_TRY(launch_density_clear(a, c.stream));
+    size_t gi = 0;                               // chunks uploaded so far, over both passes: the ring position
+    for (int pass = lo_hi ? 1 : 0; pass < 2; ++pass) {
+        if (pass == 1) {
+            if (lo_hi) {
+                memcpy(plohi, lo_hi, 8 * n_range);
+                HIP_TRY(hipMemcpyAsync(dlohi, plohi, 8 * n_range, hipMemcpyHostToDevice, c.stream));
+            }
+            HIP_TRY(launch_density_resolve(a, lo_hi ? dlohi : nullptr, c.stream));
+            ++launches;
+        }
+        for (size_t ci = 0; ci < chunks.size(); ++ci) {
+            const PredChunk& ch = chunks[ci];
+            if (pass == 1 && ch.d0 >= reach) break;
+            const int b = (int)(gi % (size_t)nbuf);
+            if (gi >= (size_t)nbuf) HIP_TRY(hipEventSynchronize(c.evk[b]));      // the kernel that read this buffer pair is done
+            ++gi;
+            double* pb = reinterpret_cast<double*>(pchunk + b_chunk * (size_t)b);
+            double* db = reinterpret_cast<double*>(dchunk + b_chunk * (size_t)b);
+            const size_t n = (size_t)ch.n;
+            for (size_t q = 0; q < wc; ++q) memcpy(pb + q * n, x + q * (size_t)p->nd_ld + (size_t)ch.d0, sizeof(double) * n);
+            HIP_TRY(hipMemcpyAsync(db, pb, sizeof(double) * wc * n, hipMemcpyHostToDevice, c.copy));
+            HIP_TRY(hipEventRecord(c.evc[b], c.copy));
+            HIP_TRY(hipStreamWaitEvent(c.stream, c.evc[b], 0));
+            a.x = db; a.d_origin = ch.d0; a.n = ch.n; a.nd_ld = ch.n;
+            if (timing) HIP_TRY(hipEventRecord(tev.ev[2 * n_timed], c.stream));
+            if (pass == 0) HIP_TRY(launch_density_range(a, c.stream));
+            else HIP_TRY(launch_density_accumulate(a, c.stream));
+            if (timing) HIP_TRY(hipEventRecord(tev.ev[2 * n_timed + 1], c.stream));
+            ++n_timed;
+            ++launches;
+            HIP_TRY(hipEventRecord(c.evk[b], c.stream));
+        }
+    }
+    HIP_TRY(launch_density_finalize(a, c.stream));
+    ++launches;
+    HIP_TRY(hipMemcpyAsync(pout, dout, b_out, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    memcpy(range, pout, 8 * n_range);
+    memcpy(counts, pout + b_range, 8 * n_counts);
+    memcpy(stats, pout + b_range + b_counts, 8 * n_stats);
+    if (n_trace) memcpy(trace, pout + b_range + b_counts + b_stats, 8 * n_trace);
+    if (timing) {
+        double kernel_ms = 0.0;
+        for (size_t i = 0; i < n_timed; ++i) {
+            float ms = 0.f;
+            HIP_TRY(hipEventElapsedTime(&ms, tev.ev[2 * i], tev.ev[2 * i + 1]));
+            kernel_ms += ms;
+        }
+        const double call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+        fill_dens_timing(timing, p, c, kernel_ms, launches, call_ms);
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1525,6 +1686,36 @@ int hmcg_mixture_moments(const hmcg_mixmom* p, const double* mu, const double* s
     std::lock_guard<std::mutex> lk(c->mu);
     HIP_TRY(hipSetDevice(c->phys));
     return mix_host(*c, p, mu, sig2, pi_end, A, out, timing);
+}
+
+int hmcg_chain_density_device(const hmcg_density* p, const double* dx, const double* dlo_hi, double* drange, int64_t* dcounts,
+                              double* dstats, double* dtrace, void* stream, hmcg_timing* timing)
+{
+    g_err[0] = 0;
+    char msg[160];
+    int rc = check_density(p, dx, dlo_hi, drange, dcounts, dstats, dtrace, false, msg, sizeof msg);
+    if (rc) { set_err("%s", msg); return rc; }
+    DeviceCtx* c = nullptr;
+    rc = get_context(p->device, &c);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->phys));
+    return dens_device(*c, p, dx, dlo_hi, drange, dcounts, dstats, dtrace, stream ? (hipStream_t)stream : c->stream, timing);
+}
+
+int hmcg_chain_density(const hmcg_density* p, const double* x, const double* lo_hi, double* range, int64_t* counts, double* stats,
+                       double* trace, hmcg_timing* timing)
+{
+    g_err[0] = 0;
+    char msg[160];
+    int rc = check_density(p, x, lo_hi, range, counts, stats, trace, true, msg, sizeof msg);
+    if (rc) { set_err("%s", msg); return rc; }
+    DeviceCtx* c = nullptr;
+    rc = get_context(p->device, &c);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->phys));
+    return dens_host(*c, p, x, lo_hi, range, counts, stats, trace, timing);
 }
 
 }  // extern "C"

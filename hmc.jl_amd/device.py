@@ -51,6 +51,7 @@ class DevicePanel:
         # extras.corr: correlations between the per-draw outputs (calccorr), needs the draws on the device
         self.corr = torch.zeros(shape["corr"], **f64) if corr else None
         self.last_timing = None
+        self._held = []                    # input tensors of enqueued library calls: kept until sync() (or a timed call) has waited
         torch.cuda.synchronize(self.dev)   # fills above ran on torch's stream; the library uses its own
 
     @staticmethod
@@ -133,6 +134,43 @@ class DevicePanel:
             self.last_timing = tm
         return out
 
+    def chain_density(self, var="mu", cuts=None, bins=64, lo_hi=None, trace=(0, 1), timed=False, round5=True):
+        """Chain densities and running means of one variable's draws from the panel's own HBM draws
+        (hmcg_chain_density_device; plots/mcplots.jl's plotchain and plotchainmean, plots/timeseriesplots.jl's plot_mean /
+        plot_var up to the drawing).  var: "mu", "sig2", "pi_end" (C = K columns), "A" (C = K * K, column i + K * j = A[i, j])
+        or "fcast" (C = 2H).  cuts: ascending prefix lengths of the chain (None: the whole chain, (nrun,)); bins equal-width
+        bins between lo and hi per window and column, lo_hi (W, C, 2) or None for the range of the finite draws;
+        trace = (length, stride) of the running mean.  Returns a dict of tensors: range (W, C, 2), counts
+        (W, C, n_cuts, bins + 3) int64 -- the bins, then below, above, nan -- stats (W, C, n_cuts, 2) = mean and variance of each
+        prefix, trace (W, C, length); _lib.unpack_chain_density names the parts of their numpy copies.  Enqueued on the library
+        stream behind `run`; with timed=True the call waits and last_timing holds the HIP-event time, otherwise call sync()
+        before reading the tensors."""
+        if var not in _lib.DRAW_KEYS:
+            raise ValueError("var must be one of %s" % (_lib.DRAW_KEYS,))
+        x = getattr(self, var)
+        if x is None:
+            raise _lib.HmcgError("chain_density needs the draws in HBM: the panel was built with keep_draws=False")
+        torch = self.torch
+        Cn = int(x.numel() // (self.W * self.nrun))
+        dens = _lib.make_density(self.W, Cn, self.nrun, self.nrun, cuts, bins, trace, self.device_index, round5)
+        f64 = dict(dtype=torch.float64, device=self.dev)
+        lh = None
+        if lo_hi is not None:
+            lh = torch.from_numpy(np.ascontiguousarray(lo_hi, dtype=np.float64).reshape(self.W, Cn, 2)).to(self.dev)     # a blocking copy
+        out = {"range": torch.empty((self.W, Cn, 2), **f64),
+               "counts": torch.empty((self.W, Cn, dens.n_cuts, max(int(bins), 0) + 3), dtype=torch.int64, device=self.dev),
+               "stats": torch.empty((self.W, Cn, dens.n_cuts, 2), **f64),
+               "trace": torch.empty((self.W, Cn, max(int(trace[0]), 0)), **f64)}
+        tm = _lib.chain_density_device(dens, x.data_ptr(), 0 if lh is None else lh.data_ptr(), out["range"].data_ptr(),
+                                       out["counts"].data_ptr(), out["stats"].data_ptr(),
+                                       out["trace"].data_ptr() if dens.trace_len > 0 else 0, None, timed)
+        if lh is not None and not timed:    # a timed call has waited; otherwise the enqueued kernels may still read it
+            self._held.append(lh)
+        if timed:
+            self.last_timing = tm
+        return out
+
     def sync(self):
         """Wait for the library stream (untimed runs are asynchronous)."""
         self.torch.cuda.synchronize(self.dev)
+        del self._held[:]

@@ -18,6 +18,8 @@ ABI.  Names, argument meaning and result layout follow the reference:
     calcskewness        code/skewness.jl:22-43 (the plug-in mixture's skewness, in closed form instead of 10 000 000 variates)
     altforecasts        code/alt_forecasts.jl:23-39 (plug-in against proper 12-month forecast; forecast_comparision.csv)
     calcmoments         both questions asked of the draws: moments of the predictive mixture (from the files or from the device)
+    calcchain           plots/mcplots.jl:24-63 and plots/timeseriesplots.jl:83-142 up to the drawing: binned chain densities over
+                        nested prefixes and the running mean (from the files or from the device); chainquantiles, chaindensity
 
 New (the reference batches by launching one SLURM task per window,
 slurmscripts/base_estimation.sh:5): `estimatewindows`, one call for many windows.
@@ -363,6 +365,28 @@ class MixtureMoments:
             setattr(self, name, parts[name])
 
 
+DENSITY_FILES = {"mu": "filtered_means", "sig2": "filtered_variances", "pi_end": "filtered_state_probs",
+                 "A": "filtered_trans_probs", "fcast": "forecasts"}
+
+
+class ChainDensity:
+    """Chain densities of one variable's draws over n windows (end dates), C columns and the nested prefixes d < cuts[j]:
+    counts (n, C, n_cuts, bins) int64 on `bins` equal-width bins between range[..., 0] and range[..., 1]; below, above, nan
+    (n, C, n_cuts) the draws under lo, over hi and NaN; mean, variance (n, C, n_cuts) of each prefix (divisor n - 1);
+    trace (n, C, trace_len) the running mean after (i + 1) * trace_stride draws; columns: the C column names of the per-draw
+    file."""
+
+    def __init__(self, var, columns, cuts, trace_stride, parts):
+        self.var, self.columns, self.cuts, self.trace_stride = var, list(columns), tuple(int(c) for c in cuts), int(trace_stride)
+        for name in _lib.DENS_FIELDS:
+            setattr(self, name, parts[name])
+        self.bins = int(self.counts.shape[3])
+
+    def rows(self, idx):
+        """The same object restricted to the windows idx."""
+        return ChainDensity(self.var, self.columns, self.cuts, self.trace_stride, {k: getattr(self, k)[idx] for k in _lib.DENS_FIELDS})
+
+
 class BatchResult:
     """Result of estimatewindows: per-window posterior summaries (+ optional draws)."""
 
@@ -377,6 +401,7 @@ class BatchResult:
         self.cdf_horizons = res.get("cdf_horizons")
         self.bias = res.get("bias")            # with bias_horizon: BiasMoments (uncerbias, totalbias, mean, cov) per window
         self.moments = res.get("moments")      # with moment_horizons: MixtureMoments, (W, n_h) arrays
+        self.density = res.get("density")      # with density_vars: {var: ChainDensity}
         self._res = res if keep_draws else None
 
     def samples(self, w):
@@ -387,7 +412,8 @@ class BatchResult:
 
 
 def estimatewindows(rawdata, dates, endIndices, startIndex=1, keep_draws=False, device=0, window_ids=None, corr=False,
-                    cdf_grid=None, cdf_horizons=(0,), bias_horizon=None, moment_horizons=None, **kwargs):
+                    cdf_grid=None, cdf_horizons=(0,), bias_horizon=None, moment_horizons=None, density_vars=None,
+                    density_cuts=None, density_bins=64, density_trace=(0, 1), **kwargs):
     """Batched estimatemodel over many expanding windows (one GPU call).
 
     Window w uses sampleRange = startIndex:endIndices[w], endIndex = endIndices[w]; the
@@ -403,9 +429,19 @@ def estimatewindows(rawdata, dates, endIndices, startIndex=1, keep_draws=False, 
     fetched and dropped likewise.
     moment_horizons: horizons (0 = the end date, as skewness.jl; 12 as alt_forecasts.jl) -> BatchResult.moments, the
     MixtureMoments of the predictive regime mixture per window and horizon, computed on the device from the 5-digit-rounded
-    draws (_lib.mixture_moments_host); its draw arrays are fetched and dropped likewise."""
+    draws (_lib.mixture_moments_host); its draw arrays are fetched and dropped likewise.
+    density_vars: names among mu, sig2, pi_end, A, fcast -> BatchResult.density, {var: ChainDensity}: per window and column
+    the binned counts of the chain prefixes density_cuts (default: the whole chain) on density_bins bins over the range of the
+    draws, mean and variance of each prefix and the running mean density_trace = (length, stride) (mcplots.jl's plotchain and
+    plotchainmean up to the drawing), computed on the device from the 5-digit-rounded draws (_lib.chain_density); the draw
+    arrays are fetched and dropped likewise."""
     if startIndex != 1:
         raise ValueError("windows must start at index 1 (see estopt)")
+    if density_vars is not None:
+        density_vars = tuple(density_vars)
+        for var in density_vars:
+            if var not in DENSITY_FILES:
+                raise ValueError("density_vars: %r is none of %s" % (var, tuple(DENSITY_FILES)))
     rawdata = np.asarray(rawdata, dtype=np.float64)
     opts = [estopt(rawdata, dates, sampleRange=range(1, int(e) + 1), endIndex=int(e), **kwargs) for e in endIndices]
     o0 = opts[0]
@@ -430,6 +466,8 @@ def estimatewindows(rawdata, dates, endIndices, startIndex=1, keep_draws=False, 
             want += ("mu", "pi_end") + (("A",) if int(bias_horizon) > 0 else ()) + (("fcast",) if len(o0.horizons) else ())
         if moment_horizons is not None:
             want += ("mu", "sig2", "pi_end") + (("A",) if any(int(h) > 0 for h in moment_horizons) else ())
+        if density_vars is not None:
+            want += tuple(density_vars)
         want = tuple(k for k in _lib.DRAW_KEYS if k in want) or False
     res = _lib.estimate_batch_host(Y, Tw, o0.D, o0.burnin, o0.Nrun, tuple(o0.horizons), yreal, seed=o0.seed,
                                    device=device, want_draws=want, window_ids=window_ids, want_corr=corr)
@@ -449,6 +487,12 @@ def estimatewindows(rawdata, dates, endIndices, startIndex=1, keep_draws=False, 
         out = _lib.mixture_moments_host(res["mu"], res["sig2"], res["pi_end"], res.get("A") if any(h > 0 for h in hz) else None,
                                         hz, device=device)
         res["moments"] = MixtureMoments(hz, _lib.unpack_mixture_moments(out))
+    if density_vars is not None:
+        res["density"] = {}
+        for var in density_vars:
+            parts = _lib.chain_density(res[var], density_cuts, density_bins, None, density_trace, device=device)
+            res["density"][var] = ChainDensity(var, _density_columns(o0, var), (o0.Nrun,) if density_cuts is None else density_cuts,
+                                               density_trace[1], parts)
     return BatchResult(opts, res, keep_draws)
 
 
@@ -1169,4 +1213,210 @@ def write_forecast_comparison(path, dates, forecast_post, forecast_proper):
     """alt_forecasts.jl:28,39: `date,forecast_post,forecast_proper`, one row per end date, float text as in the other files (_fmt)."""
     rows = [[str(d), _fmt(a), _fmt(b)] for d, a, b in zip(dates, forecast_post, forecast_proper)]
     _write_csv(path, ["date", "forecast_post", "forecast_proper"], rows)
+    return path
+
+
+# ------------------------------------------- plots/mcplots.jl, timeseriesplots.jl --
+
+def _density_columns(opt, var):
+    """The column names of the per-draw file of `var` (saveresults)."""
+    h1, h2, h3 = _header(opt, 2 * len(opt.horizons))
+    return {"A": h2, "fcast": h3}.get(var, h1)
+
+
+def _bin_slots(v, lo, hi, bins):
+    """The bin rule of include/hmcg.h on a 1-D array: the bin per value, -1 below, -2 above, -3 NaN."""
+    isn = np.isnan(v)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        below = ~isn & (bool(np.isnan(lo) or np.isnan(hi)) | (v < lo))
+        above = ~isn & ~below & (v > hi)
+        slot = np.zeros(v.shape, dtype=np.int64)
+        if hi > lo:
+            scale = np.float64(bins) / (np.float64(hi) - np.float64(lo))
+            t = np.floor((v - np.float64(lo)) * scale)
+            slot = np.clip(np.where(np.isnan(t), 0.0, t), 0.0, float(bins - 1)).astype(np.int64)
+    slot[below], slot[above], slot[isn] = -1, -2, -3
+    return slot
+
+
+def _density_from_cells(cells, cuts, bins, lo_hi, trace):
+    """The outputs of hmcg_chain_density for one date from the cells (n, C) of its per-draw file, in numpy fp64 with the
+    library's algebra (sums about the pivot p = row 0).  Returns the parts of _lib.DENS_FIELDS without the window axis."""
+    n, Cn = cells.shape
+    nc, tl, ts = len(cuts), int(trace[0]), int(trace[1])
+    out = {"counts": np.zeros((Cn, nc, bins), dtype=np.int64), "below": np.zeros((Cn, nc), dtype=np.int64),
+           "above": np.zeros((Cn, nc), dtype=np.int64), "nan": np.zeros((Cn, nc), dtype=np.int64), "range": np.empty((Cn, 2)),
+           "mean": np.empty((Cn, nc)), "variance": np.empty((Cn, nc)), "trace": np.empty((Cn, tl))}
+    idx = (np.arange(tl) + 1) * ts - 1
+    for c in range(Cn):
+        v = cells[:, c]
+        fin = v[np.isfinite(v)]
+        if lo_hi is not None:
+            lo, hi = lo_hi[c]
+        elif fin.size:
+            lo, hi = fin.min(), fin.max()
+        else:
+            lo = hi = np.nan
+        out["range"][c] = lo, hi
+        slot = _bin_slots(v, lo, hi, bins)
+        with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+            a = v - v[0]
+            for j, cut in enumerate(cuts):
+                s = slot[:cut]
+                out["counts"][c, j] = np.bincount(s[s >= 0], minlength=bins)
+                out["below"][c, j], out["above"][c, j], out["nan"][c, j] = (s == -1).sum(), (s == -2).sum(), (s == -3).sum()
+                S1, S2, m = a[:cut].sum(), (a[:cut] * a[:cut]).sum(), float(cut)
+                out["mean"][c, j] = v[0] + S1 / m
+                out["variance"][c, j] = (S2 - S1 * S1 / m) / (m - 1.0)
+            out["trace"][c] = v[0] + np.cumsum(a)[idx] / (idx + 1.0)
+    return out
+
+
+def calcchain(datadir, dates, var="mu", cuts=None, bins=64, lo_hi=None, trace=(0, 1), result=None):
+    """plots/mcplots.jl:24-38 (plotchain), :47-63 (plotchainmean) and plots/timeseriesplots.jl:83-142 (plot_mean / plot_var) up
+    to the drawing: per end date and column of one variable's per-draw file the binned counts of the chain prefixes 1:cuts[j]
+    (mcplots.jl: 100000, 150000, 200000, 250000; default: the whole chain), mean and variance of each prefix, and the running
+    mean after (i + 1) * trace[1] draws, i < trace[0] (plotchainmean: (10000, 1)).  var: mu, sig2, pi_end, A or fcast.
+
+    result=None: every date's `filtered_means_<date>.csv` (`filtered_variances_`, `filtered_state_probs_`,
+    `filtered_trans_probs_`, `forecasts_` for the other variables) is read back as the plot scripts read it and evaluated on the
+    host in numpy; no GPU is touched.  lo_hi: (n_dates, C, 2) bin ranges (default: the range of each column's finite cells).
+    result = a BatchResult of estimatewindows(..., density_vars=(var, ...)): the counts and sums were taken on the device from
+    the rounded draws; every date must be one of the result's end dates, and cuts / bins / trace must be the result's.
+    Returns (dates, ChainDensity)."""
+    dates = [str(d) for d in dates]
+    if var not in DENSITY_FILES:
+        raise ValueError("var must be one of %s" % (tuple(DENSITY_FILES),))
+    if result is not None:
+        d = getattr(result, "density", None)
+        if d is None or var not in d:
+            raise ValueError("result carries no chain density of %s (estimatewindows(..., density_vars=(%r,)))" % (var, var))
+        d = d[var]
+        if (cuts is not None and tuple(int(c) for c in cuts) != d.cuts) or int(bins) != d.bins or \
+                (int(trace[0]), int(trace[1])) != (d.trace.shape[2], d.trace_stride):
+            raise ValueError("result was computed for other cuts, bins or trace")
+        by_date = {str(enddate(o)): w for w, o in enumerate(result.opts)}
+        for x in dates:
+            if x not in by_date:
+                raise ValueError("no window ends on %s" % x)
+        return dates, d.rows([by_date[x] for x in dates])
+    parts, columns, used = [], None, None
+    for i, date in enumerate(dates):
+        header, rows = _read_csv(os.path.join(datadir, "%s_%s.csv" % (DENSITY_FILES[var], date)))
+        cells = np.array([[float(x) for x in r[1:]] for r in rows])
+        columns = header[1:]
+        ct = (cells.shape[0],) if cuts is None else tuple(int(c) for c in cuts)
+        if used is not None and ct != used:
+            raise ValueError("the dates' files differ in length: give cuts")
+        used = ct
+        if any(c < 1 or c > cells.shape[0] for c in ct) or int(trace[0]) * int(trace[1]) > cells.shape[0]:
+            raise ValueError("cuts or trace reach beyond the %d draws of %s" % (cells.shape[0], date))
+        parts.append(_density_from_cells(cells, ct, int(bins), None if lo_hi is None else np.asarray(lo_hi, dtype=np.float64)[i], trace))
+    return dates, ChainDensity(var, columns, used, trace[1], {k: np.array([q[k] for q in parts]) for k in _lib.DENS_FIELDS})
+
+
+def chainquantiles(density, qs):
+    """Credible limits at bin resolution: per window, column and prefix, for each q in qs the bin that holds the order
+    statistic ceil(q * n) (1 <= . <= n) of the n non-NaN draws of the prefix -- exact by construction, since the counts say how
+    many draws lie below each bin.  Returns a dict of (n, C, n_cuts, len(qs)) arrays: bin (-1: below lo, bins: above hi), lo and
+    hi, the bin's edges range_lo + b * (range_hi - range_lo) / bins (-inf / +inf on the open side of below / above; NaN with no
+    draw to rank)."""
+    qs = np.atleast_1d(np.asarray(qs, dtype=np.float64))
+    B = density.bins
+    full = np.concatenate([density.below[..., None], density.counts, density.above[..., None]], axis=3)      # order: below, bins, above
+    cum = np.cumsum(full, axis=3)
+    n = cum[..., -1]
+    shape = n.shape + (qs.size,)
+    out = {"bin": np.empty(shape, dtype=np.int64), "lo": np.empty(shape), "hi": np.empty(shape)}
+    lo, hi = density.range[..., 0][:, :, None], density.range[..., 1][:, :, None]
+    with np.errstate(invalid="ignore"):
+        edges = lo[..., None] + np.arange(B + 1) * ((hi - lo) / B)[..., None]                                # (n, C, 1, B + 1)
+    edges = np.broadcast_to(edges, n.shape + (B + 1,))
+    for i, q in enumerate(qs):
+        k = np.clip(np.ceil(q * n), 1, np.maximum(n, 1)).astype(np.int64)
+        b = (cum < k[..., None]).sum(axis=3) - 1                      # first slot whose running count reaches k, as a bin index
+        b = np.minimum(b, B)
+        inside = np.clip(b, 0, B - 1)
+        el = np.take_along_axis(edges, inside[..., None], axis=3)[..., 0]
+        eh = np.take_along_axis(edges, inside[..., None] + 1, axis=3)[..., 0]
+        l = np.where(b < 0, -np.inf, np.where(b >= B, np.broadcast_to(hi, b.shape), el))
+        h = np.where(b < 0, np.broadcast_to(lo, b.shape), np.where(b >= B, np.inf, eh))
+        none = n == 0
+        out["bin"][..., i] = np.where(none, -1, b)
+        out["lo"][..., i] = np.where(none, np.nan, l)
+        out["hi"][..., i] = np.where(none, np.nan, h)
+    return out
+
+
+def chaindensity(density, points=None, bandwidth=None):
+    """What Gadfly's Geom.density draws in plotchain / plot_mean / plot_var, from the binned counts: the Gaussian kernel
+    estimate f(x) = sum_b counts_b N(x; centre_b, h) / sum_b counts_b over the in-range draws, a discrete convolution of the
+    histogram with the kernel sampled at the bin spacing when points is None (the points are then the bin centres).
+    h is Silverman's rule 0.9 min(sd, IQR / 1.34) n^(-1/5) with sd from the prefix's variance and IQR from the centres of the
+    bins that hold the quartiles (chainquantiles); where that is 0 or NaN, the bin width.  bandwidth: a number that overrides it.
+    Upstream's KernelDensity.jl picks its own grid (2048 points on a padded range) and bandwidth; neither is pinned here, so the
+    curves agree in shape, not point for point.
+    Returns a dict: x (n, C, P) points, density (n, C, n_cuts, P), bandwidth (n, C, n_cuts)."""
+    B = density.bins
+    lo, hi = density.range[..., 0], density.range[..., 1]
+    width = (hi - lo) / B
+    centres = lo[..., None] + (np.arange(B) + 0.5) * width[..., None]                    # (n, C, B)
+    n_in = density.counts.sum(axis=3).astype(np.float64)
+    q = chainquantiles(density, (0.25, 0.75))
+    with np.errstate(invalid="ignore", divide="ignore"):
+        iqr = ((np.clip(q["bin"][..., 1], 0, B - 1) - np.clip(q["bin"][..., 0], 0, B - 1)) * width[..., None]).astype(np.float64)
+        sd = np.sqrt(density.variance)
+        spread = np.where(iqr > 0, np.minimum(sd, iqr / 1.34), sd)
+        h = 0.9 * spread * n_in ** -0.2
+        h = np.where(np.isfinite(h) & (h > 0), h, np.broadcast_to(width[..., None], h.shape))
+    if bandwidth is not None:
+        h = np.full(h.shape, float(bandwidth))
+    nW, Cn, nc = h.shape
+    if points is None:
+        x = centres
+    else:
+        x = np.broadcast_to(np.asarray(points, dtype=np.float64), (nW, Cn, np.size(points))).copy()
+    dens = np.full((nW, Cn, nc, x.shape[2]), np.nan)
+    for w in range(nW):
+        for c in range(Cn):
+            for j in range(nc):
+                hh, tot = h[w, c, j], n_in[w, c, j]
+                if not (tot > 0 and np.isfinite(hh) and hh > 0):
+                    continue
+                cnt = density.counts[w, c, j].astype(np.float64)
+                if points is None:
+                    off = np.arange(-(B - 1), B) * width[w, c]                          # the kernel at the bin spacing
+                    ker = np.exp(-0.5 * (off / hh) ** 2) / (hh * math.sqrt(2.0 * math.pi))
+                    dens[w, c, j] = np.convolve(cnt, ker)[B - 1:2 * B - 1] / tot
+                else:
+                    z = (x[w, c][:, None] - centres[w, c][None, :]) / hh
+                    dens[w, c, j] = (np.exp(-0.5 * z * z) @ cnt) / (hh * math.sqrt(2.0 * math.pi) * tot)
+    return {"x": x, "density": dens, "bandwidth": h}
+
+
+def write_chain_density(path, dates, density):
+    """`date,column,cut,bin_lo,bin_hi,count,density`: one row per end date, column, prefix and bin -- the bin's edges, its count
+    and the kernel estimate at its centre (chaindensity).  Our layout: upstream draws the figure and writes no file."""
+    kde = chaindensity(density)["density"]
+    B = density.bins
+    rows = []
+    for w, d in enumerate(dates):
+        for c, name in enumerate(density.columns):
+            lo, hi = density.range[w, c]
+            for j, cut in enumerate(density.cuts):
+                for b in range(B):
+                    rows.append([str(d), name, str(cut), _fmt(lo + b * ((hi - lo) / B)), _fmt(lo + (b + 1) * ((hi - lo) / B)),
+                                 str(int(density.counts[w, c, j, b])), _fmt(kde[w, c, j, b])])
+    _write_csv(path, ["date", "column", "cut", "bin_lo", "bin_hi", "count", "density"], rows)
+    return path
+
+
+def write_chain_trace(path, dates, density):
+    """`date,column,draws,mean`: the running mean of plotchainmean, one row per end date, column and trace point."""
+    rows = []
+    for w, d in enumerate(dates):
+        for c, name in enumerate(density.columns):
+            for i in range(density.trace.shape[2]):
+                rows.append([str(d), name, str((i + 1) * density.trace_stride), _fmt(density.trace[w, c, i])])
+    _write_csv(path, ["date", "column", "draws", "mean"], rows)
     return path

@@ -19,7 +19,9 @@
 # predictive CDFs of code/hassan_cdfs/calc_cdfs.jl from the draws, on the device (hmcg_predictive_cdf).  calcbias /
 # bias_moments: uncerbias and totalbias of code/hassan_cdfs/bias_calcs.jl likewise (hmcg_bias_moments).  calcmoments /
 # mixture_moments: what code/skewness.jl and code/alt_forecasts.jl ask of the summary rows, asked of the draws
-# (hmcg_mixture_moments); calcskewness / altforecasts: the two scripts themselves, in closed form.  runaggregate /
+# (hmcg_mixture_moments); calcskewness / altforecasts: the two scripts themselves, in closed form.  calcchain /
+# chain_density: the binned chain densities and running means plots/mcplots.jl and plots/timeseriesplots.jl draw
+# (hmcg_chain_density).  runaggregate /
 # calcdispersion of the reference work unchanged on the files written here (same names, columns and float text).
 #
 # Reference lines mirrored: estopt src/Hmc.jl:17-73, accessors :85-107, makedate :573-582,
@@ -144,6 +146,21 @@ struct hmcg_mixmom                    # include/hmcg.h: predictive mixture momen
     n_h::Int32
     flags::Int32
     horizons::NTuple{HMCG_MAXH,Int32}
+end
+const HMCG_DENS_ROUND5 = Int32(1)
+struct hmcg_density                   # include/hmcg.h: chain densities and running means of the draws (plots/mcplots.jl)
+    struct_size::Int32
+    W::Int32
+    C::Int32
+    device::Int32
+    nd::Int64
+    nd_ld::Int64
+    B::Int32
+    n_cuts::Int32
+    cuts::NTuple{HMCG_MAXH,Int64}
+    trace_len::Int32
+    flags::Int32
+    trace_stride::Int64
 end
 
 last_error() = unsafe_string(ccall((:hmcg_last_error, LIBHMCG), Cstring, ()))
@@ -470,6 +487,70 @@ function calcmoments(opts::Vector{estopt}; horizons=[0], device::Integer=0)
     μ, σ, πe = cat3(s -> s.μ), cat3(s -> s.σ), cat3(s -> s.πb[:, 1, :])
     A = any(h -> h > 0, horizons) ? cat((s.A for s in samples)...; dims=4) : nothing
     return [enddate(o) for o in opts], mixture_moments(μ, σ, πe, A; horizons=horizons, device=device)
+end
+
+# ---- chain densities and running means (plots/mcplots.jl, plots/timeseriesplots.jl up to the drawing) ---------------------
+_density(W, C, nd, ld, cuts, bins, trace, device, round5) =
+    hmcg_density(Int32(sizeof(hmcg_density)), Int32(W), Int32(C), Int32(device), Int64(nd), Int64(ld), Int32(bins), Int32(length(cuts)),
+                 ntuple(i -> i <= length(cuts) ? Int64(cuts[i]) : Int64(0), HMCG_MAXH), Int32(trace[1]),
+                 round5 ? HMCG_DENS_ROUND5 : Int32(0), Int64(trace[2]))
+
+"""
+    chain_density(x; cuts=[nrun], bins=64, lo_hi=nothing, trace=(0, 1), device=0, round5=true)
+        -> (range (2, C, W), counts (bins + 3, n_cuts, C, W), stats (2, n_cuts, C, W), trace (trace_len, C, W))
+
+hmcg_chain_density over ONE host draw array in a layout estimatewindows fills, draw index first and window last -- μ, σ, πe
+(nrun, K, W), A (nrun, K, K, W), forecasts (nrun, 2H, W); the axes between count as the C columns: per window and column the
+binned counts of the chain prefixes 1:cuts[j] (mcplots.jl plotchain: 100000, 150000, 200000, 250000) on `bins` equal bins between
+lo and hi (`lo_hi` (2, C, W), default the range of the finite draws), then the draws below lo, above hi and NaN; mean and variance
+of each prefix; the running mean after i * trace[2] draws, i <= trace[1] (plotchainmean: (10000, 1)).
+"""
+function chain_density(x::Array{Float64}; cuts=nothing, bins::Integer=64, lo_hi=nothing, trace=(0, 1), device::Integer=0,
+                       round5::Bool=true)
+    nrun, W = size(x, 1), size(x, ndims(x))
+    C = div(length(x), nrun * W)
+    cuts = cuts === nothing ? [nrun] : cuts
+    range = Array{Float64}(undef, 2, C, W)
+    counts = Array{Int64}(undef, bins + 3, length(cuts), C, W)
+    stats = Array{Float64}(undef, 2, length(cuts), C, W)
+    tr = Array{Float64}(undef, trace[1], C, W)
+    plh = lo_hi === nothing ? Ptr{Float64}(C_NULL) : pointer(lo_hi)
+    ptr = trace[1] > 0 ? pointer(tr) : Ptr{Float64}(C_NULL)
+    rc = GC.@preserve x lo_hi range counts stats tr ccall((:hmcg_chain_density, LIBHMCG), Cint,
+        (Ref{hmcg_density}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}),
+        _density(W, C, nrun, nrun, cuts, bins, trace, device, round5), x, plh, range, counts, stats, ptr, C_NULL)
+    rc == 0 || error("libhmcgibbs rc=$rc: $(last_error())")
+    return range, counts, stats, tr
+end
+
+"""
+    chain_density_device(W, C, nd, ld, dx, dlo_hi, drange, dcounts, dstats, dtrace; cuts, bins=64, trace=(0, 1), device=0,
+                         round5=true, stream=C_NULL)
+
+hmcg_chain_density_device over device pointers (dlo_hi = C_NULL for the automatic range, dtrace = C_NULL without a running
+mean); enqueued on `stream` (C_NULL: the library's own) and not waited for.
+"""
+function chain_density_device(W, C, nd, ld, dx::Ptr{Float64}, dlo_hi::Ptr{Float64}, drange::Ptr{Float64}, dcounts::Ptr{Int64},
+                              dstats::Ptr{Float64}, dtrace::Ptr{Float64}; cuts=[nd], bins::Integer=64, trace=(0, 1),
+                              device::Integer=0, round5::Bool=true, stream::Ptr{Cvoid}=C_NULL)
+    rc = ccall((:hmcg_chain_density_device, LIBHMCG), Cint,
+               (Ref{hmcg_density}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}, Ptr{Cvoid}),
+               _density(W, C, nd, ld, cuts, bins, trace, device, round5), dx, dlo_hi, drange, dcounts, dstats, dtrace, stream, C_NULL)
+    rc == 0 || error("libhmcgibbs rc=$rc: $(last_error())")
+    return nothing
+end
+
+"""
+    calcchain(opts, var=:μ; cuts=nothing, bins=64, trace=(0, 1), device=0) -> (dates, range, counts, stats, trace)
+
+plotchain / plotchainmean / plot_mean / plot_var up to the drawing: estimates the windows and bins the chain of one variable
+(:μ, :σ, :πe, :A or :forecasts) on the device.
+"""
+function calcchain(opts::Vector{estopt}, var::Symbol=:μ; cuts=nothing, bins::Integer=64, trace=(0, 1), device::Integer=0)
+    samples, _, _ = estimatewindows(opts; device=device)
+    pick(s) = var == :πe ? s.πb[:, 1, :] : getfield(s, var)
+    x = cat((pick(s) for s in samples)...; dims=var == :A ? 4 : 3)
+    return ([enddate(o) for o in opts], chain_density(x; cuts=cuts, bins=bins, trace=trace, device=device)...)
 end
 
 function _summary_rows(datadir, stem)

@@ -34,6 +34,13 @@
  *                                  (skewness.jl estimates one third moment from 10 000 000 variates of the plug-in mixture;
  *                                  alt_forecasts.jl sets the plug-in mean beside the draw mean), and what a plug-in hides:
  *                                  the within- and between-draw shares of the variance and the mean per-draw skewness.
+ *   hmcg_chain_density[_device]    plots/mcplots.jl:24-38 (plotchain: the density of one parameter's draws over the nested
+ *                                  prefixes 1:100_000 .. 1:250_000 of the chain), :47-63 (plotchainmean: the cumulative mean of
+ *                                  a column over the first 10 000 draws) and plots/timeseriesplots.jl:83-142 (plot_mean /
+ *                                  plot_var: the marginal posterior densities of the state means and variances) up to the
+ *                                  drawing: per window and draw column the binned counts of every prefix, its mean and
+ *                                  variance, and the running mean, taken from the draw arrays instead of the per-draw CSV
+ *                                  files the scripts read back.
  *
  * Conventions: plain C structs, fixed-width ints, no C++ types or exceptions cross
  * the boundary.  Return 0 on success, negative on API misuse (HMCG_E_*), positive
@@ -374,6 +381,55 @@ int hmcg_mixture_moments_device(const hmcg_mixmom* p, const double* dmu, const d
  * kernel of the one before. */
 int hmcg_mixture_moments(const hmcg_mixmom* p, const double* mu, const double* sig2, const double* pi_end, const double* A,
                          double* out, hmcg_timing* timing);
+
+/* ---- chain densities and running means of the draws (plots/mcplots.jl, plots/timeseriesplots.jl) ----------------------------
+ * One generic entry over ONE draw array x of C columns per window, element (d, c, w) at d + nd_ld * (c + C * w): the layout of
+ * mu, sig2 and pi_end with C = K, of A with C = K * K, of fcast with C = 2H.  Call it once per variable.
+ * With x' = the value rounded as a CSV cell is under HMCG_DENS_ROUND5 (as HMCG_PRED_ROUND5) and x' = x otherwise, per window w
+ * and column c:
+ *   range[w][c][2] = (lo, hi): the caller's lo_hi[w][c][2] when lo_hi is given (the host entry wants them finite with hi >= lo;
+ *     the device entry cannot look), else the minimum and maximum of the FINITE x' over all nd draws; both NaN with no finite value.
+ *   counts[w][c][j][B + 3], int64, for the prefix d < cuts[j]: B bins, then `below`, `above`, `nan`.  The bin rule, in this
+ *     order, every operation a rounded fp64 operation of its own (nothing fused):
+ *       x' is NaN -> nan;  lo or hi is NaN -> below;  x' < lo (-inf too) -> below;  x' > hi (+inf too) -> above;
+ *       !(hi > lo) -> bin 0;  else b = floor((x' - lo) * scale), scale = (double)B / (hi - lo), clamped to 0..B-1.
+ *     The four groups of a prefix sum to cuts[j].
+ *   stats[w][c][j][2] = mean and variance (divisor n - 1, n = cuts[j]) of x' over the prefix, both about the pivot p = x' of the
+ *     window's draw 0:  a_d = x'_d - p, S1 = sum a_d, S2 = sum a_d^2, mean = p + S1 / n, variance = (S2 - S1 * S1 / n) / (n - 1).
+ *     n = 1 gives a NaN variance; NaN and inf propagate into every prefix that holds them (a non-finite draw 0 into all); a column
+ *     of identical values gives variance exactly 0.
+ *   trace[w][c][i], i < trace_len: the mean of the first n_i = (i + 1) * trace_stride draws, p + (sum_{d < n_i} a_d) / n_i
+ *     (plotchainmean: stride 1, length 10 000).
+ * Deterministic: the draws are cut into pieces at every multiple of 1024 (the predictive entries' slabs) and at every cut; a
+ * piece's float sums are taken in an order that depends on the draw's place in the piece alone, the pieces are added in piece
+ * order; counts are integers.  No floating-point atomics: bit-identical from run to run, from both entries and for every
+ * chunking of the host entry's upload (HMCG_CHUNK_DRAWS under HMCG_DIAG=1).
+ * Misuse (HMCG_E_BADARG, checked before any HIP call): struct_size, W < 1, C outside 1..HMCG_MAXK^2, B outside
+ * 1..HMCG_DENS_MAXBINS, nd < 1 or > 2^53 (n must be an exact fp64 divisor; the counters are 64-bit), nd_ld < nd, n_cuts outside
+ * 1..HMCG_MAXH, a cut outside 1..nd or not above the one before, trace_len outside 0..HMCG_DENS_MAXTRACE, trace_stride < 1,
+ * trace_len * trace_stride > nd, more than 2^31 - 1 blocks in one launch (W * pieces * column groups, or W * C), a NULL x / range / counts / stats, NULL trace with
+ * trace_len > 0, and on the host entry a lo_hi pair that is not finite or has hi < lo. */
+#define HMCG_DENS_ROUND5 1
+#define HMCG_DENS_MAXBINS 512
+#define HMCG_DENS_MAXTRACE 65536
+typedef struct hmcg_density {
+    int32_t struct_size, W, C, device;
+    int64_t nd, nd_ld;                 /* draws per window; leading dimension of the draw array (>= nd) */
+    int32_t B, n_cuts;                 /* bins 1..HMCG_DENS_MAXBINS; prefixes 1..HMCG_MAXH */
+    int64_t cuts[HMCG_MAXH];           /* strictly ascending prefix lengths, 1..nd (mcplots.jl: 100000, 150000, 200000, 250000) */
+    int32_t trace_len, flags;          /* running-mean points 0..HMCG_DENS_MAXTRACE; HMCG_DENS_ROUND5 */
+    int64_t trace_stride;              /* >= 1, trace_len * trace_stride <= nd */
+} hmcg_density;
+/* Device entry: every data pointer is HBM-resident on p->device; enqueued on `stream` (NULL: the library's own) behind the
+ * library's earlier work there; returns after enqueueing unless `timing` is given (kernel_ms: HIP events around the kernels). */
+int hmcg_chain_density_device(const hmcg_density* p, const double* dx, const double* dlo_hi /* [W][C][2] or NULL */,
+                              double* drange /* [W][C][2] */, int64_t* dcounts /* [W][C][n_cuts][B + 3] */,
+                              double* dstats /* [W][C][n_cuts][2] */, double* dtrace /* [W][C][trace_len]; NULL iff trace_len == 0 */,
+                              void* stream, hmcg_timing* timing);
+/* Host entry (blocking): uploads the draws in chunks of whole slabs through pinned staging, the copy of one chunk beside the
+ * kernel of the one before -- twice with lo_hi NULL (the range, then the counts), once with lo_hi given. */
+int hmcg_chain_density(const hmcg_density* p, const double* x, const double* lo_hi, double* range, int64_t* counts, double* stats,
+                       double* trace, hmcg_timing* timing);
 
 /* ---- per-draw CSV output (host code, no GPU): basicsave / saveresults, src/Hmc.jl:707-748 ------------------------------
  * The five per-window files `filtered_means_<date>.csv`, `filtered_variances_<date>.csv`, `filtered_state_probs_<date>.csv`,
