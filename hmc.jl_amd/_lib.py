@@ -27,7 +27,8 @@ EXPORTS = ("hmcg_version", "hmcg_device_count", "hmcg_last_error", "hmcg_shutdow
            "hmcg_estimate_batch", "hmcg_estimate_batch_device", "hmcg_estimate_batch_multi",
            "hmcg_save_results_csv", "hmcg_write_table_csv", "hmcg_format_float",
            "hmcg_predictive_cdf", "hmcg_predictive_cdf_device", "hmcg_bias_moments", "hmcg_bias_moments_device",
-           "hmcg_mixture_moments", "hmcg_mixture_moments_device", "hmcg_chain_density", "hmcg_chain_density_device")
+           "hmcg_mixture_moments", "hmcg_mixture_moments_device", "hmcg_chain_density", "hmcg_chain_density_device",
+           "hmcg_chain_autocorr", "hmcg_chain_autocorr_device")
 HMCG_MAXDEV = 16
 PRED_ROUND5 = 1
 HMCG_MAXGRID = 4096
@@ -41,6 +42,10 @@ DENS_ROUND5 = 1
 DENS_MAXBINS = 512              # HMCG_DENS_MAXBINS
 DENS_MAXTRACE = 65536           # HMCG_DENS_MAXTRACE
 DENS_FIELDS = ("counts", "below", "above", "nan", "range", "mean", "variance", "trace")
+ACF_ROUND5 = 1
+ACF_MAXLAG = 1024               # HMCG_ACF_MAXLAG
+ACF_STRIDE = 8                  # HMCG_ACF_STRIDE: doubles per (window, column) of the diagnostics block
+ACF_FIELDS = ("mean", "variance", "tau", "ess", "mcse", "pairs", "truncated", "rhat")
 
 
 def bias_stride(K):
@@ -94,6 +99,11 @@ class Density(C.Structure):
     _fields_ = [("struct_size", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("device", C.c_int32),
                 ("nd", C.c_int64), ("nd_ld", C.c_int64), ("B", C.c_int32), ("n_cuts", C.c_int32),
                 ("cuts", C.c_int64 * HMCG_MAXH), ("trace_len", C.c_int32), ("flags", C.c_int32), ("trace_stride", C.c_int64)]
+
+
+class Autocorr(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("device", C.c_int32),
+                ("nd", C.c_int64), ("nd_ld", C.c_int64), ("L", C.c_int32), ("flags", C.c_int32)]
 
 
 class MixMom(C.Structure):
@@ -168,6 +178,8 @@ def load():
         L.hmcg_mixture_moments_device.restype = C.c_int
         L.hmcg_chain_density.restype = C.c_int
         L.hmcg_chain_density_device.restype = C.c_int
+        L.hmcg_chain_autocorr.restype = C.c_int
+        L.hmcg_chain_autocorr_device.restype = C.c_int
         _LIB = L
     return _LIB
 
@@ -651,6 +663,62 @@ def chain_density_device(dens, dx, dlo_hi, drange, dcounts, dstats, dtrace, stre
 
     _check(load().hmcg_chain_density_device(C.byref(dens), vp(dx), vp(dlo_hi), vp(drange), vp(dcounts), vp(dstats), vp(dtrace),
                                             vp(stream), C.byref(tm) if timed else None))
+    return tm
+
+
+def make_autocorr(W, Cn, nd, nd_ld, lags=255, device=0, round5=True):
+    """hmcg_autocorr of a call over a draw array of Cn columns per window; lags = the largest lag L.  Every rule is the
+    library's (HMCG_E_BADARG)."""
+    p = Autocorr()
+    p.struct_size = C.sizeof(Autocorr)
+    p.W, p.C, p.device, p.nd, p.nd_ld, p.L = int(W), int(Cn), int(device), int(nd), int(nd_ld), int(lags)
+    p.flags = ACF_ROUND5 if round5 else 0
+    return p
+
+
+def unpack_chain_autocorr(acov, diag):
+    """The two output blocks of hmcg_chain_autocorr -- acov (W, C, L + 1), diag (W, C, 8) -- as a dict: acov, the biased
+    autocovariances at lags 0..L, and per (window, column) mean, variance (divisor n - 1), tau (the integrated autocorrelation
+    time by Geyer's initial monotone sequence), ess = n / tau, mcse = sqrt(variance tau / n), pairs (int64: the lag pairs the
+    sequence used), truncated (bool: it used every pair, the lag window is too short), rhat (split-R-hat of the two halves)."""
+    diag = np.asarray(diag)
+    out = {"acov": np.asarray(acov).copy()}
+    for i, name in enumerate(ACF_FIELDS):
+        out[name] = diag[..., i].copy()
+    with np.errstate(invalid="ignore"):
+        out["pairs"] = out["pairs"].astype(np.int64)
+        out["truncated"] = out["truncated"] != 0.0
+    return out
+
+
+def chain_autocorr(x, lags=255, nd=None, device=0, round5=True, timing=None):
+    """hmcg_chain_autocorr over ONE host (numpy) draw array in a C-ABI layout with the draw index last -- mu / sig2 / pi_end
+    (W, K, nd), A (W, K, K, nd), fcast (W, 2H, nd); every axis between the first and the last counts as columns -- over its
+    first nd draws (default: all).  Per window and column: the autocovariances at lags 0..lags and the convergence diagnostics
+    of unpack_chain_autocorr.  round5 (default): every value is first rounded to 5 digits, as the cells of the per-draw CSV
+    files are.  Returns the dict of unpack_chain_autocorr, the column axis flattened.  timing: a Timing to fill."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    W, ld = x.shape[0], x.shape[-1]
+    Cn = int(np.prod(x.shape[1:-1], dtype=np.int64))
+    nd = ld if nd is None else int(nd)
+    p = make_autocorr(W, Cn, nd, ld, lags, device, round5)
+    acov = np.zeros((W, Cn, max(int(lags), 0) + 1))
+    diag = np.zeros((W, Cn, ACF_STRIDE))
+    _check(load().hmcg_chain_autocorr(C.byref(p), _np_ptr(x), _np_ptr(acov), _np_ptr(diag),
+                                      C.byref(timing) if timing is not None else None))
+    return unpack_chain_autocorr(acov, diag)
+
+
+def chain_autocorr_device(acf, dx, dacov, ddiag, stream=None, timed=False):
+    """hmcg_chain_autocorr_device over raw device pointers (ints, e.g. torch tensor.data_ptr()); acf: make_autocorr(...).
+    Enqueued on `stream` (None: the library's own).  Returns the Timing struct when timed (the call then waits for completion),
+    else None."""
+    tm = Timing() if timed else None
+
+    def vp(x):
+        return None if not x else C.c_void_p(int(x))
+
+    _check(load().hmcg_chain_autocorr_device(C.byref(acf), vp(dx), vp(dacov), vp(ddiag), vp(stream), C.byref(tm) if timed else None))
     return tm
 
 

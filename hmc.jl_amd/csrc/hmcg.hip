@@ -36,6 +36,7 @@
 #include "bias.hpp"
 #include "mixmoments.hpp"
 #include "density.hpp"
+#include "autocorr.hpp"
 
 namespace {
 
@@ -123,6 +124,7 @@ struct DeviceCtx {
     Arena bias;                    // device entry of the uncertainty-bias moments: the slab sums and pivots
     Arena mix;                     // device entry of the predictive-mixture moments: the slab sums and pivots
     Arena dens;                    // device entry of the chain densities: the piece sums, pivots and range keys
+    Arena acf;                     // device entry of the autocorrelations: the running lag sums, pivots and edge values
     hmcg_hostutil::ScatterPool pool;              // host entries: helpers for the scatter into the caller's arrays
 };
 DeviceCtx g_ctx[HMCG_MAXDEV];
@@ -223,6 +225,7 @@ void destroy_context(DeviceCtx& c)
     c.bias.release();
     c.mix.release();
     c.dens.release();
+    c.acf.release();
     c.pool.stop();
     c.stream = c.copy = nullptr;
     c.ready = false;
@@ -1491,6 +1494,125 @@ int dens_host(DeviceCtx& c, const hmcg_density* p, const double* x, const double
     return 0;
 }
 
+// ---- autocorrelation, effective sample size and split-R-hat of the draws (autocorr.hip; argument rules and thread split:
+// autocorr_plan.hpp; chunk cut: predictive_plan.hpp) ------------------------------------------------------------------------------
+
+void fill_acf_timing(hmcg_timing* t, const hmcg_autocorr* p, const DeviceCtx& c, double kernel_ms, int launches, double call_ms)
+{
+    memset(t, 0, sizeof *t);
+    t->kernel_ms = kernel_ms; t->launches = launches; t->call_ms = call_ms;
+    t->device = c.device; t->windows = p->W; t->buckets = 1; t->threads_per_window = 256;
+}
+
+hmcg_host::AcfArgs acf_args(const hmcg_autocorr* p)
+{
+    hmcg_host::AcfArgs a{};
+    a.W = p->W; a.C = p->C; a.L = p->L; a.nd = p->nd; a.round5 = (p->flags & HMCG_ACF_ROUND5) != 0;
+    return a;
+}
+
+// Caller holds c.mu and has made c.device current.  The running sums live in a context-owned arena (as density's piece sums do).
+int acf_device(DeviceCtx& c, const hmcg_autocorr* p, const double* dx, double* dacov, double* ddiag, hipStream_t stream, hmcg_timing* timing)
+{
+    int rc = grow_shared(c, c.acf, acf_work_bytes(p->W, p->C, p->L));
+    if (rc) return rc;
+    HIP_TRY(hipStreamWaitEvent(stream, c.ev_scr, 0));
+    if (timing) HIP_TRY(hipEventRecord(c.ev0, stream));
+    hmcg_host::AcfArgs a = acf_args(p);
+    a.x = dx; a.work = c.acf.base; a.acov = dacov; a.diag = ddiag; a.d_origin = 0; a.n = p->nd; a.pre = 0; a.ld = p->nd_ld;
+    HIP_TRY(launch_autocorr_accumulate(a, stream));
+    HIP_TRY(launch_autocorr_finalize(a, stream));
+    HIP_TRY(hipEventRecord(c.ev_scr, stream));
+    if (timing) {
+        HIP_TRY(hipEventRecord(c.ev1, stream));
+        HIP_TRY(hipEventSynchronize(c.ev1));
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, c.ev0, c.ev1));
+        fill_acf_timing(timing, p, c, ms, 2, 0.0);
+    }
+    return 0;
+}
+
+// Host entry on one device, as dens_host with a given range: one pass of whole-slab chunks through pinned staging, RING buffers
+// deep.  Every chunk is packed with the min(L, d0) draws before it in front (the host holds the whole array), so the device
+// carries nothing from chunk to chunk but the running sums, the pivot and the edge values in the work area.
+int acf_host(DeviceCtx& c, const hmcg_autocorr* p, const double* x, double* acov, double* diag, hmcg_timing* timing)
+{
+    const auto t_call = std::chrono::steady_clock::now();
+    const int W = p->W, C = p->C, L = p->L;
+    long long cap = 0;
+    if (const char* cenv = diag_env("HMCG_CHUNK_DRAWS")) cap = atoll(cenv);
+    const long long cdraws = pred_chunk_draws(p->nd, W, C, cap);
+    const std::vector<PredChunk> chunks = pred_chunks(p->nd, cdraws);
+    const size_t wc = (size_t)W * (size_t)C;
+    const size_t n_acov = wc * (size_t)(L + 1), n_diag = wc * HMCG_ACF_STRIDE;
+    auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
+    const size_t b_acov = up(8 * n_acov), b_diag = up(8 * n_diag), b_out = b_acov + b_diag;
+    const size_t b_work = up(acf_work_bytes(W, C, L));
+    const size_t b_chunk = up(sizeof(double) * wc * (size_t)(cdraws + L));
+    const int nbuf = (int)std::min<size_t>(RING, chunks.size());
+    const size_t need_dev = b_out + b_work + b_chunk * (size_t)nbuf, need_pin = b_out + b_chunk * (size_t)nbuf;
+    if (c.dev.ensure(need_dev) || c.pin.ensure(need_pin)) {
+        set_err("workspace allocation failed (%zu B device, %zu B pinned)", need_dev, need_pin);
+        return HMCG_E_NOMEM;
+    }
+    char* dout = c.dev.base;
+    char* dwork = c.dev.base + b_out;
+    char* dchunk = dwork + b_work;
+    char* pout = c.pin.base;
+    char* pchunk = c.pin.base + b_out;
+
+    hmcg_host::AcfArgs a = acf_args(p);
+    a.work = dwork;
+    a.acov = reinterpret_cast<double*>(dout);
+    a.diag = reinterpret_cast<double*>(dout + b_acov);
+
+    struct Events {
+        std::vector<hipEvent_t> ev;
+        ~Events() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
+    } tev;                                       // two per chunk, around its kernel (created only when timing is asked for)
+    if (timing) {
+        tev.ev.assign(2 * chunks.size() + 2, nullptr);
+        for (hipEvent_t& e : tev.ev) HIP_TRY(hipEventCreate(&e));
+    }
+    for (size_t ci = 0; ci < chunks.size(); ++ci) {
+        const PredChunk& ch = chunks[ci];
+        const int b = (int)(ci % (size_t)nbuf);
+        if (ci >= (size_t)nbuf) HIP_TRY(hipEventSynchronize(c.evk[b]));      // the kernel that read this buffer pair is done
+        double* pb = reinterpret_cast<double*>(pchunk + b_chunk * (size_t)b);
+        double* db = reinterpret_cast<double*>(dchunk + b_chunk * (size_t)b);
+        const long long pre = acf_pre(ch.d0, L);
+        const size_t n = (size_t)(pre + ch.n);
+        for (size_t q = 0; q < wc; ++q) memcpy(pb + q * n, x + q * (size_t)p->nd_ld + (size_t)(ch.d0 - pre), sizeof(double) * n);
+        HIP_TRY(hipMemcpyAsync(db, pb, sizeof(double) * wc * n, hipMemcpyHostToDevice, c.copy));
+        HIP_TRY(hipEventRecord(c.evc[b], c.copy));
+        HIP_TRY(hipStreamWaitEvent(c.stream, c.evc[b], 0));
+        a.x = db; a.d_origin = ch.d0; a.n = ch.n; a.pre = pre; a.ld = (long long)n;
+        if (timing) HIP_TRY(hipEventRecord(tev.ev[2 * ci], c.stream));
+        HIP_TRY(launch_autocorr_accumulate(a, c.stream));
+        if (timing) HIP_TRY(hipEventRecord(tev.ev[2 * ci + 1], c.stream));
+        HIP_TRY(hipEventRecord(c.evk[b], c.stream));
+    }
+    if (timing) HIP_TRY(hipEventRecord(tev.ev[2 * chunks.size()], c.stream));
+    HIP_TRY(launch_autocorr_finalize(a, c.stream));
+    if (timing) HIP_TRY(hipEventRecord(tev.ev[2 * chunks.size() + 1], c.stream));
+    HIP_TRY(hipMemcpyAsync(pout, dout, b_out, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    memcpy(acov, pout, 8 * n_acov);
+    memcpy(diag, pout + b_acov, 8 * n_diag);
+    if (timing) {
+        double kernel_ms = 0.0;
+        for (size_t i = 0; i <= chunks.size(); ++i) {
+            float ms = 0.f;
+            HIP_TRY(hipEventElapsedTime(&ms, tev.ev[2 * i], tev.ev[2 * i + 1]));
+            kernel_ms += ms;
+        }
+        const double call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+        fill_acf_timing(timing, p, c, kernel_ms, (int)chunks.size() + 1, call_ms);
+    }
+    return 0;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1716,6 +1838,34 @@ int hmcg_chain_density(const hmcg_density* p, const double* x, const double* lo_
     std::lock_guard<std::mutex> lk(c->mu);
     HIP_TRY(hipSetDevice(c->phys));
     return dens_host(*c, p, x, lo_hi, range, counts, stats, trace, timing);
+}
+
+int hmcg_chain_autocorr_device(const hmcg_autocorr* p, const double* dx, double* dacov, double* ddiag, void* stream, hmcg_timing* timing)
+{
+    g_err[0] = 0;
+    char msg[160];
+    int rc = check_autocorr(p, dx, dacov, ddiag, msg, sizeof msg);
+    if (rc) { set_err("%s", msg); return rc; }
+    DeviceCtx* c = nullptr;
+    rc = get_context(p->device, &c);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->phys));
+    return acf_device(*c, p, dx, dacov, ddiag, stream ? (hipStream_t)stream : c->stream, timing);
+}
+
+int hmcg_chain_autocorr(const hmcg_autocorr* p, const double* x, double* acov, double* diag, hmcg_timing* timing)
+{
+    g_err[0] = 0;
+    char msg[160];
+    int rc = check_autocorr(p, x, acov, diag, msg, sizeof msg);
+    if (rc) { set_err("%s", msg); return rc; }
+    DeviceCtx* c = nullptr;
+    rc = get_context(p->device, &c);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->phys));
+    return acf_host(*c, p, x, acov, diag, timing);
 }
 
 }  // extern "C"

@@ -170,6 +170,28 @@ class DevicePanel:
             self.last_timing = tm
         return out
 
+    def chain_autocorr(self, var="mu", lags=255, timed=False, round5=True):
+        """Autocovariances and convergence diagnostics of one variable's draws from the panel's own HBM draws
+        (hmcg_chain_autocorr_device).  var: "mu", "sig2", "pi_end" (C = K columns), "A" (C = K * K) or "fcast" (C = 2H); lags: the
+        largest lag L (0..1024, below nrun).  Returns a dict of tensors: acov (W, C, lags + 1), diag (W, C, 8) = mean, variance,
+        tau, ess, mcse, pairs, truncated, rhat; _lib.unpack_chain_autocorr names the parts of their numpy copies.  Enqueued on the
+        library stream behind `run`; with timed=True the call waits and last_timing holds the HIP-event time, otherwise call
+        sync() before reading the tensors."""
+        if var not in _lib.DRAW_KEYS:
+            raise ValueError("var must be one of %s" % (_lib.DRAW_KEYS,))
+        x = getattr(self, var)
+        if x is None:
+            raise _lib.HmcgError("chain_autocorr needs the draws in HBM: the panel was built with keep_draws=False")
+        torch = self.torch
+        Cn = int(x.numel() // (self.W * self.nrun))
+        acf = _lib.make_autocorr(self.W, Cn, self.nrun, self.nrun, lags, self.device_index, round5)
+        f64 = dict(dtype=torch.float64, device=self.dev)
+        out = {"acov": torch.empty((self.W, Cn, max(int(lags), 0) + 1), **f64), "diag": torch.empty((self.W, Cn, _lib.ACF_STRIDE), **f64)}
+        tm = _lib.chain_autocorr_device(acf, x.data_ptr(), out["acov"].data_ptr(), out["diag"].data_ptr(), None, timed)
+        if timed:
+            self.last_timing = tm
+        return out
+
     def sync(self):
         """Wait for the library stream (untimed runs are asynchronous)."""
         self.torch.cuda.synchronize(self.dev)

@@ -20,6 +20,8 @@ ABI.  Names, argument meaning and result layout follow the reference:
     calcmoments         both questions asked of the draws: moments of the predictive mixture (from the files or from the device)
     calcchain           plots/mcplots.jl:24-63 and plots/timeseriesplots.jl:83-142 up to the drawing: binned chain densities over
                         nested prefixes and the running mean (from the files or from the device); chainquantiles, chaindensity
+    calcess             no reference script: autocovariances, integrated autocorrelation time, effective sample size, Monte-Carlo
+                        standard error and split-R-hat of the draws (from the files or from the device); write_chain_ess
 
 New (the reference batches by launching one SLURM task per window,
 slurmscripts/base_estimation.sh:5): `estimatewindows`, one call for many windows.
@@ -387,6 +389,25 @@ class ChainDensity:
         return ChainDensity(self.var, self.columns, self.cuts, self.trace_stride, {k: getattr(self, k)[idx] for k in _lib.DENS_FIELDS})
 
 
+class ChainAutocorr:
+    """Autocovariances and convergence diagnostics of one variable's draws over n windows (end dates) and C columns: acov
+    (n, C, lags + 1) the biased autocovariances at lags 0..lags; mean, variance (divisor n - 1), tau (integrated autocorrelation
+    time, Geyer's initial monotone sequence), ess = draws / tau, mcse = sqrt(variance tau / draws), pairs (int64, the lag pairs
+    the sequence used), truncated (bool: every pair was used, `lags` is too short), rhat (split-R-hat of the chain's two halves),
+    all (n, C); columns: the C column names of the per-draw file."""
+
+    def __init__(self, var, columns, parts):
+        self.var, self.columns = var, list(columns)
+        self.acov = parts["acov"]
+        for name in _lib.ACF_FIELDS:
+            setattr(self, name, parts[name])
+        self.lags = int(self.acov.shape[2]) - 1
+
+    def rows(self, idx):
+        """The same object restricted to the windows idx."""
+        return ChainAutocorr(self.var, self.columns, {k: getattr(self, k)[idx] for k in ("acov",) + _lib.ACF_FIELDS})
+
+
 class BatchResult:
     """Result of estimatewindows: per-window posterior summaries (+ optional draws)."""
 
@@ -402,6 +423,7 @@ class BatchResult:
         self.bias = res.get("bias")            # with bias_horizon: BiasMoments (uncerbias, totalbias, mean, cov) per window
         self.moments = res.get("moments")      # with moment_horizons: MixtureMoments, (W, n_h) arrays
         self.density = res.get("density")      # with density_vars: {var: ChainDensity}
+        self.autocorr = res.get("autocorr")    # with acf_vars: {var: ChainAutocorr}
         self._res = res if keep_draws else None
 
     def samples(self, w):
@@ -413,7 +435,7 @@ class BatchResult:
 
 def estimatewindows(rawdata, dates, endIndices, startIndex=1, keep_draws=False, device=0, window_ids=None, corr=False,
                     cdf_grid=None, cdf_horizons=(0,), bias_horizon=None, moment_horizons=None, density_vars=None,
-                    density_cuts=None, density_bins=64, density_trace=(0, 1), **kwargs):
+                    density_cuts=None, density_bins=64, density_trace=(0, 1), acf_vars=None, acf_lags=255, **kwargs):
     """Batched estimatemodel over many expanding windows (one GPU call).
 
     Window w uses sampleRange = startIndex:endIndices[w], endIndex = endIndices[w]; the
@@ -434,9 +456,18 @@ def estimatewindows(rawdata, dates, endIndices, startIndex=1, keep_draws=False, 
     the binned counts of the chain prefixes density_cuts (default: the whole chain) on density_bins bins over the range of the
     draws, mean and variance of each prefix and the running mean density_trace = (length, stride) (mcplots.jl's plotchain and
     plotchainmean up to the drawing), computed on the device from the 5-digit-rounded draws (_lib.chain_density); the draw
-    arrays are fetched and dropped likewise."""
+    arrays are fetched and dropped likewise.
+    acf_vars: names among mu, sig2, pi_end, A, fcast -> BatchResult.autocorr, {var: ChainAutocorr}: per window and column the
+    autocovariances up to lag acf_lags, the integrated autocorrelation time, effective sample size, Monte-Carlo standard error
+    and split-R-hat, computed on the device from the 5-digit-rounded draws (_lib.chain_autocorr); the draw arrays are fetched
+    and dropped likewise."""
     if startIndex != 1:
         raise ValueError("windows must start at index 1 (see estopt)")
+    if acf_vars is not None:
+        acf_vars = tuple(acf_vars)
+        for var in acf_vars:
+            if var not in DENSITY_FILES:
+                raise ValueError("acf_vars: %r is none of %s" % (var, tuple(DENSITY_FILES)))
     if density_vars is not None:
         density_vars = tuple(density_vars)
         for var in density_vars:
@@ -468,6 +499,8 @@ def estimatewindows(rawdata, dates, endIndices, startIndex=1, keep_draws=False, 
             want += ("mu", "sig2", "pi_end") + (("A",) if any(int(h) > 0 for h in moment_horizons) else ())
         if density_vars is not None:
             want += tuple(density_vars)
+        if acf_vars is not None:
+            want += tuple(acf_vars)
         want = tuple(k for k in _lib.DRAW_KEYS if k in want) or False
     res = _lib.estimate_batch_host(Y, Tw, o0.D, o0.burnin, o0.Nrun, tuple(o0.horizons), yreal, seed=o0.seed,
                                    device=device, want_draws=want, window_ids=window_ids, want_corr=corr)
@@ -493,6 +526,9 @@ def estimatewindows(rawdata, dates, endIndices, startIndex=1, keep_draws=False, 
             parts = _lib.chain_density(res[var], density_cuts, density_bins, None, density_trace, device=device)
             res["density"][var] = ChainDensity(var, _density_columns(o0, var), (o0.Nrun,) if density_cuts is None else density_cuts,
                                                density_trace[1], parts)
+    if acf_vars is not None:
+        res["autocorr"] = {var: ChainAutocorr(var, _density_columns(o0, var), _lib.chain_autocorr(res[var], acf_lags, device=device))
+                           for var in acf_vars}
     return BatchResult(opts, res, keep_draws)
 
 
@@ -1419,4 +1455,108 @@ def write_chain_trace(path, dates, density):
             for i in range(density.trace.shape[2]):
                 rows.append([str(d), name, str((i + 1) * density.trace_stride), _fmt(density.trace[w, c, i])])
     _write_csv(path, ["date", "column", "draws", "mean"], rows)
+    return path
+
+
+# ------------------------------------------- autocorrelation, effective sample size, split-R-hat --
+
+def _geyer(acov, variance, n):
+    """The derived block of include/hmcg.h for one column in fp64: tau, ess, mcse, pairs, truncated."""
+    nan, n = np.float64(np.nan), np.float64(n)
+    a0 = np.float64(acov[0])
+    if not (a0 > 0.0):
+        return nan, nan, nan, 0, False
+    npairs, k = len(acov) // 2, 0
+    tau, prev = np.float64(-1.0), np.float64(np.inf)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        while k < npairs:
+            P = np.float64(acov[2 * k]) / a0 + np.float64(acov[2 * k + 1]) / a0
+            if not (P > 0.0):
+                break
+            P = min(P, prev)
+            tau = tau + np.float64(2.0) * P
+            prev = P
+            k += 1
+        if k == 0:
+            tau = nan
+        return tau, n / tau, np.sqrt((np.float64(variance) * tau) / n), k, k == npairs
+
+
+def _autocorr_from_cells(cells, lags):
+    """The outputs of hmcg_chain_autocorr for one date from the cells (n, C) of its per-draw file, in numpy fp64 with the
+    library's algebra (sums about the pivot p = row 0).  Returns the parts of a ChainAutocorr without the window axis."""
+    n, Cn = cells.shape
+    L = int(lags)
+    if L < 0 or L > _lib.ACF_MAXLAG or L > n - 1:
+        raise ValueError("lags = %d outside 0..min(%d, draws - 1 = %d)" % (L, _lib.ACF_MAXLAG, n - 1))
+    out = {"acov": np.empty((Cn, L + 1)), "pairs": np.zeros(Cn, dtype=np.int64), "truncated": np.zeros(Cn, dtype=bool)}
+    out.update({k: np.empty(Cn) for k in ("mean", "variance", "tau", "ess", "mcse", "rhat")})
+    h = n // 2
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        for c in range(Cn):
+            v = cells[:, c]
+            a = v - v[0]
+            S1, S2, nn = a.sum(), (a * a).sum(), float(n)
+            m = S1 / nn
+            out["mean"][c] = v[0] + m
+            out["variance"][c] = (S2 - S1 * S1 / nn) / (nn - 1.0)
+            H = np.concatenate([[0.0], np.cumsum(a[:L])])
+            T = np.concatenate([[0.0], np.cumsum(a[::-1][:L])])
+            Cl = np.array([np.dot(a[l:], a[:n - l]) for l in range(L + 1)])
+            out["acov"][c] = (Cl - m * (2.0 * S1 - H - T) + (n - np.arange(L + 1)) * m * m) / nn
+            out["tau"][c], out["ess"][c], out["mcse"][c], out["pairs"][c], out["truncated"][c] = _geyer(out["acov"][c], out["variance"][c], n)
+            f, g, hh = a[:h], a[n - h:], float(h)
+            m1, m2 = f.sum() / hh, g.sum() / hh
+            v1 = ((f * f).sum() - f.sum() ** 2 / hh) / (hh - 1.0)
+            v2 = ((g * g).sum() - g.sum() ** 2 / hh) / (hh - 1.0)
+            Wv = (v1 + v2) / 2.0
+            mid = a[h:n - h].sum()                   # the draw between the halves of an odd n: 0 unless it is not finite
+            out["rhat"][c] = np.sqrt(((((hh - 1.0) / hh) * Wv + (m1 - m2) ** 2 / 2.0) + (mid - mid)) / Wv)
+    return out
+
+
+def calcess(datadir, dates, var="mu", lags=255, result=None):
+    """Convergence diagnostics of one variable's chain per end date and column (no reference script computes them): the biased
+    autocovariances at lags 0..lags, the integrated autocorrelation time tau by Geyer's initial monotone sequence, the effective
+    sample size draws / tau, the Monte-Carlo standard error of the mean and the split-R-hat of the chain's two halves.
+    var: mu, sig2, pi_end, A or fcast.
+
+    result=None: every date's per-draw file (`filtered_means_<date>.csv` for mu; see calcchain) is read back and evaluated on
+    the host in numpy; no GPU is touched.
+    result = a BatchResult of estimatewindows(..., acf_vars=(var, ...), acf_lags=lags): the sums were taken on the device from
+    the rounded draws; every date must be one of the result's end dates, and lags must be the result's.
+    Returns (dates, ChainAutocorr)."""
+    dates = [str(d) for d in dates]
+    if var not in DENSITY_FILES:
+        raise ValueError("var must be one of %s" % (tuple(DENSITY_FILES),))
+    if result is not None:
+        d = getattr(result, "autocorr", None)
+        if d is None or var not in d:
+            raise ValueError("result carries no autocorrelation of %s (estimatewindows(..., acf_vars=(%r,)))" % (var, var))
+        d = d[var]
+        if int(lags) != d.lags:
+            raise ValueError("result was computed for other lags")
+        by_date = {str(enddate(o)): w for w, o in enumerate(result.opts)}
+        for x in dates:
+            if x not in by_date:
+                raise ValueError("no window ends on %s" % x)
+        return dates, d.rows([by_date[x] for x in dates])
+    parts, columns = [], None
+    for date in dates:
+        header, rows = _read_csv(os.path.join(datadir, "%s_%s.csv" % (DENSITY_FILES[var], date)))
+        cells = np.array([[float(x) for x in r[1:]] for r in rows])
+        columns = header[1:]
+        parts.append(_autocorr_from_cells(cells, lags))
+    return dates, ChainAutocorr(var, columns, {k: np.array([q[k] for q in parts]) for k in ("acov",) + _lib.ACF_FIELDS})
+
+
+def write_chain_ess(path, dates, diag):
+    """`date,column,mean,variance,tau,ess,mcse,pairs,truncated,rhat`: one row per end date and column of a ChainAutocorr.  Our
+    layout: the reference writes no such file."""
+    rows = []
+    for w, d in enumerate(dates):
+        for c, name in enumerate(diag.columns):
+            rows.append([str(d), name] + [_fmt(getattr(diag, k)[w, c]) for k in ("mean", "variance", "tau", "ess", "mcse")] +
+                        [str(int(diag.pairs[w, c])), str(int(diag.truncated[w, c])), _fmt(diag.rhat[w, c])])
+    _write_csv(path, ["date", "column", "mean", "variance", "tau", "ess", "mcse", "pairs", "truncated", "rhat"], rows)
     return path

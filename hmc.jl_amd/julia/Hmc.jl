@@ -21,7 +21,8 @@
 # mixture_moments: what code/skewness.jl and code/alt_forecasts.jl ask of the summary rows, asked of the draws
 # (hmcg_mixture_moments); calcskewness / altforecasts: the two scripts themselves, in closed form.  calcchain /
 # chain_density: the binned chain densities and running means plots/mcplots.jl and plots/timeseriesplots.jl draw
-# (hmcg_chain_density).  runaggregate /
+# (hmcg_chain_density).  calcess / chain_autocorr: autocovariances, integrated autocorrelation time, effective sample size,
+# Monte-Carlo standard error and split-R-hat of the draws (hmcg_chain_autocorr; no reference script).  runaggregate /
 # calcdispersion of the reference work unchanged on the files written here (same names, columns and float text).
 #
 # Reference lines mirrored: estopt src/Hmc.jl:17-73, accessors :85-107, makedate :573-582,
@@ -161,6 +162,18 @@ struct hmcg_density                   # include/hmcg.h: chain densities and runn
     trace_len::Int32
     flags::Int32
     trace_stride::Int64
+end
+const HMCG_ACF_ROUND5 = Int32(1)
+const HMCG_ACF_STRIDE = 8
+struct hmcg_autocorr                  # include/hmcg.h: autocorrelation, effective sample size and split-R-hat of the draws
+    struct_size::Int32
+    W::Int32
+    C::Int32
+    device::Int32
+    nd::Int64
+    nd_ld::Int64
+    L::Int32
+    flags::Int32
 end
 
 last_error() = unsafe_string(ccall((:hmcg_last_error, LIBHMCG), Cstring, ()))
@@ -551,6 +564,58 @@ function calcchain(opts::Vector{estopt}, var::Symbol=:μ; cuts=nothing, bins::In
     pick(s) = var == :πe ? s.πb[:, 1, :] : getfield(s, var)
     x = cat((pick(s) for s in samples)...; dims=var == :A ? 4 : 3)
     return ([enddate(o) for o in opts], chain_density(x; cuts=cuts, bins=bins, trace=trace, device=device)...)
+end
+
+# ---- autocorrelation, effective sample size and split-R-hat of the draws (no reference script) ------------------------------
+_autocorr(W, C, nd, ld, lags, device, round5) =
+    hmcg_autocorr(Int32(sizeof(hmcg_autocorr)), Int32(W), Int32(C), Int32(device), Int64(nd), Int64(ld), Int32(lags),
+                  round5 ? HMCG_ACF_ROUND5 : Int32(0))
+
+"""
+    chain_autocorr(x; lags=255, device=0, round5=true) -> (acov (lags + 1, C, W), diag (8, C, W))
+
+hmcg_chain_autocorr over ONE host draw array in a layout estimatewindows fills, draw index first and window last -- μ, σ, πe
+(nrun, K, W), A (nrun, K, K, W), forecasts (nrun, 2H, W); the axes between count as the C columns: per window and column the
+biased autocovariances at lags 0:lags, and diag = mean, variance, tau (integrated autocorrelation time, Geyer's initial monotone
+sequence), ess = nrun / tau, mcse = sqrt(variance * tau / nrun), pairs, truncated (1: `lags` is too short), rhat (split-R-hat of
+the chain's two halves).
+"""
+function chain_autocorr(x::Array{Float64}; lags::Integer=255, device::Integer=0, round5::Bool=true)
+    nrun, W = size(x, 1), size(x, ndims(x))
+    C = div(length(x), nrun * W)
+    acov = Array{Float64}(undef, lags + 1, C, W)
+    diag = Array{Float64}(undef, HMCG_ACF_STRIDE, C, W)
+    rc = GC.@preserve x acov diag ccall((:hmcg_chain_autocorr, LIBHMCG), Cint,
+        (Ref{hmcg_autocorr}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}),
+        _autocorr(W, C, nrun, nrun, lags, device, round5), x, acov, diag, C_NULL)
+    rc == 0 || error("libhmcgibbs rc=$rc: $(last_error())")
+    return acov, diag
+end
+
+"""
+    chain_autocorr_device(W, C, nd, ld, dx, dacov, ddiag; lags=255, device=0, round5=true, stream=C_NULL)
+
+hmcg_chain_autocorr_device over device pointers; enqueued on `stream` (C_NULL: the library's own) and not waited for.
+"""
+function chain_autocorr_device(W, C, nd, ld, dx::Ptr{Float64}, dacov::Ptr{Float64}, ddiag::Ptr{Float64}; lags::Integer=255,
+                               device::Integer=0, round5::Bool=true, stream::Ptr{Cvoid}=C_NULL)
+    rc = ccall((:hmcg_chain_autocorr_device, LIBHMCG), Cint,
+               (Ref{hmcg_autocorr}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}, Ptr{Cvoid}),
+               _autocorr(W, C, nd, ld, lags, device, round5), dx, dacov, ddiag, stream, C_NULL)
+    rc == 0 || error("libhmcgibbs rc=$rc: $(last_error())")
+    return nothing
+end
+
+"""
+    calcess(opts, var=:μ; lags=255, device=0) -> (dates, acov, diag)
+
+Estimates the windows and takes the convergence diagnostics of one variable's chain (:μ, :σ, :πe, :A or :forecasts) on the device.
+"""
+function calcess(opts::Vector{estopt}, var::Symbol=:μ; lags::Integer=255, device::Integer=0)
+    samples, _, _ = estimatewindows(opts; device=device)
+    pick(s) = var == :πe ? s.πb[:, 1, :] : getfield(s, var)
+    x = cat((pick(s) for s in samples)...; dims=var == :A ? 4 : 3)
+    return ([enddate(o) for o in opts], chain_autocorr(x; lags=lags, device=device)...)
 end
 
 function _summary_rows(datadir, stem)

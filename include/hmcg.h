@@ -41,6 +41,10 @@
  *                                  drawing: per window and draw column the binned counts of every prefix, its mean and
  *                                  variance, and the running mean, taken from the draw arrays instead of the per-draw CSV
  *                                  files the scripts read back.
+ *   hmcg_chain_autocorr[_device]   no reference script: the convergence diagnostics a user of the sampler asks for next --
+ *                                  per window and draw column the autocovariances up to a largest lag, the integrated
+ *                                  autocorrelation time by Geyer's initial monotone sequence, the effective sample size, the
+ *                                  Monte-Carlo standard error of the mean and the split-R-hat of the chain's two halves.
  *
  * Conventions: plain C structs, fixed-width ints, no C++ types or exceptions cross
  * the boundary.  Return 0 on success, negative on API misuse (HMCG_E_*), positive
@@ -430,6 +434,52 @@ int hmcg_chain_density_device(const hmcg_density* p, const double* dx, const dou
  * kernel of the one before -- twice with lo_hi NULL (the range, then the counts), once with lo_hi given. */
 int hmcg_chain_density(const hmcg_density* p, const double* x, const double* lo_hi, double* range, int64_t* counts, double* stats,
                        double* trace, hmcg_timing* timing);
+
+/* ---- autocorrelation, effective sample size and split-R-hat of the draws ----------------------------------------------------
+ * One generic entry over ONE draw array x of C columns per window, in the layout of hmcg_chain_density: element (d, c, w) at
+ * d + nd_ld * (c + C * w).  With x' = the value rounded as a CSV cell is under HMCG_ACF_ROUND5 and x' = x otherwise, n = nd,
+ * p = x' of the window's draw 0 and a_d = x'_d - p (one rounded fp64 subtraction), per window w and column c:
+ *   S1 = sum a_d, S2 = sum a_d^2, m = S1 / n, mean = p + m, variance = (S2 - S1 * S1 / n) / (n - 1)  (density's `stats`).
+ *   C_l = sum_{d = l}^{n - 1} a_d a_{d - l}, l = 0..L;  H_l = a_0 + .. + a_{l - 1},  T_l = a_{n - 1} + .. + a_{n - l}
+ *   (running sums in l, H_0 = T_0 = 0).
+ *   acov[w][c][l] = (C_l - m (2 S1 - H_l - T_l) + (n - l) m m) / n: the biased autocovariance about the sample mean, exact in
+ *     the pivoted form.  Operation order, every step a rounded fp64 operation of its own:
+ *       q = ((2 S1) - H_l) - T_l;  r = C_l - m q;  s = ((double)(n - l) * m) * m;  acov_l = (r + s) / n.
+ *   From acov, likewise one rounded operation per step, nothing fused (this part is ABI; tests restate it in numpy and compare bits):
+ *     !(acov_0 > 0): tau, ess, mcse NaN, pairs = 0, truncated = 0.  Else rho_l = acov_l / acov_0 and Geyer's initial monotone
+ *     sequence over (L + 1) / 2 pairs: tau = -1, prev = +inf; for k = 0, 1, ..: P = rho_2k + rho_2k+1; stop if !(P > 0);
+ *     if P > prev then P = prev; tau = tau + 2 P; prev = P.  pairs = the pairs used; truncated = 1 when every pair was used
+ *     and none stopped the sequence (the lag window is too short), else 0 (L = 0 has no pair at all: truncated = 1); pairs = 0 with acov_0 > 0 gives tau NaN.
+ *     ess = n / tau;  mcse = sqrt((variance * tau) / n).
+ *   Split-R-hat of the single chain: h = n / 2 (integer), halves [0, h) and [n - h, n), S1 and S2 of each half about p:
+ *     m_i = S1_i / h, v_i = (S2_i - S1_i * S1_i / h) / (h - 1), Wv = (v1 + v2) / 2,
+ *     varplus = (((h - 1) / h) * Wv + ((m1 - m2) * (m1 - m2)) / 2) + (S1_mid - S1_mid), rhat = sqrt(varplus / Wv).  S1_mid is the
+ *     draw between the halves of an odd n (0 for an even n): the last term is 0 unless that draw is not finite, which then
+ *     reaches rhat as it reaches every other output.  Nothing is special-cased: h < 2 or a constant column gives NaN by 0 / 0.
+ *   diag[w][c][HMCG_ACF_STRIDE] = mean, variance, tau, ess, mcse, pairs, truncated, rhat (pairs and truncated as doubles).
+ * NaN or inf anywhere in a column makes every output of that column NaN or inf (acov: NaN), pairs = truncated = 0.
+ * Deterministic: a product (d, d - l) belongs to the 1024-draw slab of d; a slab's sum per lag is taken in an order fixed by
+ * the place in the slab and L, the slab sums are added in ascending slab order into running accumulators; S1 and S2 are
+ * taken per slab and per third of the chain ([0, h), [h, n - h), [n - h, n)) by a fixed butterfly with unfused squares, the
+ * slabs added in order, S1 = (first + middle) + second.  No floating-point atomics: bit-identical from run to run, from both entries and for every
+ * chunking of the host entry's upload (HMCG_CHUNK_DRAWS under HMCG_DIAG=1).
+ * Misuse (HMCG_E_BADARG, checked before any HIP call): struct_size, W < 1, C outside 1..HMCG_MAXK^2, nd < 1 or > 2^53,
+ * nd_ld < nd, L outside 0..HMCG_ACF_MAXLAG, L > nd - 1, W * C above 2^31 - 1 blocks, a NULL x / acov / diag. */
+#define HMCG_ACF_ROUND5 1
+#define HMCG_ACF_MAXLAG 1024
+#define HMCG_ACF_STRIDE 8
+typedef struct hmcg_autocorr {
+    int32_t struct_size, W, C, device;
+    int64_t nd, nd_ld;                 /* draws per window; leading dimension of the draw array (>= nd) */
+    int32_t L, flags;                  /* largest lag 0..min(HMCG_ACF_MAXLAG, nd - 1); HMCG_ACF_ROUND5 */
+} hmcg_autocorr;
+/* Device entry: every data pointer is HBM-resident on p->device; enqueued on `stream` (NULL: the library's own) behind the
+ * library's earlier work there; returns after enqueueing unless `timing` is given (kernel_ms: HIP events around the kernels). */
+int hmcg_chain_autocorr_device(const hmcg_autocorr* p, const double* dx, double* dacov /* [W][C][L + 1] */,
+                               double* ddiag /* [W][C][HMCG_ACF_STRIDE] */, void* stream, hmcg_timing* timing);
+/* Host entry (blocking): uploads the draws once in chunks of whole slabs through pinned staging, each chunk with the
+ * min(L, d0) draws before it in front, the copy of one chunk beside the kernel of the one before. */
+int hmcg_chain_autocorr(const hmcg_autocorr* p, const double* x, double* acov, double* diag, hmcg_timing* timing);
 
 /* ---- per-draw CSV output (host code, no GPU): basicsave / saveresults, src/Hmc.jl:707-748 ------------------------------
  * The five per-window files `filtered_means_<date>.csv`, `filtered_variances_<date>.csv`, `filtered_state_probs_<date>.csv`,
