@@ -20,6 +20,7 @@ import numpy as np
 import pytest
 
 import config_range_cases as cr
+import corr_cases as cc
 import device_entry as de
 from hmc_jl_amd import _lib
 from device_entry import assert_device_equals_host, kept_after
@@ -244,7 +245,8 @@ def test_cut_chain_equals_one_launch(hmclib, monkeypatch, c):
 @pytest.mark.parametrize("cid", ["reg-K3-h-H8", "lds-K8-H8"])
 def test_corr_does_not_depend_on_the_number_of_horizons(hmclib, monkeypatch, cid):
     """extras.corr reads the forecast of horizons[0] out of a 2H-wide block: the H = 8 run's matrix equals the H = 1 run's bit
-    for bit, and numpy.corrcoef of the rounded draws within the 1e-10 of test_gpu_corr.py (reference in long double)."""
+    for bit, and the Pearson matrix of the rounded draws in long double within min(the bound derived in corr_cases, 1e-10), as in
+    test_gpu_corr.py."""
     c = cr.BY_ID[cid]
     set_env(monkeypatch, c)
     args8, kw8 = cr.gpu_call(c, sweeps=cr.CORR_SWEEPS, want_corr=True)
@@ -262,6 +264,8 @@ def test_corr_does_not_depend_on_the_number_of_horizons(hmclib, monkeypatch, cid
         assert np.array_equal(np.isfinite(got), ok), (cid, w)
         assert T < 10 or ok.all(), (cid, w)                    # (a two-step window's draws may be constant after rounding)
         assert not ok.any() or float(np.abs(got[ok] - ref[ok]).max()) < 1e-10, (cid, w)
+        # ... and within min(the derived bound, 1e-10) of corr_cases' reference (moments about the first draw, long double)
+        cc.check(got[None], cc.reference(cols[None], cols.shape[-1]), "%s window %d" % (cid, w), cap=1e-10)
 
 
 # ---- the seed's high word ----

@@ -1,12 +1,31 @@
 """extras.corr: correlations between the per-draw outputs, accumulated on the device (calccorr, src/Hmc.jl:1094-1163).
 
-Checker: numpy.corrcoef of the 5-digit-rounded draws the same call returned -- the matrix upstream's calccorr computes
-from the per-draw CSV cells (`cor(Matrix(df))`, :1125; columns mu | sigma | pi | vec(A) | first forecast, :1122).
-Tolerance 1e-10 absolute: the device accumulates second moments about the first draw in fp64, numpy centres on the mean."""
+Checker: the Pearson matrix of the 5-digit-rounded draws the same call returned -- the matrix upstream's calccorr computes
+from the per-draw CSV cells (`cor(Matrix(df))`, :1125; columns mu | sigma | pi | vec(A) | first forecast, :1122) -- in
+np.longdouble (corr_cases.reference), every cell within min(the bound derived in tests/corr_cases.py, 1e-10); a cell outside
+that derivation's guard (a column all but constant after rounding) keeps 1e-10.  numpy.corrcoef in fp64 is kept beside it for the
+NaN positions.  K = 2..8 run every draw_moments_kernel instantiation through the ABI (K = 5, 6: <4>, <8>), on the
+register-resident, the LDS-resident and the streaming route.  The kernels by themselves: tests/test_gpu_corr_kernels.py."""
 import numpy as np
 import pytest
 
+import corr_cases as cc
+import kernel_tables as kt
+
 pytestmark = pytest.mark.gpu
+CAP = 1e-10
+
+
+def _columns(res):
+    W, nd = res["mu"].shape[0], res["mu"].shape[-1]
+    return cc.columns(res["mu"], res["sig2"], res["pi_end"], res["A"].reshape(W, -1, nd), res["fcast"])
+
+
+def _check_against_reference(res, label):
+    """Every window's matrix against the long-double reference of the call's own draws; skipped windows (status != 0) apart."""
+    cols = _columns(res)
+    ok = res["status"] == 0
+    return cc.check(res["corr"][ok], cc.reference(cols[ok], cols.shape[-1]), label, cap=CAP)
 
 
 def _round5(a):
@@ -21,7 +40,8 @@ def _expected(res, w, K):
         return np.corrcoef(_round5(np.stack(cols)))
 
 
-@pytest.mark.parametrize("K,T,nrun,W", [(3, 400, 1500, 5), (2, 300, 700, 3), (4, 250, 600, 2), (8, 600, 300, 2)])
+@pytest.mark.parametrize("K,T,nrun,W", [(3, 400, 1500, 5), (2, 300, 700, 3), (4, 250, 600, 2), (8, 600, 300, 2),
+                                        (5, 300, 129, 2), (6, 300, 129, 2), (7, 300, 129, 2)])
 def test_corr_matches_numpy(K, T, nrun, W):
     from hmc_jl_amd import _lib, synth
     Y, Tw, fut = synth.generate_panel(W, T, K)
@@ -29,6 +49,8 @@ def test_corr_matches_numpy(K, T, nrun, W):
     assert (res["status"] == 0).all()
     NC = 3 * K + K * K + 1
     assert res["corr"].shape == (W, NC, NC)
+    assert res["streaming"] == 0 and (res["occupancy"] == 0) == (K >= 5)          # K >= 5: the LDS-resident kernel
+    _check_against_reference(res, "K=%d T=%d nrun=%d" % (K, T, nrun))
     for w in range(W):
         exp = _expected(res, w, K)
         got = res["corr"][w]
@@ -37,6 +59,20 @@ def test_corr_matches_numpy(K, T, nrun, W):
         assert np.abs(got[ok] - exp[ok]).max() < 1e-10
         assert np.array_equal(got[ok], got.T[ok])
         assert (np.diag(got)[np.isfinite(np.diag(got))] == 1.0).all()
+
+
+def test_corr_on_the_streaming_route():
+    """One window beyond the LDS (kernel_tables.STREAM_T: streaming whatever the kernel's static share), K = 5, few draws."""
+    from hmc_jl_amd import _lib, synth
+    K, T, nrun = 5, kt.STREAM_T, 24
+    assert kt.dyn_bytes((T + kt.NT - 1) // kt.NT) > kt.LDS_LIMIT >= kt.dyn_bytes((T - kt.NT + kt.NT - 1) // kt.NT)
+    Y, Tw, fut = synth.generate_panel(1, T, K)
+    res = _lib.estimate_batch_host(Y, Tw, K, 2, nrun, (12,), fut[:, 11:12], want_corr=True)
+    assert (res["status"] == 0).all() and res["streaming"] and res["occupancy"] == 0
+    exp = _expected(res, 0, K)
+    assert np.array_equal(np.isfinite(res["corr"][0]), np.isfinite(exp))
+    assert np.isfinite(res["corr"][0]).sum() > 0.5 * exp.size
+    _check_against_reference(res, "streaming K=%d T=%d nrun=%d" % (K, T, nrun))
 
 
 def test_corr_is_chunk_invariant_and_needs_no_draw_copy(monkeypatch):
@@ -55,6 +91,12 @@ def test_corr_is_chunk_invariant_and_needs_no_draw_copy(monkeypatch):
     assert b["launches"] > a["launches"] >= 1 and d["launches"] == 1
     for o in (b, c, d):
         assert np.array_equal(a["corr"], o["corr"], equal_nan=True)
+    monkeypatch.delenv("HMCG_NO_CHUNKS")
+    for chunk in (63, 64, 65):                   # below, on and above the 64-draw tile of draw_moments_kernel
+        monkeypatch.setenv("HMCG_CHUNK_DRAWS", str(chunk))
+        o = _lib.estimate_batch_host(Y, Tw, K, 20, nrun, **kw)
+        assert o["launches"] > b["launches"]
+        assert np.array_equal(a["corr"], o["corr"], equal_nan=True), chunk
     assert "mu" not in c and np.array_equal(a["summary"], c["summary"])
 
 
@@ -104,12 +146,11 @@ def test_calccorr_device_matrices_equal_the_file_route(inflation, tmp_path):
 
 def test_corr_device_entry_equals_host_entry():
     """hmcg_estimate_batch_device with extras.corr (device pointers, one launch) against the chunked host entry: the same
-    bits -- the moments are accumulated in draw order whatever the chunking.  K = 8 runs the LDS-resident kernel, whose pdf
-    scratch shares the device context with the moment tables."""
+    bits -- the moments are accumulated in draw order whatever the chunking.  K >= 5 runs the LDS-resident kernel, whose pdf
+    scratch shares the device context with the moment tables; K = 5, 6, 7 are draw_moments_kernel<4>, <8>, <16>."""
     from hmc_jl_amd import _lib, synth
     from hmc_jl_amd.device import DevicePanel
-    for K, T, nrun in ((3, 500, 800), (8, 700, 200)):
-        W = 6
+    for K, T, nrun, W in ((3, 500, 800, 6), (8, 700, 200, 6), (5, 300, 129, 2), (6, 300, 129, 2), (7, 300, 129, 2)):
         Y, Tw, fut = synth.generate_panel(W, T, K)
         host = _lib.estimate_batch_host(Y, Tw, K, 20, nrun, (12,), fut[:, 11:12], want_corr=True)
         p = DevicePanel(Y, Tw, K, nrun, (12,), fut[:, 11:12], corr=True)
