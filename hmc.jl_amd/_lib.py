@@ -217,6 +217,18 @@ def _np_ptr(a):
     return None if a is None else C.c_void_p(a.ctypes.data)
 
 
+def _vp(x):
+    """A raw device pointer or stream (an int; 0 / None: NULL) as a void pointer."""
+    return None if not x else C.c_void_p(int(x))
+
+
+def _device_call(fn, struct, pointers, stream, timed):
+    """One *_device entry: fn(struct, pointers..., stream, timing).  Returns the Timing struct when timed, else None."""
+    tm = Timing() if timed else None
+    _check(fn(C.byref(struct), *[_vp(x) for x in pointers], _vp(stream), C.byref(tm) if timed else None))
+    return tm
+
+
 # ---- one table of a call's buffers (the Python twin of host_buffers in csrc/host_util.hpp) ----
 Row = collections.namedtuple("Row", "name pos dtype shape io request carried nan")
 _f64, _i32 = np.float64, np.int32
@@ -411,18 +423,8 @@ def estimate_batch_device(cfg, dY, dT, dyreal, dmu, dsig2, dA, dpi_end, dfcast, 
                           extras=None, stream=None, timed=True):
     """hmcg_estimate_batch_device over raw device pointers (ints, e.g. torch
     tensor.data_ptr()).  Returns the Timing struct when timed, else None."""
-    L = load()
-    tm = Timing() if timed else None
-
-    def vp(x):
-        return None if not x else C.c_void_p(int(x))
-
-    rc = L.hmcg_estimate_batch_device(C.byref(cfg), vp(dY), vp(dT), vp(dyreal), vp(dmu), vp(dsig2), vp(dA),
-                                      vp(dpi_end), vp(dfcast), vp(dsummary), vp(dstatus),
-                                      C.byref(extras) if extras is not None else None, vp(stream),
-                                      C.byref(tm) if timed else None)
-    _check(rc)
-    return tm
+    pointers = (dY, dT, dyreal, dmu, dsig2, dA, dpi_end, dfcast, dsummary, dstatus, C.addressof(extras) if extras is not None else None)
+    return _device_call(load().hmcg_estimate_batch_device, cfg, pointers, stream, timed)
 
 
 def make_predictive(W, K, nd, nd_ld, G, horizons=(0,), device=0, round5=True):
@@ -466,14 +468,7 @@ def predictive_cdf_device(pred, dmu, dsig2, dpi_end, dA, dgrid, dcdf, stream=Non
     """hmcg_predictive_cdf_device over raw device pointers (ints, e.g. torch tensor.data_ptr(); dA 0 / None when every horizon
     is 0); pred: make_predictive(...).  Enqueued on `stream` (None: the library's own).  Returns the Timing struct when timed
     (the call then waits for completion), else None."""
-    tm = Timing() if timed else None
-
-    def vp(x):
-        return None if not x else C.c_void_p(int(x))
-
-    _check(load().hmcg_predictive_cdf_device(C.byref(pred), vp(dmu), vp(dsig2), vp(dpi_end), vp(dA), vp(dgrid), vp(dcdf),
-                                             vp(stream), C.byref(tm) if timed else None))
-    return tm
+    return _device_call(load().hmcg_predictive_cdf_device, pred, (dmu, dsig2, dpi_end, dA, dgrid, dcdf), stream, timed)
 
 
 def make_bias(W, K, nd, nd_ld, horizon=12, H=0, device=0, round5=True):
@@ -527,14 +522,7 @@ def bias_moments_device(bias, dmu, dpi_end, dA, dfcast, dout, stream=None, timed
     """hmcg_bias_moments_device over raw device pointers (ints, e.g. torch tensor.data_ptr(); dA 0 / None when the horizon is 0,
     dfcast 0 / None for no totalbias); bias: make_bias(...).  Enqueued on `stream` (None: the library's own).  Returns the
     Timing struct when timed (the call then waits for completion), else None."""
-    tm = Timing() if timed else None
-
-    def vp(x):
-        return None if not x else C.c_void_p(int(x))
-
-    _check(load().hmcg_bias_moments_device(C.byref(bias), vp(dmu), vp(dpi_end), vp(dA), vp(dfcast), vp(dout), vp(stream),
-                                           C.byref(tm) if timed else None))
-    return tm
+    return _device_call(load().hmcg_bias_moments_device, bias, (dmu, dpi_end, dA, dfcast, dout), stream, timed)
 
 
 def make_mixmom(W, K, nd, nd_ld, horizons=(0,), device=0, round5=True):
@@ -586,14 +574,7 @@ def mixture_moments_device(mix, dmu, dsig2, dpi_end, dA, dout, stream=None, time
     """hmcg_mixture_moments_device over raw device pointers (ints, e.g. torch tensor.data_ptr(); dA 0 / None when every horizon
     is 0); mix: make_mixmom(...).  Enqueued on `stream` (None: the library's own).  Returns the Timing struct when timed (the
     call then waits for completion), else None."""
-    tm = Timing() if timed else None
-
-    def vp(x):
-        return None if not x else C.c_void_p(int(x))
-
-    _check(load().hmcg_mixture_moments_device(C.byref(mix), vp(dmu), vp(dsig2), vp(dpi_end), vp(dA), vp(dout), vp(stream),
-                                              C.byref(tm) if timed else None))
-    return tm
+    return _device_call(load().hmcg_mixture_moments_device, mix, (dmu, dsig2, dpi_end, dA, dout), stream, timed)
 
 
 def make_density(W, Cn, nd, nd_ld, cuts=None, bins=64, trace=(0, 1), device=0, round5=True):
@@ -656,14 +637,7 @@ def chain_density_device(dens, dx, dlo_hi, drange, dcounts, dstats, dtrace, stre
     """hmcg_chain_density_device over raw device pointers (ints, e.g. torch tensor.data_ptr(); dlo_hi 0 / None for the automatic
     range, dtrace 0 / None with no trace); dens: make_density(...).  Enqueued on `stream` (None: the library's own).  Returns
     the Timing struct when timed (the call then waits for completion), else None."""
-    tm = Timing() if timed else None
-
-    def vp(x):
-        return None if not x else C.c_void_p(int(x))
-
-    _check(load().hmcg_chain_density_device(C.byref(dens), vp(dx), vp(dlo_hi), vp(drange), vp(dcounts), vp(dstats), vp(dtrace),
-                                            vp(stream), C.byref(tm) if timed else None))
-    return tm
+    return _device_call(load().hmcg_chain_density_device, dens, (dx, dlo_hi, drange, dcounts, dstats, dtrace), stream, timed)
 
 
 def make_autocorr(W, Cn, nd, nd_ld, lags=255, device=0, round5=True):
@@ -713,13 +687,7 @@ def chain_autocorr_device(acf, dx, dacov, ddiag, stream=None, timed=False):
     """hmcg_chain_autocorr_device over raw device pointers (ints, e.g. torch tensor.data_ptr()); acf: make_autocorr(...).
     Enqueued on `stream` (None: the library's own).  Returns the Timing struct when timed (the call then waits for completion),
     else None."""
-    tm = Timing() if timed else None
-
-    def vp(x):
-        return None if not x else C.c_void_p(int(x))
-
-    _check(load().hmcg_chain_autocorr_device(C.byref(acf), vp(dx), vp(dacov), vp(ddiag), vp(stream), C.byref(tm) if timed else None))
-    return tm
+    return _device_call(load().hmcg_chain_autocorr_device, acf, (dx, dacov, ddiag), stream, timed)
 
 
 def format_float(x):

@@ -18,6 +18,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <climits>
 #include <cstdarg>
 #include <cstdlib>
 #include <cstdio>
@@ -98,6 +99,12 @@ struct Arena {
         if (base) { if (pinned) (void)hipHostFree(base); else (void)hipFree(base); }
         base = nullptr; cap = 0;
     }
+};
+
+// Events that time launches, in pairs around each; released on every path out of a call.
+struct Events {
+    std::vector<hipEvent_t> ev;
+    ~Events() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
 };
 
 using namespace hmcg_host;
@@ -232,23 +239,24 @@ void destroy_context(DeviceCtx& c)
     c.device = c.phys = -1;
 }
 
-int validate(const hmcg_config* cfg)
+// Argument rules of hmcg_config; 0 or HMCG_E_BADARG with the reason in msg (as the check_* of the statistics).
+int validate(const hmcg_config* cfg, char* msg, size_t nmsg)
 {
-    if (!cfg) { set_err("cfg is NULL"); return HMCG_E_BADARG; }
+    if (!cfg) { snprintf(msg, nmsg, "cfg is NULL"); return HMCG_E_BADARG; }
     if (cfg->struct_size != (int32_t)sizeof(hmcg_config)) {
-        set_err("hmcg_config.struct_size %d != %d", cfg->struct_size, (int)sizeof(hmcg_config));
+        snprintf(msg, nmsg, "hmcg_config.struct_size %d != %d", cfg->struct_size, (int)sizeof(hmcg_config));
         return HMCG_E_BADARG;
     }
     if (cfg->W < 1 || cfg->K < 2 || cfg->K > HMCG_MAXK || cfg->ldY < 2 || cfg->burnin < 0 || cfg->nrun < 0 ||
         cfg->H < 0 || cfg->H > HMCG_MAXH || cfg->max_T < 0 || cfg->max_T > cfg->ldY || cfg->sweep_base < 0 || cfg->sweep_count < 0 || cfg->n_samples < 0 || cfg->kappa < 0.0 || cfg->min_T < 0) {
-        set_err("bad hmcg_config (W=%d K=%d ldY=%d max_T=%d burnin=%d nrun=%d H=%d)", cfg->W, cfg->K, cfg->ldY,
+        snprintf(msg, nmsg, "bad hmcg_config (W=%d K=%d ldY=%d max_T=%d burnin=%d nrun=%d H=%d)", cfg->W, cfg->K, cfg->ldY,
                 cfg->max_T, cfg->burnin, cfg->nrun, cfg->H);
         return HMCG_E_BADARG;
     }
     for (int h = 0; h < cfg->H; ++h)
-        if (cfg->horizons[h] < 0) { set_err("negative horizon"); return HMCG_E_BADARG; }
+        if (cfg->horizons[h] < 0) { snprintf(msg, nmsg, "negative horizon"); return HMCG_E_BADARG; }
     if ((long long)(cfg->n_samples > 1 ? cfg->n_samples : 1) * ((long long)cfg->burnin + cfg->nrun) > 0x7fffffffLL) {
-        set_err("n_samples * (burnin + nrun) exceeds 2^31 - 1 sweeps");
+        snprintf(msg, nmsg, "n_samples * (burnin + nrun) exceeds 2^31 - 1 sweeps");
         return HMCG_E_BADARG;
     }
     return 0;
@@ -649,10 +657,7 @@ struct HostCall {
     hmcg::KernelParams base{};
     // per-chunk timing events, two per chunk: around the sweep kernel(s) alone -- the copy-out of the last chunk rides the
     // same stream behind its kernel and is not kernel time.  (Created only when timing is requested; released on every path.)
-    struct TimingEvents {
-        std::vector<hipEvent_t> ev;
-        ~TimingEvents() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
-    } tev;
+    Events tev;
 
     size_t row(int i) const { return idx ? (size_t)idx[i] : (size_t)i; }
     // HMCG_TRACE=1 (diagnostics): host-side timeline of the call on stderr -- where the wall time beyond the kernels goes
@@ -959,6 +964,150 @@ int run_host_on_device(DeviceCtx& c, const hmcg_config* cfg, const int32_t* idx,
     return rc;
 }
 
+// ---- statistics of the draws: what the five pairs of entries below share --------------------------------------------------------
+
+// What a statistic's hmcg_timing says of its kernels beside the times and the launch count.
+struct StatShape { int windows, threads_per_window, lds_bytes; };
+
+void fill_stat_timing(hmcg_timing* t, const DeviceCtx& c, const StatShape& sh, double kernel_ms, int launches, double call_ms)
+{
+    memset(t, 0, sizeof *t);
+    t->kernel_ms = kernel_ms; t->launches = launches; t->call_ms = call_ms;
+    t->device = c.device; t->windows = sh.windows; t->buckets = 1;
+    t->threads_per_window = sh.threads_per_window; t->lds_bytes = sh.lds_bytes;
+}
+
+// The frame of a statistic's device entry.  Its sums live in a context-owned arena (as the moment tables do): what `body`
+// enqueues on `stream` is ordered behind the arena's last use on any stream (ev_scr) and becomes that last use.  With `timing`
+// the call waits for the launches and reports their time.  Caller holds c.mu and has made c.device current.
+template <class Body>
+int stat_device(DeviceCtx& c, Arena& work, size_t work_bytes, hipStream_t stream, hmcg_timing* timing, const StatShape& sh, int launches,
+                Body body)
+{
+    int rc = grow_shared(c, work, work_bytes);
+    if (rc) return rc;
+    HIP_TRY(hipStreamWaitEvent(stream, c.ev_scr, 0));
+    if (timing) HIP_TRY(hipEventRecord(c.ev0, stream));
+    if ((rc = body())) return rc;
+    HIP_TRY(hipEventRecord(c.ev_scr, stream));
+    if (timing) {
+        HIP_TRY(hipEventRecord(c.ev1, stream));
+        HIP_TRY(hipEventSynchronize(c.ev1));
+        float ms = 0.f;
+        HIP_TRY(hipEventElapsedTime(&ms, c.ev0, c.ev1));
+        fill_stat_timing(timing, c, sh, ms, launches, 0.0);
+    }
+    return 0;
+}
+
+// Columns 0..cols-1 of src (leading dimension ld), draws [d0, d0 + n) of each, packed with leading dimension n; returns the end.
+double* pack_columns(const double* src, size_t cols, size_t ld, long long d0, size_t n, double* dst)
+{
+    for (size_t q = 0; q < cols; ++q) memcpy(dst + q * n, src + q * ld + (size_t)d0, sizeof(double) * n);
+    return dst + cols * n;
+}
+
+// The upload ring of a statistic's host entry.  The draws go up in chunks of whole slabs (predictive_plan.hpp): packed column by
+// column into pinned staging (leading dimension = the chunk's draws), copied on the copy stream, reduced on the compute stream,
+// RING buffers deep, so chunk c + 1 is packed and copied while chunk c's kernel runs.  Every chunk adds to the same sums in the
+// work area; the caller finalizes at the end.  Both arenas are laid out once, before any pointer is taken: `io` (results and
+// fixed inputs, at the same offsets in both) | work (device only) | the chunk buffers.
+// Caller holds c.mu and has made c.device current.
+struct UploadRing {
+    DeviceCtx& c;
+    hmcg_timing* timing;
+    const std::chrono::steady_clock::time_point t_call = std::chrono::steady_clock::now();
+    long long cdraws = 0;                            // draws of a full chunk
+    std::vector<PredChunk> chunks;
+    int nbuf = 0;
+    char *dev = nullptr, *pin = nullptr, *work = nullptr;    // after alloc(): the arenas and the device's work area
+    double *dbuf[RING] = {}, *pbuf[RING] = {};
+    size_t uploads = 0;                              // chunks uploaded so far, over every run(): the ring position
+    Events tev;                                      // two per timed launch (only when timing is asked for)
+
+    UploadRing(DeviceCtx& ctx, long long nd, int W, int ncol, hmcg_timing* t) : c(ctx), timing(t)
+    {
+        long long cap = 0;
+        if (const char* cenv = diag_env("HMCG_CHUNK_DRAWS")) cap = atoll(cenv);
+        cdraws = pred_chunk_draws(nd, W, ncol, cap);
+        chunks = pred_chunks(nd, cdraws);
+        nbuf = (int)std::min<size_t>(RING, chunks.size());
+    }
+
+    int alloc(const Layout& io, size_t work_bytes, size_t chunk_doubles)
+    {
+        Layout d = io, p = io;
+        const size_t o_work = d.add(work_bytes);
+        size_t o_d[RING] = {}, o_p[RING] = {};
+        for (int b = 0; b < nbuf; ++b) { o_d[b] = d.add(sizeof(double) * chunk_doubles); o_p[b] = p.add(sizeof(double) * chunk_doubles); }
+        if (c.dev.ensure(d.total) || c.pin.ensure(p.total)) {
+            set_err("workspace allocation failed (%zu B device, %zu B pinned)", d.total, p.total);
+            return HMCG_E_NOMEM;
+        }
+        dev = c.dev.base; pin = c.pin.base; work = dev + o_work;
+        for (int b = 0; b < nbuf; ++b) { dbuf[b] = reinterpret_cast<double*>(dev + o_d[b]); pbuf[b] = reinterpret_cast<double*>(pin + o_p[b]); }
+        return 0;
+    }
+
+    // enqueue() on the compute stream, between two events when the call is timed (a chunk's pair is created behind the enqueue
+    // of its copy, so the copy hides it)
+    template <class Enqueue>
+    int timed(Enqueue enqueue)
+    {
+        if (!timing) return enqueue();
+        hipEvent_t e[2] = {};
+        for (hipEvent_t& x : e) { HIP_TRY(hipEventCreate(&x)); tev.ev.push_back(x); }
+        HIP_TRY(hipEventRecord(e[0], c.stream));
+        const int rc = enqueue();
+        if (rc) return rc;
+        HIP_TRY(hipEventRecord(e[1], c.stream));
+        return 0;
+    }
+
+    // One pass over the chunks that start below `stop`: pack(chunk, pinned) fills the staging buffer and returns the doubles to
+    // copy; launch(chunk, device, stream) enqueues the chunk's kernel.  A later run goes on where this one stood in the ring.
+    template <class Pack, class Launch>
+    int run(Pack pack, Launch launch, long long stop = LLONG_MAX)
+    {
+        for (const PredChunk& ch : chunks) {
+            if (ch.d0 >= stop) break;
+            const int b = (int)(uploads % (size_t)nbuf);
+            if (uploads >= (size_t)nbuf) HIP_TRY(hipEventSynchronize(c.evk[b]));      // the kernel that read this buffer pair is done
+            ++uploads;
+            const size_t n = pack(ch, pbuf[b]);
+            HIP_TRY(hipMemcpyAsync(dbuf[b], pbuf[b], sizeof(double) * n, hipMemcpyHostToDevice, c.copy));
+            HIP_TRY(hipEventRecord(c.evc[b], c.copy));
+            HIP_TRY(hipStreamWaitEvent(c.stream, c.evc[b], 0));
+            const int rc = timed([&] { return launch(ch, dbuf[b], c.stream); });
+            if (rc) return rc;
+            HIP_TRY(hipEventRecord(c.evk[b], c.stream));
+        }
+        return 0;
+    }
+
+    // The results, `bytes` at offset `off` of `io`, into pinned staging behind everything on the compute stream; waits for them.
+    int fetch(size_t off, size_t bytes)
+    {
+        HIP_TRY(hipMemcpyAsync(pin + off, dev + off, bytes, hipMemcpyDeviceToHost, c.stream));
+        HIP_TRY(hipStreamSynchronize(c.stream));
+        return 0;
+    }
+
+    int report(const StatShape& sh, int launches)
+    {
+        if (!timing) return 0;
+        double kernel_ms = 0.0;
+        for (size_t i = 0; i + 1 < tev.ev.size(); i += 2) {
+            float ms = 0.f;
+            HIP_TRY(hipEventElapsedTime(&ms, tev.ev[i], tev.ev[i + 1]));
+            kernel_ms += ms;
+        }
+        const double call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+        fill_stat_timing(timing, c, sh, kernel_ms, launches, call_ms);
+        return 0;
+    }
+};
+
 // ---- predictive CDFs of the regime mixture (predictive.hip; argument rules and slab / chunk cut: predictive_plan.hpp) ----------
 
 hmcg_host::PredictiveArgs predictive_args(const hmcg_predictive* p)
@@ -971,380 +1120,202 @@ hmcg_host::PredictiveArgs predictive_args(const hmcg_predictive* p)
     return a;
 }
 
-void fill_predictive_timing(hmcg_timing* t, const hmcg_predictive* p, const DeviceCtx& c, double kernel_ms, int launches, double call_ms)
-{
-    memset(t, 0, sizeof *t);
-    t->kernel_ms = kernel_ms; t->launches = launches; t->call_ms = call_ms;
-    t->device = c.device; t->windows = p->W; t->buckets = 1;
-    t->lds_bytes = (int32_t)predictive_lds_bytes(p->K, p->n_h, pred_max_horizon(*p) > 0);
-}
+StatShape predictive_shape(const hmcg_predictive* p) { return {p->W, 0, (int32_t)predictive_lds_bytes(p->K, p->n_h, pred_max_horizon(*p) > 0)}; }
 
-// Caller holds c.mu and has made c.device current.  The slab sums live in a context-owned arena (as the moment tables do).
 int predictive_device(DeviceCtx& c, const hmcg_predictive* p, const double* dmu, const double* dsig2, const double* dpi_end,
                       const double* dA, const double* dgrid, double* dcdf, hipStream_t stream, hmcg_timing* timing)
 {
-    int rc = grow_shared(c, c.pred, sizeof(double) * predictive_part_doubles(p->W, p->nd, p->n_h, p->G));
-    if (rc) return rc;
-    HIP_TRY(hipStreamWaitEvent(stream, c.ev_scr, 0));
-    if (timing) HIP_TRY(hipEventRecord(c.ev0, stream));
-    hmcg_host::PredictiveArgs a = predictive_args(p);
-    a.mu = dmu; a.sig2 = dsig2; a.pi_end = dpi_end; a.A = dA; a.grid = dgrid;
-    a.part = reinterpret_cast<double*>(c.pred.base);
-    a.nd = p->nd; a.nd_ld = p->nd_ld; a.slab0 = 0;
-    HIP_TRY(launch_predictive(a, stream));
-    HIP_TRY(launch_predictive_finalize(a.part, dcdf, p->W, p->n_h, p->G, p->nd, stream));
-    HIP_TRY(hipEventRecord(c.ev_scr, stream));
-    if (timing) {
-        HIP_TRY(hipEventRecord(c.ev1, stream));
-        HIP_TRY(hipEventSynchronize(c.ev1));
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, c.ev0, c.ev1));
-        fill_predictive_timing(timing, p, c, ms, 2, 0.0);
-    }
-    return 0;
+    const size_t work = sizeof(double) * predictive_part_doubles(p->W, p->nd, p->n_h, p->G);
+    return stat_device(c, c.pred, work, stream, timing, predictive_shape(p), 2, [&]() -> int {
+        hmcg_host::PredictiveArgs a = predictive_args(p);
+        a.mu = dmu; a.sig2 = dsig2; a.pi_end = dpi_end; a.A = dA; a.grid = dgrid;
+        a.part = reinterpret_cast<double*>(c.pred.base);
+        a.nd = p->nd; a.nd_ld = p->nd_ld; a.slab0 = 0;
+        HIP_TRY(launch_predictive(a, stream));
+        HIP_TRY(launch_predictive_finalize(a.part, dcdf, p->W, p->n_h, p->G, p->nd, stream));
+        return 0;
+    });
 }
 
-// Host entry on one device: the draws go up in chunks of whole slabs -- packed window by window, column by column into pinned
-// staging (leading dimension = the chunk's draws), copied on the copy stream, reduced on the compute stream -- RING buffers deep,
-// so chunk c + 1 is packed and copied while chunk c's kernel runs.  Every chunk adds its slabs' sums to the same table; one
-// finalize at the end.  Caller holds c.mu and has made c.device current.
+// Host entry on one device, through the upload ring: every chunk adds its slabs' sums to the same table; one finalize at the end.
 int predictive_host(DeviceCtx& c, const hmcg_predictive* p, const double* mu, const double* sig2, const double* pi_end, const double* A,
                     const double* grid, double* cdf, hmcg_timing* timing)
 {
-    const auto t_call = std::chrono::steady_clock::now();
-    const int K = p->K, W = p->W;
     const bool with_A = pred_max_horizon(*p) > 0;
+    const size_t WK = (size_t)p->W * (size_t)p->K, ld = (size_t)p->nd_ld;
     const int ncol = pred_columns(*p);
-    long long cap = 0;
-    if (const char* cenv = diag_env("HMCG_CHUNK_DRAWS")) cap = atoll(cenv);
-    const long long cdraws = pred_chunk_draws(p->nd, W, ncol, cap);
-    const std::vector<PredChunk> chunks = pred_chunks(p->nd, cdraws);
-    const size_t items = (size_t)p->n_h * (size_t)p->G;
-    auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
-    const size_t b_chunk = up(sizeof(double) * (size_t)W * (size_t)ncol * (size_t)cdraws);
-    const size_t b_grid = up(sizeof(double) * (size_t)p->G), b_cdf = up(sizeof(double) * (size_t)W * items);
-    const size_t b_part = up(sizeof(double) * predictive_part_doubles(W, p->nd, p->n_h, p->G));
-    const int nbuf = (int)std::min<size_t>(RING, chunks.size());
-    if (c.dev.ensure(b_grid + b_cdf + b_part + b_chunk * (size_t)nbuf) || c.pin.ensure(b_grid + b_cdf + b_chunk * (size_t)nbuf)) {
-        set_err("workspace allocation failed (%zu B device, %zu B pinned)", b_grid + b_cdf + b_part + b_chunk * (size_t)nbuf,
-                b_grid + b_cdf + b_chunk * (size_t)nbuf);
-        return HMCG_E_NOMEM;
-    }
-    double* dgrid = reinterpret_cast<double*>(c.dev.base);
-    double* dcdf = reinterpret_cast<double*>(c.dev.base + b_grid);
-    double* dpart = reinterpret_cast<double*>(c.dev.base + b_grid + b_cdf);
-    char* dchunk = c.dev.base + b_grid + b_cdf + b_part;
-    double* pgrid = reinterpret_cast<double*>(c.pin.base);
-    double* pcdf = reinterpret_cast<double*>(c.pin.base + b_grid);
-    char* pchunk = c.pin.base + b_grid + b_cdf;
-
-    struct Events {
-        std::vector<hipEvent_t> ev;
-        ~Events() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
-    } tev;                                       // two per chunk, around its kernel (created only when timing is asked for)
-    if (timing) {
-        tev.ev.assign(2 * chunks.size(), nullptr);
-        for (hipEvent_t& e : tev.ev) HIP_TRY(hipEventCreate(&e));
-    }
-    memcpy(pgrid, grid, sizeof(double) * (size_t)p->G);
-    HIP_TRY(hipMemcpyAsync(dgrid, pgrid, sizeof(double) * (size_t)p->G, hipMemcpyHostToDevice, c.stream));
+    UploadRing ring(c, p->nd, p->W, ncol, timing);
+    const size_t b_grid = sizeof(double) * (size_t)p->G, b_cdf = sizeof(double) * (size_t)p->W * (size_t)p->n_h * (size_t)p->G;
+    Layout io;
+    const size_t o_grid = io.add(b_grid), o_cdf = io.add(b_cdf);
+    const size_t work = sizeof(double) * predictive_part_doubles(p->W, p->nd, p->n_h, p->G);
+    int rc = ring.alloc(io, work, (size_t)p->W * (size_t)ncol * (size_t)ring.cdraws);
+    if (rc) return rc;
+    memcpy(ring.pin + o_grid, grid, b_grid);
+    HIP_TRY(hipMemcpyAsync(ring.dev + o_grid, ring.pin + o_grid, b_grid, hipMemcpyHostToDevice, c.stream));
     hmcg_host::PredictiveArgs a = predictive_args(p);
-    a.grid = dgrid; a.part = dpart;
-    for (size_t ci = 0; ci < chunks.size(); ++ci) {
-        const PredChunk& ch = chunks[ci];
-        const int b = (int)(ci % (size_t)nbuf);
-        if (ci >= (size_t)nbuf) HIP_TRY(hipEventSynchronize(c.evk[b]));       // the kernel that read this buffer pair is done
-        double* pb = reinterpret_cast<double*>(pchunk + b_chunk * (size_t)b);
-        double* db = reinterpret_cast<double*>(dchunk + b_chunk * (size_t)b);
-        // packed chunk: mu | sig2 | pi_end | A, each [W][columns][ch.n]
-        const size_t n = (size_t)ch.n, o_sig = (size_t)W * K * n, o_pi = 2 * o_sig, o_A = 3 * o_sig;
-        auto pack = [&](const double* src, size_t cols, double* dst) {
-            for (size_t q = 0; q < (size_t)W * cols; ++q) memcpy(dst + q * n, src + q * (size_t)p->nd_ld + (size_t)ch.d0, sizeof(double) * n);
-        };
-        pack(mu, (size_t)K, pb);
-        pack(sig2, (size_t)K, pb + o_sig);
-        pack(pi_end, (size_t)K, pb + o_pi);
-        if (with_A) pack(A, (size_t)K * K, pb + o_A);
-        HIP_TRY(hipMemcpyAsync(db, pb, sizeof(double) * (size_t)W * (size_t)ncol * n, hipMemcpyHostToDevice, c.copy));
-        HIP_TRY(hipEventRecord(c.evc[b], c.copy));
-        HIP_TRY(hipStreamWaitEvent(c.stream, c.evc[b], 0));
-        a.mu = db; a.sig2 = db + o_sig; a.pi_end = db + o_pi; a.A = with_A ? db + o_A : nullptr;
-        a.nd = ch.n; a.nd_ld = ch.n; a.slab0 = ch.d0 / PRED_SLAB;
-        if (timing) HIP_TRY(hipEventRecord(tev.ev[2 * ci], c.stream));
-        HIP_TRY(launch_predictive(a, c.stream));
-        if (timing) HIP_TRY(hipEventRecord(tev.ev[2 * ci + 1], c.stream));
-        HIP_TRY(hipEventRecord(c.evk[b], c.stream));
-    }
-    HIP_TRY(launch_predictive_finalize(dpart, dcdf, W, p->n_h, p->G, p->nd, c.stream));
-    HIP_TRY(hipMemcpyAsync(pcdf, dcdf, sizeof(double) * (size_t)W * items, hipMemcpyDeviceToHost, c.stream));
-    HIP_TRY(hipStreamSynchronize(c.stream));
-    memcpy(cdf, pcdf, sizeof(double) * (size_t)W * items);
-    if (timing) {
-        double kernel_ms = 0.0;
-        for (size_t ci = 0; ci < chunks.size(); ++ci) {
-            float ms = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms, tev.ev[2 * ci], tev.ev[2 * ci + 1]));
-            kernel_ms += ms;
-        }
-        const double call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
-        fill_predictive_timing(timing, p, c, kernel_ms, (int)chunks.size() + 1, call_ms);
-    }
-    return 0;
+    a.grid = reinterpret_cast<double*>(ring.dev + o_grid); a.part = reinterpret_cast<double*>(ring.work);
+    double* const dcdf = reinterpret_cast<double*>(ring.dev + o_cdf);
+    // packed chunk: mu | sig2 | pi_end | A, each [W][columns][ch.n]
+    rc = ring.run(
+        [&](const PredChunk& ch, double* pb) {
+            double* e = pack_columns(mu, WK, ld, ch.d0, (size_t)ch.n, pb);
+            e = pack_columns(sig2, WK, ld, ch.d0, (size_t)ch.n, e);
+            e = pack_columns(pi_end, WK, ld, ch.d0, (size_t)ch.n, e);
+            if (with_A) e = pack_columns(A, WK * (size_t)p->K, ld, ch.d0, (size_t)ch.n, e);
+            return (size_t)(e - pb);
+        },
+        [&](const PredChunk& ch, double* db, hipStream_t s) -> int {
+            const size_t o_col = WK * (size_t)ch.n;
+            a.mu = db; a.sig2 = db + o_col; a.pi_end = db + 2 * o_col; a.A = with_A ? db + 3 * o_col : nullptr;
+            a.nd = ch.n; a.nd_ld = ch.n; a.slab0 = ch.d0 / PRED_SLAB;
+            HIP_TRY(launch_predictive(a, s));
+            return 0;
+        });
+    if (rc) return rc;
+    HIP_TRY(launch_predictive_finalize(a.part, dcdf, p->W, p->n_h, p->G, p->nd, c.stream));
+    if ((rc = ring.fetch(o_cdf, b_cdf))) return rc;
+    memcpy(cdf, ring.pin + o_cdf, b_cdf);
+    return ring.report(predictive_shape(p), (int)ring.uploads + 1);
 }
 
 // ---- uncertainty-bias moments of the draws (bias.hip; argument rules: bias_plan.hpp; slab / chunk cut: predictive_plan.hpp) ------
 
-void fill_bias_timing(hmcg_timing* t, const hmcg_bias* p, const DeviceCtx& c, double kernel_ms, int launches, double call_ms)
+hmcg_host::BiasArgs bias_args(const hmcg_bias* p)
 {
-    memset(t, 0, sizeof *t);
-    t->kernel_ms = kernel_ms; t->launches = launches; t->call_ms = call_ms;
-    t->device = c.device; t->windows = p->W; t->buckets = 1; t->threads_per_window = 256;
+    hmcg_host::BiasArgs a{};
+    a.W = p->W; a.K = p->K; a.horizon = p->horizon; a.round5 = (p->flags & HMCG_BIAS_ROUND5) != 0;
+    a.nslab_total = pred_slabs(p->nd);
+    return a;
 }
 
-// Caller holds c.mu and has made c.device current.  The slab sums live in a context-owned arena (as those of the predictive CDFs do).
 int bias_device(DeviceCtx& c, const hmcg_bias* p, const double* dmu, const double* dpi_end, const double* dA, const double* dfcast,
                 double* dout, hipStream_t stream, hmcg_timing* timing)
 {
-    int rc = grow_shared(c, c.bias, sizeof(double) * bias_part_doubles(p->W, p->nd, p->K));
-    if (rc) return rc;
-    HIP_TRY(hipStreamWaitEvent(stream, c.ev_scr, 0));
-    if (timing) HIP_TRY(hipEventRecord(c.ev0, stream));
-    hmcg_host::BiasArgs a{};
-    a.W = p->W; a.K = p->K; a.horizon = p->horizon; a.round5 = (p->flags & HMCG_BIAS_ROUND5) != 0;
-    a.mu = dmu; a.pi_end = dpi_end; a.A = dA;
-    a.fc = dfcast ? dfcast + p->nd_ld : nullptr;             // column 1: forecast_error of the first horizon
-    a.fc_wstride = 2LL * p->H * p->nd_ld;
-    a.part = reinterpret_cast<double*>(c.bias.base);
-    a.nd = p->nd; a.nd_ld = p->nd_ld; a.slab0 = 0; a.nslab_total = pred_slabs(p->nd);
-    HIP_TRY(launch_bias(a, stream));
-    HIP_TRY(launch_bias_finalize(a.part, dout, p->W, p->K, p->nd, dfcast != nullptr, stream));
-    HIP_TRY(hipEventRecord(c.ev_scr, stream));
-    if (timing) {
-        HIP_TRY(hipEventRecord(c.ev1, stream));
-        HIP_TRY(hipEventSynchronize(c.ev1));
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, c.ev0, c.ev1));
-        fill_bias_timing(timing, p, c, ms, 2, 0.0);
-    }
-    return 0;
+    const size_t work = sizeof(double) * bias_part_doubles(p->W, p->nd, p->K);
+    return stat_device(c, c.bias, work, stream, timing, {p->W, 256, 0}, 2, [&]() -> int {
+        hmcg_host::BiasArgs a = bias_args(p);
+        a.mu = dmu; a.pi_end = dpi_end; a.A = dA;
+        a.fc = dfcast ? dfcast + p->nd_ld : nullptr;             // column 1: forecast_error of the first horizon
+        a.fc_wstride = 2LL * p->H * p->nd_ld;
+        a.part = reinterpret_cast<double*>(c.bias.base);
+        a.nd = p->nd; a.nd_ld = p->nd_ld; a.slab0 = 0;
+        HIP_TRY(launch_bias(a, stream));
+        HIP_TRY(launch_bias_finalize(a.part, dout, p->W, p->K, p->nd, dfcast != nullptr, stream));
+        return 0;
+    });
 }
 
-// Host entry on one device, as predictive_host: whole-slab chunks packed window by window, column by column into pinned staging
-// (mu | pi_end | A | forecast error, leading dimension = the chunk's draws), RING buffers deep, the copy of chunk c + 1 beside the
-// kernel of chunk c; every chunk files its slabs' sums in the same table (the first one the pivots too); one finalize at the end.
+// Host entry on one device, through the upload ring: every chunk files its slabs' sums in the same table (the first one the
+// pivots too); one finalize at the end.
 int bias_host(DeviceCtx& c, const hmcg_bias* p, const double* mu, const double* pi_end, const double* A, const double* fcast, double* out,
               hmcg_timing* timing)
 {
-    const auto t_call = std::chrono::steady_clock::now();
     const int K = p->K, W = p->W;
     const bool with_A = p->horizon > 0, with_fc = fcast != nullptr;
+    const size_t WK = (size_t)W * (size_t)K, ld = (size_t)p->nd_ld;
     const int ncol = bias_columns(*p, with_fc);
-    long long cap = 0;
-    if (const char* cenv = diag_env("HMCG_CHUNK_DRAWS")) cap = atoll(cenv);
-    const long long cdraws = pred_chunk_draws(p->nd, W, ncol, cap);
-    const std::vector<PredChunk> chunks = pred_chunks(p->nd, cdraws);
-    const size_t nout = (size_t)W * (size_t)HMCG_BIAS_STRIDE(K);
-    auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
-    const size_t b_chunk = up(sizeof(double) * (size_t)W * (size_t)ncol * (size_t)cdraws);
-    const size_t b_out = up(sizeof(double) * nout);
-    const size_t b_part = up(sizeof(double) * bias_part_doubles(W, p->nd, K));
-    const int nbuf = (int)std::min<size_t>(RING, chunks.size());
-    if (c.dev.ensure(b_out + b_part + b_chunk * (size_t)nbuf) || c.pin.ensure(b_out + b_chunk * (size_t)nbuf)) {
-        set_err("workspace allocation failed (%zu B device, %zu B pinned)", b_out + b_part + b_chunk * (size_t)nbuf,
-                b_out + b_chunk * (size_t)nbuf);
-        return HMCG_E_NOMEM;
-    }
-    double* dout = reinterpret_cast<double*>(c.dev.base);
-    double* dpart = reinterpret_cast<double*>(c.dev.base + b_out);
-    char* dchunk = c.dev.base + b_out + b_part;
-    double* pout = reinterpret_cast<double*>(c.pin.base);
-    char* pchunk = c.pin.base + b_out;
-
-    struct Events {
-        std::vector<hipEvent_t> ev;
-        ~Events() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
-    } tev;                                       // two per chunk, around its kernel (created only when timing is asked for)
-    if (timing) {
-        tev.ev.assign(2 * chunks.size(), nullptr);
-        for (hipEvent_t& e : tev.ev) HIP_TRY(hipEventCreate(&e));
-    }
-    hmcg_host::BiasArgs a{};
-    a.W = W; a.K = K; a.horizon = p->horizon; a.round5 = (p->flags & HMCG_BIAS_ROUND5) != 0;
-    a.part = dpart; a.nslab_total = pred_slabs(p->nd);
-    for (size_t ci = 0; ci < chunks.size(); ++ci) {
-        const PredChunk& ch = chunks[ci];
-        const int b = (int)(ci % (size_t)nbuf);
-        if (ci >= (size_t)nbuf) HIP_TRY(hipEventSynchronize(c.evk[b]));       // the kernel that read this buffer pair is done
-        double* pb = reinterpret_cast<double*>(pchunk + b_chunk * (size_t)b);
-        double* db = reinterpret_cast<double*>(dchunk + b_chunk * (size_t)b);
-        // packed chunk: mu | pi_end | A | forecast error, each [W][columns][ch.n]
-        const size_t n = (size_t)ch.n, o_pi = (size_t)W * K * n, o_A = 2 * o_pi, o_fc = o_A + (with_A ? (size_t)W * K * K * n : 0);
-        auto pack = [&](const double* src, size_t cols, double* dst) {
-            for (size_t q = 0; q < (size_t)W * cols; ++q) memcpy(dst + q * n, src + q * (size_t)p->nd_ld + (size_t)ch.d0, sizeof(double) * n);
-        };
-        pack(mu, (size_t)K, pb);
-        pack(pi_end, (size_t)K, pb + o_pi);
-        if (with_A) pack(A, (size_t)K * K, pb + o_A);
-        if (with_fc)
-            for (size_t w = 0; w < (size_t)W; ++w)
-                memcpy(pb + o_fc + w * n, fcast + (w * 2 * (size_t)p->H + 1) * (size_t)p->nd_ld + (size_t)ch.d0, sizeof(double) * n);
-        HIP_TRY(hipMemcpyAsync(db, pb, sizeof(double) * (size_t)W * (size_t)ncol * n, hipMemcpyHostToDevice, c.copy));
-        HIP_TRY(hipEventRecord(c.evc[b], c.copy));
-        HIP_TRY(hipStreamWaitEvent(c.stream, c.evc[b], 0));
-        a.mu = db; a.pi_end = db + o_pi; a.A = with_A ? db + o_A : nullptr;
-        a.fc = with_fc ? db + o_fc : nullptr; a.fc_wstride = ch.n;
-        a.nd = ch.n; a.nd_ld = ch.n; a.slab0 = ch.d0 / PRED_SLAB;
-        if (timing) HIP_TRY(hipEventRecord(tev.ev[2 * ci], c.stream));
-        HIP_TRY(launch_bias(a, c.stream));
-        if (timing) HIP_TRY(hipEventRecord(tev.ev[2 * ci + 1], c.stream));
-        HIP_TRY(hipEventRecord(c.evk[b], c.stream));
-    }
-    HIP_TRY(launch_bias_finalize(dpart, dout, W, K, p->nd, with_fc, c.stream));
-    HIP_TRY(hipMemcpyAsync(pout, dout, sizeof(double) * nout, hipMemcpyDeviceToHost, c.stream));
-    HIP_TRY(hipStreamSynchronize(c.stream));
-    memcpy(out, pout, sizeof(double) * nout);
-    if (timing) {
-        double kernel_ms = 0.0;
-        for (size_t ci = 0; ci < chunks.size(); ++ci) {
-            float ms = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms, tev.ev[2 * ci], tev.ev[2 * ci + 1]));
-            kernel_ms += ms;
-        }
-        const double call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
-        fill_bias_timing(timing, p, c, kernel_ms, (int)chunks.size() + 1, call_ms);
-    }
-    return 0;
+    UploadRing ring(c, p->nd, W, ncol, timing);
+    const size_t b_out = sizeof(double) * (size_t)W * (size_t)HMCG_BIAS_STRIDE(K);
+    Layout io;
+    const size_t o_out = io.add(b_out);
+    int rc = ring.alloc(io, sizeof(double) * bias_part_doubles(W, p->nd, K), (size_t)W * (size_t)ncol * (size_t)ring.cdraws);
+    if (rc) return rc;
+    hmcg_host::BiasArgs a = bias_args(p);
+    a.part = reinterpret_cast<double*>(ring.work);
+    // packed chunk: mu | pi_end | A | forecast error, each [W][columns][ch.n]
+    rc = ring.run(
+        [&](const PredChunk& ch, double* pb) {
+            double* e = pack_columns(mu, WK, ld, ch.d0, (size_t)ch.n, pb);
+            e = pack_columns(pi_end, WK, ld, ch.d0, (size_t)ch.n, e);
+            if (with_A) e = pack_columns(A, WK * (size_t)K, ld, ch.d0, (size_t)ch.n, e);
+            // column 1 of every window's 2H: forecast_error of the first horizon
+            if (with_fc) e = pack_columns(fcast + ld, (size_t)W, 2 * (size_t)p->H * ld, ch.d0, (size_t)ch.n, e);
+            return (size_t)(e - pb);
+        },
+        [&](const PredChunk& ch, double* db, hipStream_t s) -> int {
+            const size_t o_pi = WK * (size_t)ch.n, o_A = 2 * o_pi, o_fc = o_A + (with_A ? o_pi * (size_t)K : 0);
+            a.mu = db; a.pi_end = db + o_pi; a.A = with_A ? db + o_A : nullptr;
+            a.fc = with_fc ? db + o_fc : nullptr; a.fc_wstride = ch.n;
+            a.nd = ch.n; a.nd_ld = ch.n; a.slab0 = ch.d0 / PRED_SLAB;
+            HIP_TRY(launch_bias(a, s));
+            return 0;
+        });
+    if (rc) return rc;
+    HIP_TRY(launch_bias_finalize(a.part, reinterpret_cast<double*>(ring.dev + o_out), W, K, p->nd, with_fc, c.stream));
+    if ((rc = ring.fetch(o_out, b_out))) return rc;
+    memcpy(out, ring.pin + o_out, b_out);
+    return ring.report({W, 256, 0}, (int)ring.uploads + 1);
 }
 
 // ---- predictive-mixture moments of the draws (mixmoments.hip; argument rules and the walk: mixmoments_plan.hpp; slab / chunk cut:
 // predictive_plan.hpp) -----------------------------------------------------------------------------------------------------------
 
-void fill_mix_timing(hmcg_timing* t, const hmcg_mixmom* p, const DeviceCtx& c, double kernel_ms, int launches, double call_ms)
+hmcg_host::MixArgs mix_args(const hmcg_mixmom* p)
 {
-    memset(t, 0, sizeof *t);
-    t->kernel_ms = kernel_ms; t->launches = launches; t->call_ms = call_ms;
-    t->device = c.device; t->windows = p->W; t->buckets = 1; t->threads_per_window = 256;
+    hmcg_host::MixArgs a{};
+    a.W = p->W; a.K = p->K; a.n_h = p->n_h; a.walk = mix_walk(*p); a.round5 = (p->flags & HMCG_MIX_ROUND5) != 0;
+    a.nslab_total = pred_slabs(p->nd);
+    return a;
 }
 
-// Caller holds c.mu and has made c.device current.  The slab sums live in a context-owned arena (as those of the predictive CDFs do).
 int mix_device(DeviceCtx& c, const hmcg_mixmom* p, const double* dmu, const double* dsig2, const double* dpi_end, const double* dA,
                double* dout, hipStream_t stream, hmcg_timing* timing)
 {
-    int rc = grow_shared(c, c.mix, sizeof(double) * mix_part_doubles(p->W, p->nd, p->n_h));
-    if (rc) return rc;
-    HIP_TRY(hipStreamWaitEvent(stream, c.ev_scr, 0));
-    if (timing) HIP_TRY(hipEventRecord(c.ev0, stream));
-    hmcg_host::MixArgs a{};
-    a.W = p->W; a.K = p->K; a.n_h = p->n_h; a.walk = mix_walk(*p); a.round5 = (p->flags & HMCG_MIX_ROUND5) != 0;
-    a.mu = dmu; a.sig2 = dsig2; a.pi_end = dpi_end; a.A = dA;
-    a.part = reinterpret_cast<double*>(c.mix.base);
-    a.nd = p->nd; a.nd_ld = p->nd_ld; a.slab0 = 0; a.nslab_total = pred_slabs(p->nd);
-    HIP_TRY(launch_mixmoments(a, stream));
-    HIP_TRY(launch_mixmoments_finalize(a.part, dout, p->W, p->n_h, p->nd, stream));
-    HIP_TRY(hipEventRecord(c.ev_scr, stream));
-    if (timing) {
-        HIP_TRY(hipEventRecord(c.ev1, stream));
-        HIP_TRY(hipEventSynchronize(c.ev1));
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, c.ev0, c.ev1));
-        fill_mix_timing(timing, p, c, ms, 2, 0.0);
-    }
-    return 0;
+    const size_t work = sizeof(double) * mix_part_doubles(p->W, p->nd, p->n_h);
+    return stat_device(c, c.mix, work, stream, timing, {p->W, 256, 0}, 2, [&]() -> int {
+        hmcg_host::MixArgs a = mix_args(p);
+        a.mu = dmu; a.sig2 = dsig2; a.pi_end = dpi_end; a.A = dA;
+        a.part = reinterpret_cast<double*>(c.mix.base);
+        a.nd = p->nd; a.nd_ld = p->nd_ld; a.slab0 = 0;
+        HIP_TRY(launch_mixmoments(a, stream));
+        HIP_TRY(launch_mixmoments_finalize(a.part, dout, p->W, p->n_h, p->nd, stream));
+        return 0;
+    });
 }
 
-// Host entry on one device, as bias_host: whole-slab chunks packed window by window, column by column into pinned staging
-// (mu | sig2 | pi_end | A, leading dimension = the chunk's draws), RING buffers deep, the copy of chunk c + 1 beside the kernel of
-// chunk c; every chunk files its slabs' sums in the same table (the first one the pivots too); one finalize at the end.
+// Host entry on one device, through the upload ring: every chunk files its slabs' sums in the same table (the first one the
+// pivots too); one finalize at the end.
 int mix_host(DeviceCtx& c, const hmcg_mixmom* p, const double* mu, const double* sig2, const double* pi_end, const double* A, double* out,
              hmcg_timing* timing)
 {
-    const auto t_call = std::chrono::steady_clock::now();
     const int K = p->K, W = p->W;
     const bool with_A = mix_max_horizon(*p) > 0;
+    const size_t WK = (size_t)W * (size_t)K, ld = (size_t)p->nd_ld;
     const int ncol = mix_columns(*p);
-    long long cap = 0;
-    if (const char* cenv = diag_env("HMCG_CHUNK_DRAWS")) cap = atoll(cenv);
-    const long long cdraws = pred_chunk_draws(p->nd, W, ncol, cap);
-    const std::vector<PredChunk> chunks = pred_chunks(p->nd, cdraws);
-    const size_t nout = (size_t)W * (size_t)p->n_h * (size_t)HMCG_MIX_STRIDE;
-    auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
-    const size_t b_chunk = up(sizeof(double) * (size_t)W * (size_t)ncol * (size_t)cdraws);
-    const size_t b_out = up(sizeof(double) * nout);
-    const size_t b_part = up(sizeof(double) * mix_part_doubles(W, p->nd, p->n_h));
-    const int nbuf = (int)std::min<size_t>(RING, chunks.size());
-    if (c.dev.ensure(b_out + b_part + b_chunk * (size_t)nbuf) || c.pin.ensure(b_out + b_chunk * (size_t)nbuf)) {
-        set_err("workspace allocation failed (%zu B device, %zu B pinned)", b_out + b_part + b_chunk * (size_t)nbuf,
-                b_out + b_chunk * (size_t)nbuf);
-        return HMCG_E_NOMEM;
-    }
-    double* dout = reinterpret_cast<double*>(c.dev.base);
-    double* dpart = reinterpret_cast<double*>(c.dev.base + b_out);
-    char* dchunk = c.dev.base + b_out + b_part;
-    double* pout = reinterpret_cast<double*>(c.pin.base);
-    char* pchunk = c.pin.base + b_out;
-
-    struct Events {
-        std::vector<hipEvent_t> ev;
-        ~Events() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
-    } tev;                                       // two per chunk, around its kernel (created only when timing is asked for)
-    if (timing) {
-        tev.ev.assign(2 * chunks.size(), nullptr);
-        for (hipEvent_t& e : tev.ev) HIP_TRY(hipEventCreate(&e));
-    }
-    hmcg_host::MixArgs a{};
-    a.W = W; a.K = K; a.n_h = p->n_h; a.walk = mix_walk(*p); a.round5 = (p->flags & HMCG_MIX_ROUND5) != 0;
-    a.part = dpart; a.nslab_total = pred_slabs(p->nd);
-    for (size_t ci = 0; ci < chunks.size(); ++ci) {
-        const PredChunk& ch = chunks[ci];
-        const int b = (int)(ci % (size_t)nbuf);
-        if (ci >= (size_t)nbuf) HIP_TRY(hipEventSynchronize(c.evk[b]));       // the kernel that read this buffer pair is done
-        double* pb = reinterpret_cast<double*>(pchunk + b_chunk * (size_t)b);
-        double* db = reinterpret_cast<double*>(dchunk + b_chunk * (size_t)b);
-        // packed chunk: mu | sig2 | pi_end | A, each [W][columns][ch.n]
-        const size_t n = (size_t)ch.n, o_col = (size_t)W * K * n;
-        auto pack = [&](const double* src, size_t cols, double* dst) {
-            for (size_t q = 0; q < (size_t)W * cols; ++q) memcpy(dst + q * n, src + q * (size_t)p->nd_ld + (size_t)ch.d0, sizeof(double) * n);
-        };
-        pack(mu, (size_t)K, pb);
-        pack(sig2, (size_t)K, pb + o_col);
-        pack(pi_end, (size_t)K, pb + 2 * o_col);
-        if (with_A) pack(A, (size_t)K * K, pb + 3 * o_col);
-        HIP_TRY(hipMemcpyAsync(db, pb, sizeof(double) * (size_t)W * (size_t)ncol * n, hipMemcpyHostToDevice, c.copy));
-        HIP_TRY(hipEventRecord(c.evc[b], c.copy));
-        HIP_TRY(hipStreamWaitEvent(c.stream, c.evc[b], 0));
-        a.mu = db; a.sig2 = db + o_col; a.pi_end = db + 2 * o_col; a.A = with_A ? db + 3 * o_col : nullptr;
-        a.nd = ch.n; a.nd_ld = ch.n; a.slab0 = ch.d0 / PRED_SLAB;
-        if (timing) HIP_TRY(hipEventRecord(tev.ev[2 * ci], c.stream));
-        HIP_TRY(launch_mixmoments(a, c.stream));
-        if (timing) HIP_TRY(hipEventRecord(tev.ev[2 * ci + 1], c.stream));
-        HIP_TRY(hipEventRecord(c.evk[b], c.stream));
-    }
-    HIP_TRY(launch_mixmoments_finalize(dpart, dout, W, p->n_h, p->nd, c.stream));
-    HIP_TRY(hipMemcpyAsync(pout, dout, sizeof(double) * nout, hipMemcpyDeviceToHost, c.stream));
-    HIP_TRY(hipStreamSynchronize(c.stream));
-    memcpy(out, pout, sizeof(double) * nout);
-    if (timing) {
-        double kernel_ms = 0.0;
-        for (size_t ci = 0; ci < chunks.size(); ++ci) {
-            float ms = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms, tev.ev[2 * ci], tev.ev[2 * ci + 1]));
-            kernel_ms += ms;
-        }
-        const double call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
-        fill_mix_timing(timing, p, c, kernel_ms, (int)chunks.size() + 1, call_ms);
-    }
-    return 0;
+    UploadRing ring(c, p->nd, W, ncol, timing);
+    const size_t b_out = sizeof(double) * (size_t)W * (size_t)p->n_h * (size_t)HMCG_MIX_STRIDE;
+    Layout io;
+    const size_t o_out = io.add(b_out);
+    int rc = ring.alloc(io, sizeof(double) * mix_part_doubles(W, p->nd, p->n_h), (size_t)W * (size_t)ncol * (size_t)ring.cdraws);
+    if (rc) return rc;
+    hmcg_host::MixArgs a = mix_args(p);
+    a.part = reinterpret_cast<double*>(ring.work);
+    // packed chunk: mu | sig2 | pi_end | A, each [W][columns][ch.n]
+    rc = ring.run(
+        [&](const PredChunk& ch, double* pb) {
+            double* e = pack_columns(mu, WK, ld, ch.d0, (size_t)ch.n, pb);
+            e = pack_columns(sig2, WK, ld, ch.d0, (size_t)ch.n, e);
+            e = pack_columns(pi_end, WK, ld, ch.d0, (size_t)ch.n, e);
+            if (with_A) e = pack_columns(A, WK * (size_t)K, ld, ch.d0, (size_t)ch.n, e);
+            return (size_t)(e - pb);
+        },
+        [&](const PredChunk& ch, double* db, hipStream_t s) -> int {
+            const size_t o_col = WK * (size_t)ch.n;
+            a.mu = db; a.sig2 = db + o_col; a.pi_end = db + 2 * o_col; a.A = with_A ? db + 3 * o_col : nullptr;
+            a.nd = ch.n; a.nd_ld = ch.n; a.slab0 = ch.d0 / PRED_SLAB;
+            HIP_TRY(launch_mixmoments(a, s));
+            return 0;
+        });
+    if (rc) return rc;
+    HIP_TRY(launch_mixmoments_finalize(a.part, reinterpret_cast<double*>(ring.dev + o_out), W, p->n_h, p->nd, c.stream));
+    if ((rc = ring.fetch(o_out, b_out))) return rc;
+    memcpy(out, ring.pin + o_out, b_out);
+    return ring.report({W, 256, 0}, (int)ring.uploads + 1);
 }
 
 // ---- chain densities and running means of the draws (density.hip; argument rules, pieces and column groups: density_plan.hpp;
 // chunk cut: predictive_plan.hpp) -------------------------------------------------------------------------------------------------
-
-void fill_dens_timing(hmcg_timing* t, const hmcg_density* p, const DeviceCtx& c, double kernel_ms, int launches, double call_ms)
-{
-    memset(t, 0, sizeof *t);
-    t->kernel_ms = kernel_ms; t->launches = launches; t->call_ms = call_ms;
-    t->device = c.device; t->windows = p->W; t->buckets = 1; t->threads_per_window = 256;
-}
 
 hmcg_host::DensArgs dens_args(const hmcg_density* p)
 {
@@ -1355,154 +1326,82 @@ hmcg_host::DensArgs dens_args(const hmcg_density* p)
     return a;
 }
 
-// Caller holds c.mu and has made c.device current.  The piece sums live in a context-owned arena (as the slab sums of the siblings do).
 int dens_device(DeviceCtx& c, const hmcg_density* p, const double* dx, const double* dlo_hi, double* drange, int64_t* dcounts,
                 double* dstats, double* dtrace, hipStream_t stream, hmcg_timing* timing)
 {
-    int rc = grow_shared(c, c.dens, dens_work_bytes(p->W, p->C, p->nd, p->cuts, p->n_cuts));
-    if (rc) return rc;
-    HIP_TRY(hipStreamWaitEvent(stream, c.ev_scr, 0));
-    if (timing) HIP_TRY(hipEventRecord(c.ev0, stream));
-    hmcg_host::DensArgs a = dens_args(p);
-    a.x = dx; a.work = c.dens.base; a.range = drange; a.counts = reinterpret_cast<unsigned long long*>(dcounts);
-    a.stats = dstats; a.trace = dtrace; a.d_origin = 0; a.n = p->nd; a.nd_ld = p->nd_ld;
-    HIP_TRY(launch_density_clear(a, stream));
-    if (!dlo_hi) HIP_TRY(launch_density_range(a, stream));
-    HIP_TRY(launch_density_resolve(a, dlo_hi, stream));
-    HIP_TRY(launch_density_accumulate(a, stream));
-    HIP_TRY(launch_density_finalize(a, stream));
-    HIP_TRY(hipEventRecord(c.ev_scr, stream));
-    if (timing) {
-        HIP_TRY(hipEventRecord(c.ev1, stream));
-        HIP_TRY(hipEventSynchronize(c.ev1));
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, c.ev0, c.ev1));
-        fill_dens_timing(timing, p, c, ms, dlo_hi ? 3 : 4, 0.0);
-    }
-    return 0;
+    const size_t work = dens_work_bytes(p->W, p->C, p->nd, p->cuts, p->n_cuts);
+    return stat_device(c, c.dens, work, stream, timing, {p->W, 256, 0}, dlo_hi ? 3 : 4, [&]() -> int {
+        hmcg_host::DensArgs a = dens_args(p);
+        a.x = dx; a.work = c.dens.base; a.range = drange; a.counts = reinterpret_cast<unsigned long long*>(dcounts);
+        a.stats = dstats; a.trace = dtrace; a.d_origin = 0; a.n = p->nd; a.nd_ld = p->nd_ld;
+        HIP_TRY(launch_density_clear(a, stream));
+        if (!dlo_hi) HIP_TRY(launch_density_range(a, stream));
+        HIP_TRY(launch_density_resolve(a, dlo_hi, stream));
+        HIP_TRY(launch_density_accumulate(a, stream));
+        HIP_TRY(launch_density_finalize(a, stream));
+        return 0;
+    });
 }
 
-// Host entry on one device, as mix_host: whole-slab chunks packed window by window, column by column into pinned staging
-// (leading dimension = the chunk's draws), RING buffers deep, the copy of chunk c + 1 beside the kernel of chunk c.  Without
-// lo_hi the bins need the range of ALL draws first: one pass of uploads for the range kernel, a second one for the counts and
-// sums (chunks that lie wholly beyond the last cut and the running mean are not uploaded again); with lo_hi the second pass alone.
+// Host entry on one device, through the upload ring.  Without lo_hi the bins need the range of ALL draws first: one pass of
+// uploads for the range kernel, a second one for the counts and sums (chunks that lie wholly beyond the last cut and the running
+// mean are not uploaded again); with lo_hi the second pass alone.  Both passes go through the one ring.
 int dens_host(DeviceCtx& c, const hmcg_density* p, const double* x, const double* lo_hi, double* range, int64_t* counts, double* stats,
               double* trace, hmcg_timing* timing)
 {
-    const auto t_call = std::chrono::steady_clock::now();
     const int W = p->W, C = p->C;
-    long long cap = 0;
-    if (const char* cenv = diag_env("HMCG_CHUNK_DRAWS")) cap = atoll(cenv);
-    const long long cdraws = pred_chunk_draws(p->nd, W, C, cap);
-    const std::vector<PredChunk> chunks = pred_chunks(p->nd, cdraws);
-    const size_t wc = (size_t)W * (size_t)C;
-    const size_t n_range = wc * 2, n_counts = wc * (size_t)p->n_cuts * (size_t)(p->B + DENS_SLOTS), n_stats = wc * (size_t)p->n_cuts * 2,
-                 n_trace = wc * (size_t)p->trace_len;
-    auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
-    const size_t b_range = up(8 * n_range), b_counts = up(8 * n_counts), b_stats = up(8 * n_stats), b_trace = up(8 * n_trace);
-    const size_t b_out = b_range + b_counts + b_stats + b_trace;
-    const size_t b_lohi = up(8 * n_range);
-    const size_t b_work = up(dens_work_bytes(W, C, p->nd, p->cuts, p->n_cuts));
-    const size_t b_chunk = up(sizeof(double) * wc * (size_t)cdraws);
-    const int nbuf = (int)std::min<size_t>(RING, chunks.size());
-    const size_t need_dev = b_out + b_lohi + b_work + b_chunk * (size_t)nbuf, need_pin = b_out + b_lohi + b_chunk * (size_t)nbuf;
-    if (c.dev.ensure(need_dev) || c.pin.ensure(need_pin)) {
-        set_err("workspace allocation failed (%zu B device, %zu B pinned)", need_dev, need_pin);
-        return HMCG_E_NOMEM;
-    }
-    char* dout = c.dev.base;
-    double* dlohi = reinterpret_cast<double*>(c.dev.base + b_out);
-    char* dwork = c.dev.base + b_out + b_lohi;
-    char* dchunk = dwork + b_work;
-    char* pout = c.pin.base;
-    double* plohi = reinterpret_cast<double*>(c.pin.base + b_out);
-    char* pchunk = c.pin.base + b_out + b_lohi;
-
+    const size_t wc = (size_t)W * (size_t)C, ld = (size_t)p->nd_ld;
+    UploadRing ring(c, p->nd, W, C, timing);
+    const size_t b_range = 8 * wc * 2, b_counts = 8 * wc * (size_t)p->n_cuts * (size_t)(p->B + DENS_SLOTS), b_stats = 8 * wc * (size_t)p->n_cuts * 2,
+                 b_trace = 8 * wc * (size_t)p->trace_len;
+    Layout io;
+    const size_t o_range = io.add(b_range), o_counts = io.add(b_counts), o_stats = io.add(b_stats), o_trace = io.add(b_trace);
+    const size_t b_out = io.total;               // the four results come back in one copy
+    const size_t o_lohi = io.add(b_range);
+    int rc = ring.alloc(io, dens_work_bytes(W, C, p->nd, p->cuts, p->n_cuts), wc * (size_t)ring.cdraws);
+    if (rc) return rc;
     hmcg_host::DensArgs a = dens_args(p);
-    a.work = dwork;
-    a.range = reinterpret_cast<double*>(dout);
-    a.counts = reinterpret_cast<unsigned long long*>(dout + b_range);
-    a.stats = reinterpret_cast<double*>(dout + b_range + b_counts);
-    a.trace = reinterpret_cast<double*>(dout + b_range + b_counts + b_stats);
+    a.work = ring.work;
+    a.range = reinterpret_cast<double*>(ring.dev + o_range);
+    a.counts = reinterpret_cast<unsigned long long*>(ring.dev + o_counts);
+    a.stats = reinterpret_cast<double*>(ring.dev + o_stats);
+    a.trace = reinterpret_cast<double*>(ring.dev + o_trace);
     // draws a second-pass chunk must reach below to matter: the last cut and the end of the running mean
     const long long reach = std::max<long long>(p->cuts[p->n_cuts - 1], (long long)p->trace_len * p->trace_stride);
 
-    struct Events {
-        std::vector<hipEvent_t> ev;
-        ~Events() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
-    } tev;                                       // two per chunk and pass, around its kernel (created only when timing is asked for)
-    size_t n_timed = 0;
-    if (timing) {
-        tev.ev.assign(4 * chunks.size(), nullptr);
-        for (hipEvent_t& e : tev.ev) HIP_TRY(hipEventCreate(&e));
-    }
-    int launches = 0;
     // the calls below must be enqueued on c.stream behind each other: clear, [range per chunk], resolve, accumulate per chunk, finalize
-    a.x = reinterpret_cast<double*>(dchunk); a.d_origin = 0; a.n = chunks[0].n; a.nd_ld = chunks[0].n;
+    a.x = ring.dbuf[0]; a.d_origin = 0; a.n = ring.chunks[0].n; a.nd_ld = ring.chunks[0].n;
     HIP_TRY(launch_density_clear(a, c.stream));
-    size_t gi = 0;                               // chunks uploaded so far, over both passes: the ring position
     for (int pass = lo_hi ? 1 : 0; pass < 2; ++pass) {
         if (pass == 1) {
+            double* const dlohi = reinterpret_cast<double*>(ring.dev + o_lohi);
             if (lo_hi) {
-                memcpy(plohi, lo_hi, 8 * n_range);
-                HIP_TRY(hipMemcpyAsync(dlohi, plohi, 8 * n_range, hipMemcpyHostToDevice, c.stream));
+                memcpy(ring.pin + o_lohi, lo_hi, b_range);
+                HIP_TRY(hipMemcpyAsync(dlohi, ring.pin + o_lohi, b_range, hipMemcpyHostToDevice, c.stream));
             }
             HIP_TRY(launch_density_resolve(a, lo_hi ? dlohi : nullptr, c.stream));
-            ++launches;
         }
-        for (size_t ci = 0; ci < chunks.size(); ++ci) {
-            const PredChunk& ch = chunks[ci];
-            if (pass == 1 && ch.d0 >= reach) break;
-            const int b = (int)(gi % (size_t)nbuf);
-            if (gi >= (size_t)nbuf) HIP_TRY(hipEventSynchronize(c.evk[b]));      // the kernel that read this buffer pair is done
-            ++gi;
-            double* pb = reinterpret_cast<double*>(pchunk + b_chunk * (size_t)b);
-            double* db = reinterpret_cast<double*>(dchunk + b_chunk * (size_t)b);
-            const size_t n = (size_t)ch.n;
-            for (size_t q = 0; q < wc; ++q) memcpy(pb + q * n, x + q * (size_t)p->nd_ld + (size_t)ch.d0, sizeof(double) * n);
-            HIP_TRY(hipMemcpyAsync(db, pb, sizeof(double) * wc * n, hipMemcpyHostToDevice, c.copy));
-            HIP_TRY(hipEventRecord(c.evc[b], c.copy));
-            HIP_TRY(hipStreamWaitEvent(c.stream, c.evc[b], 0));
-            a.x = db; a.d_origin = ch.d0; a.n = ch.n; a.nd_ld = ch.n;
-            if (timing) HIP_TRY(hipEventRecord(tev.ev[2 * n_timed], c.stream));
-            if (pass == 0) HIP_TRY(launch_density_range(a, c.stream));
-            else HIP_TRY(launch_density_accumulate(a, c.stream));
-            if (timing) HIP_TRY(hipEventRecord(tev.ev[2 * n_timed + 1], c.stream));
-            ++n_timed;
-            ++launches;
-            HIP_TRY(hipEventRecord(c.evk[b], c.stream));
-        }
+        rc = ring.run(
+            [&](const PredChunk& ch, double* pb) { return (size_t)(pack_columns(x, wc, ld, ch.d0, (size_t)ch.n, pb) - pb); },
+            [&](const PredChunk& ch, double* db, hipStream_t s) -> int {
+                a.x = db; a.d_origin = ch.d0; a.n = ch.n; a.nd_ld = ch.n;
+                HIP_TRY(pass == 0 ? launch_density_range(a, s) : launch_density_accumulate(a, s));
+                return 0;
+            },
+            pass == 1 ? reach : LLONG_MAX);
+        if (rc) return rc;
     }
     HIP_TRY(launch_density_finalize(a, c.stream));
-    ++launches;
-    HIP_TRY(hipMemcpyAsync(pout, dout, b_out, hipMemcpyDeviceToHost, c.stream));
-    HIP_TRY(hipStreamSynchronize(c.stream));
-    memcpy(range, pout, 8 * n_range);
-    memcpy(counts, pout + b_range, 8 * n_counts);
-    memcpy(stats, pout + b_range + b_counts, 8 * n_stats);
-    if (n_trace) memcpy(trace, pout + b_range + b_counts + b_stats, 8 * n_trace);
-    if (timing) {
-        double kernel_ms = 0.0;
-        for (size_t i = 0; i < n_timed; ++i) {
-            float ms = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms, tev.ev[2 * i], tev.ev[2 * i + 1]));
-            kernel_ms += ms;
-        }
-        const double call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
-        fill_dens_timing(timing, p, c, kernel_ms, launches, call_ms);
-    }
-    return 0;
+    if ((rc = ring.fetch(0, b_out))) return rc;
+    memcpy(range, ring.pin + o_range, b_range);
+    memcpy(counts, ring.pin + o_counts, b_counts);
+    memcpy(stats, ring.pin + o_stats, b_stats);
+    if (b_trace) memcpy(trace, ring.pin + o_trace, b_trace);
+    return ring.report({W, 256, 0}, (int)ring.uploads + 2);      // the chunks' kernels, resolve and finalize (the clear is not counted)
 }
 
 // ---- autocorrelation, effective sample size and split-R-hat of the draws (autocorr.hip; argument rules and thread split:
 // autocorr_plan.hpp; chunk cut: predictive_plan.hpp) ------------------------------------------------------------------------------
-
-void fill_acf_timing(hmcg_timing* t, const hmcg_autocorr* p, const DeviceCtx& c, double kernel_ms, int launches, double call_ms)
-{
-    memset(t, 0, sizeof *t);
-    t->kernel_ms = kernel_ms; t->launches = launches; t->call_ms = call_ms;
-    t->device = c.device; t->windows = p->W; t->buckets = 1; t->threads_per_window = 256;
-}
 
 hmcg_host::AcfArgs acf_args(const hmcg_autocorr* p)
 {
@@ -1511,106 +1410,67 @@ hmcg_host::AcfArgs acf_args(const hmcg_autocorr* p)
     return a;
 }
 
-// Caller holds c.mu and has made c.device current.  The running sums live in a context-owned arena (as density's piece sums do).
 int acf_device(DeviceCtx& c, const hmcg_autocorr* p, const double* dx, double* dacov, double* ddiag, hipStream_t stream, hmcg_timing* timing)
 {
-    int rc = grow_shared(c, c.acf, acf_work_bytes(p->W, p->C, p->L));
-    if (rc) return rc;
-    HIP_TRY(hipStreamWaitEvent(stream, c.ev_scr, 0));
-    if (timing) HIP_TRY(hipEventRecord(c.ev0, stream));
-    hmcg_host::AcfArgs a = acf_args(p);
-    a.x = dx; a.work = c.acf.base; a.acov = dacov; a.diag = ddiag; a.d_origin = 0; a.n = p->nd; a.pre = 0; a.ld = p->nd_ld;
-    HIP_TRY(launch_autocorr_accumulate(a, stream));
-    HIP_TRY(launch_autocorr_finalize(a, stream));
-    HIP_TRY(hipEventRecord(c.ev_scr, stream));
-    if (timing) {
-        HIP_TRY(hipEventRecord(c.ev1, stream));
-        HIP_TRY(hipEventSynchronize(c.ev1));
-        float ms = 0.f;
-        HIP_TRY(hipEventElapsedTime(&ms, c.ev0, c.ev1));
-        fill_acf_timing(timing, p, c, ms, 2, 0.0);
-    }
-    return 0;
+    return stat_device(c, c.acf, acf_work_bytes(p->W, p->C, p->L), stream, timing, {p->W, 256, 0}, 2, [&]() -> int {
+        hmcg_host::AcfArgs a = acf_args(p);
+        a.x = dx; a.work = c.acf.base; a.acov = dacov; a.diag = ddiag; a.d_origin = 0; a.n = p->nd; a.pre = 0; a.ld = p->nd_ld;
+        HIP_TRY(launch_autocorr_accumulate(a, stream));
+        HIP_TRY(launch_autocorr_finalize(a, stream));
+        return 0;
+    });
 }
 
-// Host entry on one device, as dens_host with a given range: one pass of whole-slab chunks through pinned staging, RING buffers
-// deep.  Every chunk is packed with the min(L, d0) draws before it in front (the host holds the whole array), so the device
-// carries nothing from chunk to chunk but the running sums, the pivot and the edge values in the work area.
+// Host entry on one device, through the upload ring in one pass.  Every chunk is packed with the min(L, d0) draws before it in
+// front (the host holds the whole array), so the device carries nothing from chunk to chunk but the running sums, the pivot and
+// the edge values in the work area.
 int acf_host(DeviceCtx& c, const hmcg_autocorr* p, const double* x, double* acov, double* diag, hmcg_timing* timing)
 {
-    const auto t_call = std::chrono::steady_clock::now();
     const int W = p->W, C = p->C, L = p->L;
-    long long cap = 0;
-    if (const char* cenv = diag_env("HMCG_CHUNK_DRAWS")) cap = atoll(cenv);
-    const long long cdraws = pred_chunk_draws(p->nd, W, C, cap);
-    const std::vector<PredChunk> chunks = pred_chunks(p->nd, cdraws);
-    const size_t wc = (size_t)W * (size_t)C;
-    const size_t n_acov = wc * (size_t)(L + 1), n_diag = wc * HMCG_ACF_STRIDE;
-    auto up = [](size_t n) { return (n + 255) & ~(size_t)255; };
-    const size_t b_acov = up(8 * n_acov), b_diag = up(8 * n_diag), b_out = b_acov + b_diag;
-    const size_t b_work = up(acf_work_bytes(W, C, L));
-    const size_t b_chunk = up(sizeof(double) * wc * (size_t)(cdraws + L));
-    const int nbuf = (int)std::min<size_t>(RING, chunks.size());
-    const size_t need_dev = b_out + b_work + b_chunk * (size_t)nbuf, need_pin = b_out + b_chunk * (size_t)nbuf;
-    if (c.dev.ensure(need_dev) || c.pin.ensure(need_pin)) {
-        set_err("workspace allocation failed (%zu B device, %zu B pinned)", need_dev, need_pin);
-        return HMCG_E_NOMEM;
-    }
-    char* dout = c.dev.base;
-    char* dwork = c.dev.base + b_out;
-    char* dchunk = dwork + b_work;
-    char* pout = c.pin.base;
-    char* pchunk = c.pin.base + b_out;
-
+    const size_t wc = (size_t)W * (size_t)C, ld = (size_t)p->nd_ld;
+    UploadRing ring(c, p->nd, W, C, timing);
+    const size_t b_acov = 8 * wc * (size_t)(L + 1), b_diag = 8 * wc * HMCG_ACF_STRIDE;
+    Layout io;
+    const size_t o_acov = io.add(b_acov), o_diag = io.add(b_diag);
+    int rc = ring.alloc(io, acf_work_bytes(W, C, L), wc * (size_t)(ring.cdraws + L));
+    if (rc) return rc;
     hmcg_host::AcfArgs a = acf_args(p);
-    a.work = dwork;
-    a.acov = reinterpret_cast<double*>(dout);
-    a.diag = reinterpret_cast<double*>(dout + b_acov);
+    a.work = ring.work;
+    a.acov = reinterpret_cast<double*>(ring.dev + o_acov);
+    a.diag = reinterpret_cast<double*>(ring.dev + o_diag);
+    rc = ring.run(
+        [&](const PredChunk& ch, double* pb) {
+            const long long pre = acf_pre(ch.d0, L);
+            return (size_t)(pack_columns(x, wc, ld, ch.d0 - pre, (size_t)(pre + ch.n), pb) - pb);
+        },
+        [&](const PredChunk& ch, double* db, hipStream_t s) -> int {
+            a.x = db; a.d_origin = ch.d0; a.n = ch.n; a.pre = acf_pre(ch.d0, L); a.ld = a.pre + ch.n;
+            HIP_TRY(launch_autocorr_accumulate(a, s));
+            return 0;
+        });
+    if (rc) return rc;
+    // (the finalize kernel counts as kernel time here: it walks every lag of every column)
+    if ((rc = ring.timed([&]() -> int { HIP_TRY(launch_autocorr_finalize(a, c.stream)); return 0; }))) return rc;
+    if ((rc = ring.fetch(0, io.total))) return rc;
+    memcpy(acov, ring.pin + o_acov, b_acov);
+    memcpy(diag, ring.pin + o_diag, b_diag);
+    return ring.report({W, 256, 0}, (int)ring.uploads + 1);
+}
 
-    struct Events {
-        std::vector<hipEvent_t> ev;
-        ~Events() { for (hipEvent_t e : ev) if (e) (void)hipEventDestroy(e); }
-    } tev;                                       // two per chunk, around its kernel (created only when timing is asked for)
-    if (timing) {
-        tev.ev.assign(2 * chunks.size() + 2, nullptr);
-        for (hipEvent_t& e : tev.ev) HIP_TRY(hipEventCreate(&e));
-    }
-    for (size_t ci = 0; ci < chunks.size(); ++ci) {
-        const PredChunk& ch = chunks[ci];
-        const int b = (int)(ci % (size_t)nbuf);
-        if (ci >= (size_t)nbuf) HIP_TRY(hipEventSynchronize(c.evk[b]));      // the kernel that read this buffer pair is done
-        double* pb = reinterpret_cast<double*>(pchunk + b_chunk * (size_t)b);
-        double* db = reinterpret_cast<double*>(dchunk + b_chunk * (size_t)b);
-        const long long pre = acf_pre(ch.d0, L);
-        const size_t n = (size_t)(pre + ch.n);
-        for (size_t q = 0; q < wc; ++q) memcpy(pb + q * n, x + q * (size_t)p->nd_ld + (size_t)(ch.d0 - pre), sizeof(double) * n);
-        HIP_TRY(hipMemcpyAsync(db, pb, sizeof(double) * wc * n, hipMemcpyHostToDevice, c.copy));
-        HIP_TRY(hipEventRecord(c.evc[b], c.copy));
-        HIP_TRY(hipStreamWaitEvent(c.stream, c.evc[b], 0));
-        a.x = db; a.d_origin = ch.d0; a.n = ch.n; a.pre = pre; a.ld = (long long)n;
-        if (timing) HIP_TRY(hipEventRecord(tev.ev[2 * ci], c.stream));
-        HIP_TRY(launch_autocorr_accumulate(a, c.stream));
-        if (timing) HIP_TRY(hipEventRecord(tev.ev[2 * ci + 1], c.stream));
-        HIP_TRY(hipEventRecord(c.evk[b], c.stream));
-    }
-    if (timing) HIP_TRY(hipEventRecord(tev.ev[2 * chunks.size()], c.stream));
-    HIP_TRY(launch_autocorr_finalize(a, c.stream));
-    if (timing) HIP_TRY(hipEventRecord(tev.ev[2 * chunks.size() + 1], c.stream));
-    HIP_TRY(hipMemcpyAsync(pout, dout, b_out, hipMemcpyDeviceToHost, c.stream));
-    HIP_TRY(hipStreamSynchronize(c.stream));
-    memcpy(acov, pout, 8 * n_acov);
-    memcpy(diag, pout + b_acov, 8 * n_diag);
-    if (timing) {
-        double kernel_ms = 0.0;
-        for (size_t i = 0; i <= chunks.size(); ++i) {
-            float ms = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms, tev.ev[2 * i], tev.ev[2 * i + 1]));
-            kernel_ms += ms;
-        }
-        const double call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
-        fill_acf_timing(timing, p, c, kernel_ms, (int)chunks.size() + 1, call_ms);
-    }
-    return 0;
+// The prologue of a compute entry on one device.  The argument check comes first and needs no device: a caller on a machine
+// without one still gets the argument errors.  Then the context of p->device, its lock, the device made current, and body(context).
+template <class P, class Check, class Body>
+int entry(const P* p, Check check, Body body)
+{
+    g_err[0] = 0;
+    char msg[160];
+    int rc = check(msg, sizeof msg);
+    if (rc) { set_err("%s", msg); return rc; }
+    DeviceCtx* c = nullptr;
+    if ((rc = get_context(p->device, &c))) return rc;
+    std::lock_guard<std::mutex> lk(c->mu);
+    HIP_TRY(hipSetDevice(c->phys));
+    return body(*c);
 }
 
 }  // namespace
@@ -1643,32 +1503,20 @@ int hmcg_estimate_batch_device(const hmcg_config* cfg, const double* dY, const i
                                double* dsummary, int32_t* dstatus, const hmcg_extras* dextras, void* stream,
                                hmcg_timing* timing)
 {
-    g_err[0] = 0;
-    int rc = validate(cfg);
-    if (rc) return rc;
-    DeviceCtx* c = nullptr;
-    rc = get_context(cfg->device, &c);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(hipSetDevice(c->phys));
-    hipStream_t s = stream ? (hipStream_t)stream : c->stream;
-    return launch_device(*c, cfg, dY, dT, dyreal, dmu, dsig2, dA, dpi_end, dfcast, dsummary, dstatus, dextras, s, timing);
+    return entry(cfg, [&](char* msg, size_t n) { return validate(cfg, msg, n); }, [&](DeviceCtx& c) {
+        hipStream_t s = stream ? (hipStream_t)stream : c.stream;
+        return launch_device(c, cfg, dY, dT, dyreal, dmu, dsig2, dA, dpi_end, dfcast, dsummary, dstatus, dextras, s, timing);
+    });
 }
 
 int hmcg_estimate_batch(const hmcg_config* cfg, const double* Y, const int32_t* T, const double* yreal, double* mu,
                         double* sig2, double* A, double* pi_end, double* fcast, double* summary, int32_t* status,
                         const hmcg_extras* extras, hmcg_timing* timing)
 {
-    g_err[0] = 0;
-    int rc = validate(cfg);
-    if (rc) return rc;
-    DeviceCtx* c = nullptr;
-    rc = get_context(cfg->device, &c);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(hipSetDevice(c->phys));
-    const HostArrays h{Y, T, yreal, mu, sig2, A, pi_end, fcast, summary, status, extras};
-    return run_host_on_device(*c, cfg, nullptr, cfg->W, h, timing);
+    return entry(cfg, [&](char* msg, size_t n) { return validate(cfg, msg, n); }, [&](DeviceCtx& c) {
+        const HostArrays h{Y, T, yreal, mu, sig2, A, pi_end, fcast, summary, status, extras};
+        return run_host_on_device(c, cfg, nullptr, cfg->W, h, timing);
+    });
 }
 
 int hmcg_estimate_batch_multi(const hmcg_config* cfg, int32_t n_devices, const int32_t* device_ids, const double* Y,
@@ -1676,8 +1524,9 @@ int hmcg_estimate_batch_multi(const hmcg_config* cfg, int32_t n_devices, const i
                               double* fcast, double* summary, int32_t* status, const hmcg_extras* extras, hmcg_timing* timing)
 {
     g_err[0] = 0;
-    int rc = validate(cfg);
-    if (rc) return rc;
+    char msg[160];
+    int rc = validate(cfg, msg, sizeof msg);
+    if (rc) { set_err("%s", msg); return rc; }
     if (!Y || !T) { set_err("Y and T are required"); return HMCG_E_BADARG; }
     if (n_devices < 1 || n_devices > HMCG_MAXDEV) { set_err("n_devices %d out of range (1..%d)", n_devices, HMCG_MAXDEV); return HMCG_E_BADARG; }
     std::vector<int32_t> devs((size_t)n_devices);
@@ -1723,149 +1572,75 @@ int hmcg_estimate_batch_multi(const hmcg_config* cfg, int32_t n_devices, const i
 int hmcg_predictive_cdf_device(const hmcg_predictive* p, const double* dmu, const double* dsig2, const double* dpi_end, const double* dA,
                                const double* dgrid, double* dcdf, void* stream, hmcg_timing* timing)
 {
-    g_err[0] = 0;
-    char msg[160];
-    int rc = check_predictive(p, dmu, dsig2, dpi_end, dA, dgrid, dcdf, false, msg, sizeof msg);
-    if (rc) { set_err("%s", msg); return rc; }
-    DeviceCtx* c = nullptr;
-    rc = get_context(p->device, &c);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(hipSetDevice(c->phys));
-    return predictive_device(*c, p, dmu, dsig2, dpi_end, dA, dgrid, dcdf, stream ? (hipStream_t)stream : c->stream, timing);
+    return entry(p, [&](char* msg, size_t n) { return check_predictive(p, dmu, dsig2, dpi_end, dA, dgrid, dcdf, false, msg, n); },
+                 [&](DeviceCtx& c) {
+        return predictive_device(c, p, dmu, dsig2, dpi_end, dA, dgrid, dcdf, stream ? (hipStream_t)stream : c.stream, timing);
+    });
 }
 
 int hmcg_predictive_cdf(const hmcg_predictive* p, const double* mu, const double* sig2, const double* pi_end, const double* A,
                         const double* grid, double* cdf, hmcg_timing* timing)
 {
-    g_err[0] = 0;
-    char msg[160];
-    int rc = check_predictive(p, mu, sig2, pi_end, A, grid, cdf, true, msg, sizeof msg);
-    if (rc) { set_err("%s", msg); return rc; }
-    DeviceCtx* c = nullptr;
-    rc = get_context(p->device, &c);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(hipSetDevice(c->phys));
-    return predictive_host(*c, p, mu, sig2, pi_end, A, grid, cdf, timing);
+    return entry(p, [&](char* msg, size_t n) { return check_predictive(p, mu, sig2, pi_end, A, grid, cdf, true, msg, n); },
+                 [&](DeviceCtx& c) { return predictive_host(c, p, mu, sig2, pi_end, A, grid, cdf, timing); });
 }
 
 int hmcg_bias_moments_device(const hmcg_bias* p, const double* dmu, const double* dpi_end, const double* dA, const double* dfcast,
                              double* dout, void* stream, hmcg_timing* timing)
 {
-    g_err[0] = 0;
-    char msg[160];
-    int rc = check_bias(p, dmu, dpi_end, dA, dfcast, dout, msg, sizeof msg);
-    if (rc) { set_err("%s", msg); return rc; }
-    DeviceCtx* c = nullptr;
-    rc = get_context(p->device, &c);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(hipSetDevice(c->phys));
-    return bias_device(*c, p, dmu, dpi_end, dA, dfcast, dout, stream ? (hipStream_t)stream : c->stream, timing);
+    return entry(p, [&](char* msg, size_t n) { return check_bias(p, dmu, dpi_end, dA, dfcast, dout, msg, n); }, [&](DeviceCtx& c) {
+        return bias_device(c, p, dmu, dpi_end, dA, dfcast, dout, stream ? (hipStream_t)stream : c.stream, timing);
+    });
 }
 
 int hmcg_bias_moments(const hmcg_bias* p, const double* mu, const double* pi_end, const double* A, const double* fcast, double* out,
                       hmcg_timing* timing)
 {
-    g_err[0] = 0;
-    char msg[160];
-    int rc = check_bias(p, mu, pi_end, A, fcast, out, msg, sizeof msg);
-    if (rc) { set_err("%s", msg); return rc; }
-    DeviceCtx* c = nullptr;
-    rc = get_context(p->device, &c);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(hipSetDevice(c->phys));
-    return bias_host(*c, p, mu, pi_end, A, fcast, out, timing);
+    return entry(p, [&](char* msg, size_t n) { return check_bias(p, mu, pi_end, A, fcast, out, msg, n); },
+                 [&](DeviceCtx& c) { return bias_host(c, p, mu, pi_end, A, fcast, out, timing); });
 }
 
 int hmcg_mixture_moments_device(const hmcg_mixmom* p, const double* dmu, const double* dsig2, const double* dpi_end, const double* dA,
                                 double* dout, void* stream, hmcg_timing* timing)
 {
-    g_err[0] = 0;
-    char msg[160];
-    int rc = check_mixmom(p, dmu, dsig2, dpi_end, dA, dout, msg, sizeof msg);
-    if (rc) { set_err("%s", msg); return rc; }
-    DeviceCtx* c = nullptr;
-    rc = get_context(p->device, &c);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(hipSetDevice(c->phys));
-    return mix_device(*c, p, dmu, dsig2, dpi_end, dA, dout, stream ? (hipStream_t)stream : c->stream, timing);
+    return entry(p, [&](char* msg, size_t n) { return check_mixmom(p, dmu, dsig2, dpi_end, dA, dout, msg, n); }, [&](DeviceCtx& c) {
+        return mix_device(c, p, dmu, dsig2, dpi_end, dA, dout, stream ? (hipStream_t)stream : c.stream, timing);
+    });
 }
 
 int hmcg_mixture_moments(const hmcg_mixmom* p, const double* mu, const double* sig2, const double* pi_end, const double* A, double* out,
                          hmcg_timing* timing)
 {
-    g_err[0] = 0;
-    char msg[160];
-    int rc = check_mixmom(p, mu, sig2, pi_end, A, out, msg, sizeof msg);
-    if (rc) { set_err("%s", msg); return rc; }
-    DeviceCtx* c = nullptr;
-    rc = get_context(p->device, &c);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(hipSetDevice(c->phys));
-    return mix_host(*c, p, mu, sig2, pi_end, A, out, timing);
+    return entry(p, [&](char* msg, size_t n) { return check_mixmom(p, mu, sig2, pi_end, A, out, msg, n); },
+                 [&](DeviceCtx& c) { return mix_host(c, p, mu, sig2, pi_end, A, out, timing); });
 }
 
 int hmcg_chain_density_device(const hmcg_density* p, const double* dx, const double* dlo_hi, double* drange, int64_t* dcounts,
                               double* dstats, double* dtrace, void* stream, hmcg_timing* timing)
 {
-    g_err[0] = 0;
-    char msg[160];
-    int rc = check_density(p, dx, dlo_hi, drange, dcounts, dstats, dtrace, false, msg, sizeof msg);
-    if (rc) { set_err("%s", msg); return rc; }
-    DeviceCtx* c = nullptr;
-    rc = get_context(p->device, &c);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(hipSetDevice(c->phys));
-    return dens_device(*c, p, dx, dlo_hi, drange, dcounts, dstats, dtrace, stream ? (hipStream_t)stream : c->stream, timing);
+    return entry(p, [&](char* msg, size_t n) { return check_density(p, dx, dlo_hi, drange, dcounts, dstats, dtrace, false, msg, n); },
+                 [&](DeviceCtx& c) {
+        return dens_device(c, p, dx, dlo_hi, drange, dcounts, dstats, dtrace, stream ? (hipStream_t)stream : c.stream, timing);
+    });
 }
 
 int hmcg_chain_density(const hmcg_density* p, const double* x, const double* lo_hi, double* range, int64_t* counts, double* stats,
                        double* trace, hmcg_timing* timing)
 {
-    g_err[0] = 0;
-    char msg[160];
-    int rc = check_density(p, x, lo_hi, range, counts, stats, trace, true, msg, sizeof msg);
-    if (rc) { set_err("%s", msg); return rc; }
-    DeviceCtx* c = nullptr;
-    rc = get_context(p->device, &c);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(hipSetDevice(c->phys));
-    return dens_host(*c, p, x, lo_hi, range, counts, stats, trace, timing);
+    return entry(p, [&](char* msg, size_t n) { return check_density(p, x, lo_hi, range, counts, stats, trace, true, msg, n); },
+                 [&](DeviceCtx& c) { return dens_host(c, p, x, lo_hi, range, counts, stats, trace, timing); });
 }
 
 int hmcg_chain_autocorr_device(const hmcg_autocorr* p, const double* dx, double* dacov, double* ddiag, void* stream, hmcg_timing* timing)
 {
-    g_err[0] = 0;
-    char msg[160];
-    int rc = check_autocorr(p, dx, dacov, ddiag, msg, sizeof msg);
-    if (rc) { set_err("%s", msg); return rc; }
-    DeviceCtx* c = nullptr;
-    rc = get_context(p->device, &c);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(hipSetDevice(c->phys));
-    return acf_device(*c, p, dx, dacov, ddiag, stream ? (hipStream_t)stream : c->stream, timing);
+    return entry(p, [&](char* msg, size_t n) { return check_autocorr(p, dx, dacov, ddiag, msg, n); },
+                 [&](DeviceCtx& c) { return acf_device(c, p, dx, dacov, ddiag, stream ? (hipStream_t)stream : c.stream, timing); });
 }
 
 int hmcg_chain_autocorr(const hmcg_autocorr* p, const double* x, double* acov, double* diag, hmcg_timing* timing)
 {
-    g_err[0] = 0;
-    char msg[160];
-    int rc = check_autocorr(p, x, acov, diag, msg, sizeof msg);
-    if (rc) { set_err("%s", msg); return rc; }
-    DeviceCtx* c = nullptr;
-    rc = get_context(p->device, &c);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(c->mu);
-    HIP_TRY(hipSetDevice(c->phys));
-    return acf_host(*c, p, x, acov, diag, timing);
+    return entry(p, [&](char* msg, size_t n) { return check_autocorr(p, x, acov, diag, msg, n); },
+                 [&](DeviceCtx& c) { return acf_host(c, p, x, acov, diag, timing); });
 }
 
 }  // extern "C"
