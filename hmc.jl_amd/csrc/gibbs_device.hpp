@@ -716,7 +716,7 @@ struct SweepShared {
     double wtot[NW][K * K];       // forward scan: wave totals
     double pfirst[NT + 1][K];     // filtered probs at each thread's first step
     uint32_t wmap[NW];            // backward scan: wave totals
-    double ulast;                 // the uniform that draws X[T-1]
+    double ulast;                 // the uniform that draws X[T-1] (rows that draw it behind Bd; else the owner keeps it)
     int xfirst[NT + 1];           // init only: first state of each thread's chunk
     double bred[NW];              // generic block reductions (init)
     int selcnt[2][8][3];          // block_select (init): by round parity, wave, digit
@@ -1097,7 +1097,8 @@ void gibbs_sweeps_kernel(const KernelParams p)
     }
     __syncthreads();
     xnext = sh.xfirst[helper ? NT : tid + 1];
-    int x_end = sh.x_end;
+    int x_end = sh.x_end;                // (rows without OWNER_DRAW, below: tid 0 carries X[T-1] to the next parameter phase)
+    (void)x_end;
 
     Rng rng{p.seed_lo, p.seed_hi, p.window_ids ? p.window_ids[w] : p.window_base + (uint32_t)w, 0u};
     const int NS = 3 * K + KK + 2 * p.H;
@@ -1397,6 +1398,12 @@ void gibbs_sweeps_kernel(const KernelParams p)
     constexpr int NPK = Sh::NPK;
     constexpr bool PADCNT = PADMARK && !SIG && NWORD == 1 && NF < FPW;    // counts without `t + 1 < T` predicates
     static_assert(64 * L < 65536, "wave totals fit their fields (10 bits while 64 L < 1024, else 16)");
+    // X[T-1] is drawn by the owner of step T-1 ahead of Bd, from registers, and the later waves' maps behind Be are fetched
+    // with one wait (see both places) in the rows that hold their registers without a spill: K = 2, and K = 3 up to four steps
+    // per thread on the base path.  The register-capped rows (K = 4, L > 4, the signal and smoothing paths at K >= 3) keep
+    // the draw behind Bd by every thread from sh.ulast / th.pi_end: the owner's form cost some of them a spilled VGPR or
+    // scratch bytes (profiles/r08/isa_lint_tables_every_row.txt).
+    constexpr bool OWNER_DRAW = K == 2 || (K == 3 && L <= 4 && !SIG && !SMOOTH);
     // SPLIT takes the statistics in two parts: the integer counts (all that the gamma and Dirichlet draws need:
     // publish_counts) and the pivoted sums (which enter the sig2 / mu draws only: publish_sums) -- the two halves of
     // publish_stats below, statement for statement; every other flavour keeps publish_stats as it was.  The COUNTS half
@@ -1528,12 +1535,14 @@ void gibbs_sweeps_kernel(const KernelParams p)
                 for (int d = 0; d < NPK; ++d) sh.red_pk[wave][d] = pk[d];
             }
         }
-        if (COUNTS ? tid == 0 : (dw == 0 && lane == 0)) {
-            if constexpr (SUMS) {
+        if constexpr (SUMS || !OWNER_DRAW) {
+            if (COUNTS ? tid == 0 : (dw == 0 && lane == 0)) {
+                if constexpr (SUMS) {
 #pragma unroll
-                for (int k = 0; k < K; ++k) sh.pivot[k] = pv[k];
+                    for (int k = 0; k < K; ++k) sh.pivot[k] = pv[k];
+                }
+                if constexpr (COUNTS) sh.x_end = x_end;
             }
-            if constexpr (COUNTS) sh.x_end = x_end;
         }
     };
     auto publish_stats = [&]() __attribute__((always_inline)) {
@@ -1656,7 +1665,7 @@ void gibbs_sweeps_kernel(const KernelParams p)
         if (tid == 0) {
 #pragma unroll
             for (int k = 0; k < K; ++k) sh.pivot[k] = pivot[k];
-            sh.x_end = x_end;
+            if constexpr (!OWNER_DRAW) sh.x_end = x_end;
         }
     };
     auto publish_counts = [&]() __attribute__((always_inline)) { publish(std::true_type(), std::false_type(), x, pivot, t0, wave); };
@@ -2446,15 +2455,33 @@ void gibbs_sweeps_kernel(const KernelParams p)
         }
 #pragma unroll
         for (int s = 0; s < K; ++s) sh.pfirst[tid][s] = pf[0][s];
-        // owner of the last step publishes pif[T-1,:] (unsorted) and its uniform; X[T-1] itself (sorted
-        // labels, :464) is then drawn redundantly by every thread after the barrier (no divergent tail)
+        // owner of the last step publishes pif[T-1,:] (unsorted, for the outputs job) and draws X[T-1] itself (sorted
+        // labels, :464) from what it holds in registers: the value is consumed by this thread's own map of step T-1 behind
+        // Bd and by wave 0's next parameter phase (sh.x_end: read after Ba and Ba2, written here between Bc and Bd -- two
+        // barriers either way; the store moved behind Bd, on every wave's path, measured slower).  Nobody reads LDS for it
+        // behind Bd.  The rows without OWNER_DRAW publish the uniform instead, and every thread draws X[T-1] redundantly
+        // after the barrier.
+        int xlast = 0;
         if (tid == owner) {
 #pragma unroll
             for (int l = 0; l < L; ++l)
                 if (l == l_last) {
 #pragma unroll
                     for (int s = 0; s < K; ++s) th.pi_end[s] = pf[l][s];
-                    sh.ulast = ux[l];
+                    if constexpr (OWNER_DRAW) {
+                        double cp = 0.0;
+#pragma unroll
+                        for (int q = 0; q < K - 1; ++q) {
+                            double pq = 0.0;
+#pragma unroll
+                            for (int s = 0; s < K; ++s) pq = (order[q] == s) ? pf[l][s] : pq;
+                            cp += pq;
+                            xlast += (cp <= ux[l]) ? 1 : 0;
+                        }
+                        sh.x_end = xlast;
+                    } else {
+                        sh.ulast = ux[l];
+                    }
                 }
         }
         if constexpr (SIG) {
@@ -2562,8 +2589,7 @@ void gibbs_sweeps_kernel(const KernelParams p)
         // left, and come back through two lane reads each.  Rebuilt here from two per-lane values with one compare each.
         int dlast = T - 1 - t0, lane_o = lane;       // slot of the last step in this thread (negative: all padding; >= L: none)
         asm volatile("" : "+v"(dlast), "+v"(lane_o));
-        int xlast = 0;
-        {
+        if constexpr (!OWNER_DRAW) {
             const double ulast = sh.ulast;
             double cp = 0.0;
 #pragma unroll
@@ -2634,14 +2660,27 @@ void gibbs_sweeps_kernel(const KernelParams p)
         STAMP(10);
         SWEEP_BARRIER(5);                                                  // Be
         STAMP(11);
+        // (the later waves' maps: the OWNER_DRAW rows of up to four waves fetch wmap[1..NW-1] at once -- every read on its way
+        //  before the one wait -- and compose from registers; read inside the branches below they are one dependent LDS round
+        //  trip per branch)
         uint32_t Rw = BMAP_IDENTITY;
+        if constexpr (OWNER_DRAW && NW > 2 && NW <= 4) {
+            uint32_t wm[NW];
 #pragma unroll
-        for (int ww = NW - 1; ww >= 1; --ww) if (ww > wave_u) Rw = bmap_compose(sh.wmap[ww], Rw);
+            for (int ww = 1; ww < NW; ++ww) wm[ww] = sh.wmap[ww];
+            __builtin_amdgcn_s_waitcnt(0xC07F);          // lgkmcnt(0)
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int ww = NW - 1; ww >= 1; --ww) if (ww > wave_u) Rw = bmap_compose(wm[ww], Rw);
+        } else {
+#pragma unroll
+            for (int ww = NW - 1; ww >= 1; --ww) if (ww > wave_u) Rw = bmap_compose(sh.wmap[ww], Rw);
+        }
         const uint32_t Hx = (uint32_t)dpp_i32<DPP_WAVE_SHL1, 0xF>((int)BMAP_IDENTITY, (int)Hm);   // lane 63: identity
         const uint32_t Sfx = bmap_compose(Hx, Rw);     // everything after this thread's chunk
         int sin = bmap_apply(Sfx, XPAD);               // constant map below T-1; the identity (-> XPAD) for the last thread
         xnext = sin;
-        x_end = xlast;
+        if constexpr (!OWNER_DRAW) x_end = xlast;
 #pragma unroll
         for (int l = L - 1; l >= 0; --l) {
             sin = bmap_apply(gmap[l], sin);      // (slots at or beyond T: XPAD when PADMARK, else a value that is never read)
