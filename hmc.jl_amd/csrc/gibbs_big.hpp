@@ -290,7 +290,7 @@ __global__ __launch_bounds__(NT) void gibbs_sweeps_kernel_big(const KernelParams
     constexpr int NSH = NW - 1;
 
     // ---- shadow jobs -------------------------------------------------------------------------
-    auto job_prep = [&](int sw) __attribute__((always_inline)) {                    // see gibbs_device.hpp job_prep
+    auto job_prep = [&](int sw) __attribute__((always_inline)) {                    // the task list: gibbs_device.hpp job_prep
         Rng g = rng;
         g.sweep = (uint32_t)sw;
         RngBuf<K>& rb = sh.rb[sw & 1];
@@ -298,53 +298,16 @@ __global__ __launch_bounds__(NT) void gibbs_sweeps_kernel_big(const KernelParams
         for (int base = 0; base < NTASK; base += 64) {
             const int task = base + lane;
             const bool live = task < NTASK;
-            const bool t_rho = task < K;
-            const bool t_gx = !t_rho && task < K + 2 * NG;
-            const bool t_z = !t_rho && !t_gx && task < 2 * K + 2 * NG;
-            const bool t_gl = !t_rho && !t_gx && !t_z;
-            const int gt = t_gx ? task - K : task - (2 * K + 2 * NG);
-            const int role = gt >> 1, j = gt & 1;
-            uint32_t site = SITE_RHO, elem = (uint32_t)task, idx = 0;
-            if (t_gx || t_gl) {
-                site = role < K ? SITE_SIG2 : SITE_A;
-                elem = role < K ? (uint32_t)role : (uint32_t)(role - K);
-                idx = 2u * (uint32_t)j + (t_gl ? 1u : 0u);
-            } else if (t_z) {
-                site = SITE_MU; elem = (uint32_t)(task - (K + 2 * NG));
-            }
+            HMCG_PREP_TASK_KIND(task);
+            HMCG_PREP_TASK_BLOCK(task);
             uint32_t r[4];
             g.block(site, elem, idx, r);
             const double uraw = u53(r[0], r[1]);
             const double lg = log_fast(1.0 - uraw);
-            double val = lg;
-            if (t_gx || t_z) val = sqrt_fast(-2.0 * lg) * cos2pi_fast(u53(r[2], r[3]));
-            double rs = 0.0;
-#pragma unroll
-            for (int i = 0; i < K; ++i) rs += -__shfl(lg, i, 64);
-            if (live) {
-                if (t_rho) rb.rho[task] = -lg * (1.0 / rs);
-                else if (t_gx) rb.x[role][j] = val;
-                else if (t_z) rb.z[task - (K + 2 * NG)] = val;
-                else if (t_gl) { rb.lu[role][j] = val; rb.uu[role][j] = uraw; }
-            }
+            HMCG_PREP_TASK_FINISH(task, r[2], r[3]);
         }
     };
-    auto job_uniforms = [&](int sw, int b0, int b1) __attribute__((always_inline)) {
-        Rng g = rng;
-        g.sweep = (uint32_t)sw;
-        for (int b = b0 + lane; b < b1; b += 128) {
-            const int bb = b + 64;
-            uint32_t r[4], q[4];
-            g.block(SITE_X, 0, (uint32_t)b, r);
-            g.block(SITE_X, 0, (uint32_t)bb, q);
-            uxs[2 * b] = u53(r[0], r[1]);
-            if (2 * b + 1 < cap) uxs[2 * b + 1] = u53(r[2], r[3]);
-            if (bb < b1) {
-                uxs[2 * bb] = u53(q[0], q[1]);
-                if (2 * bb + 1 < cap) uxs[2 * bb + 1] = u53(q[2], q[3]);
-            }
-        }
-    };
+    auto job_uniforms = [&](int sw, int b0, int b1) __attribute__((always_inline)) { uniform_blocks(rng, sw, lane, b0, b1, uxs, cap); };
     // outputs: parameter roles [0, NP) take ceil(NP/64) passes over wave 1; forecast roles sit on the last wave
     constexpr int OUT_WAVE = 1, FC_WAVE = NW - 1;
     constexpr int NP = 3 * K + KK;

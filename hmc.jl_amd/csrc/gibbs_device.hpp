@@ -891,6 +891,65 @@ __device__ __forceinline__ void sort_order(const double (&mu)[K], int (&order)[K
 #define SWEEP_BARRIER(i) __syncthreads()
 #endif
 
+// The tasks of a sweep's RNG preparation (the list: at job_prep below), shared by job_prep of either kernel and the SPLIT
+// helper's two stages (prep_head / prep_tail).  Macros, not functions: as __forceinline__ templates or lambdas, in every form
+// tried, the same statements moved SGPR spills in every kernel (profiles/r09/README.md).  They declare into the caller's scope
+// and read its K, NG, live, lg, uraw and rb.  The kind of task `task_` (t_rho | t_gx | t_z | t_gl) and, for a gamma task
+// (gx / gl), its role and attempt j ...
+#define HMCG_PREP_TASK_KIND(task_)                                                               \
+    const bool t_rho = task_ < K;                                                                \
+    const bool t_gx = !t_rho && task_ < K + 2 * NG;                                              \
+    const bool t_z = !t_rho && !t_gx && task_ < 2 * K + 2 * NG;                                  \
+    const bool t_gl = !t_rho && !t_gx && !t_z;                                                   \
+    const int gt = t_gx ? task_ - K : task_ - (2 * K + 2 * NG);      /* gamma task id for gx / gl */ \
+    const int role = gt >> 1, j = gt & 1
+// ... and its Philox block (site, elem, idx)
+#define HMCG_PREP_TASK_BLOCK(task_)                                                              \
+    uint32_t site = SITE_RHO, elem = (uint32_t)task_, idx = 0;                                   \
+    if (t_gx || t_gl) {                                                                          \
+        site = role < K ? SITE_SIG2 : SITE_A;                                                    \
+        elem = role < K ? (uint32_t)role : (uint32_t)(role - K);                                 \
+        idx = 2u * (uint32_t)j + (t_gl ? 1u : 0u);                                               \
+    } else if (t_z) {                                                                            \
+        site = SITE_MU; elem = (uint32_t)(task_ - (K + 2 * NG));                                 \
+    }
+// ... and, from its log lg = log(1 - uraw) and the block's second half, what it leaves in rb (live: the task exists): Box-Muller
+// for the normals; rho ~ Dirichlet(ones(K)) (:350-356) is K exponentials normalised in element order (lanes 0..K-1 of pass 0)
+#define HMCG_PREP_TASK_FINISH(task_, r2_, r3_)                                                   \
+    double val = lg;                                                                             \
+    if (t_gx || t_z) val = sqrt_fast(-2.0 * lg) * cos2pi_fast(u53(r2_, r3_));                    \
+    double rs = 0.0;                                                                             \
+    _Pragma("unroll") for (int i = 0; i < K; ++i) rs += -__shfl(lg, i, 64);                      \
+    if (live) {                                                                                  \
+        if (t_rho) rb.rho[task_] = -lg * (1.0 / rs);                                             \
+        else if (t_gx) rb.x[role][j] = val;                                                      \
+        else if (t_z) rb.z[task_ - (K + 2 * NG)] = val;                                          \
+        else if (t_gl) { rb.lu[role][j] = val; rb.uu[role][j] = uraw; }                          \
+    }
+
+// the two state-draw uniforms of Philox block b (steps 2b, 2b + 1; `end`: steps the buffer holds; P: double* in LDS or HBM)
+template <class P>
+__device__ __forceinline__ void put_uniforms(P ub, int b, const uint32_t (&r)[4], int end)
+{
+    ub[2 * b] = u53(r[0], r[1]);
+    if (2 * b + 1 < end) ub[2 * b + 1] = u53(r[2], r[3]);
+}
+
+// Philox blocks [b0, b1) of the state-draw uniforms of sweep sw, dealt round-robin to the calling wave's lanes
+template <class P>
+__device__ __forceinline__ void uniform_blocks(Rng g, int sw, int lane, int b0, int b1, P ub, int end)
+{
+    g.sweep = (uint32_t)sw;
+    for (int b = b0 + lane; b < b1; b += 128) {       // two independent blocks per trip (ILP across the mul chains)
+        const int bb = b + 64;
+        uint32_t r[4], q[4];
+        g.block(SITE_X, 0, (uint32_t)b, r);
+        g.block(SITE_X, 0, (uint32_t)bb, q);
+        put_uniforms(ub, b, r, end);
+        if (bb < b1) put_uniforms(ub, bb, q, end);
+    }
+}
+
 // ------------------------------------------------------------- kernel ----
 
 // NH > 0 adds NH "helper" waves (threads NT .. NT+64*NH-1) that own no time steps: they carry the per-draw
@@ -1121,36 +1180,13 @@ void gibbs_sweeps_kernel(const KernelParams p)
         for (int base = 0; base < NTASK; base += 64) {
             const int task = base + lane;
             const bool live = task < NTASK;
-            const bool t_rho = task < K;
-            const bool t_gx = !t_rho && task < K + 2 * NG;
-            const bool t_z = !t_rho && !t_gx && task < 2 * K + 2 * NG;
-            const bool t_gl = !t_rho && !t_gx && !t_z;
-            const int gt = t_gx ? task - K : task - (2 * K + 2 * NG);      // gamma task id for gx / gl
-            const int role = gt >> 1, j = gt & 1;
-            uint32_t site = SITE_RHO, elem = (uint32_t)task, idx = 0;
-            if (t_gx || t_gl) {
-                site = role < K ? SITE_SIG2 : SITE_A;
-                elem = role < K ? (uint32_t)role : (uint32_t)(role - K);
-                idx = 2u * (uint32_t)j + (t_gl ? 1u : 0u);
-            } else if (t_z) {
-                site = SITE_MU; elem = (uint32_t)(task - (K + 2 * NG));
-            }
+            HMCG_PREP_TASK_KIND(task);
+            HMCG_PREP_TASK_BLOCK(task);
             uint32_t r[4];
             g.block(site, elem, idx, r);
             const double uraw = u53(r[0], r[1]);
             const double lg = log_fast(1.0 - uraw);
-            double val = lg;
-            if (t_gx || t_z) val = sqrt_fast(-2.0 * lg) * cos2pi_fast(u53(r[2], r[3]));   // Box-Muller
-            // rho ~ Dirichlet(ones(K)) (:350-356): K exponentials normalised in element order (lanes 0..K-1 of pass 0)
-            double rs = 0.0;
-#pragma unroll
-            for (int i = 0; i < K; ++i) rs += -__shfl(lg, i, 64);
-            if (live) {
-                if (t_rho) rb.rho[task] = -lg * (1.0 / rs);
-                else if (t_gx) rb.x[role][j] = val;
-                else if (t_z) rb.z[task - (K + 2 * NG)] = val;
-                else if (t_gl) { rb.lu[role][j] = val; rb.uu[role][j] = uraw; }
-            }
+            HMCG_PREP_TASK_FINISH(task, r[2], r[3]);
         }
     };
     static_assert(NW > 2 || 3 * K + KK <= 64 - 2 * HMCG_MAXH, "parameter and forecast output lanes share a wave when NW == 2");
@@ -1161,23 +1197,7 @@ void gibbs_sweeps_kernel(const KernelParams p)
         if constexpr (SPLIT) return (sw & 1) ? sh.ux2 : sh.ux;
         else return sh.ux;
     };
-    auto job_uniforms = [&](int sw, int b0, int b1) __attribute__((always_inline)) {
-        Rng g = rng;
-        g.sweep = (uint32_t)sw;
-        double* const ub = ux_of(sw);
-        for (int b = b0 + lane; b < b1; b += 128) {       // two independent blocks per trip (ILP across the mul chains)
-            const int bb = b + 64;
-            uint32_t r[4], q[4];
-            g.block(SITE_X, 0, (uint32_t)b, r);
-            g.block(SITE_X, 0, (uint32_t)bb, q);
-            ub[2 * b] = u53(r[0], r[1]);
-            if (2 * b + 1 < NT * L) ub[2 * b + 1] = u53(r[2], r[3]);
-            if (bb < b1) {
-                ub[2 * bb] = u53(q[0], q[1]);
-                if (2 * bb + 1 < NT * L) ub[2 * bb + 1] = u53(q[2], q[3]);
-            }
-        }
-    };
+    auto job_uniforms = [&](int sw, int b0, int b1) __attribute__((always_inline)) { uniform_blocks(rng, sw, lane, b0, b1, ux_of(sw), NT * L); };
     // half a trip: blocks [b0, b1), b1 - b0 <= 64, one per lane
     auto job_uniforms_half = [&](int sw, int b0, int b1) __attribute__((always_inline)) {
         Rng g = rng;
@@ -1187,8 +1207,7 @@ void gibbs_sweeps_kernel(const KernelParams p)
         if (b < b1) {
             uint32_t r[4];
             g.block(SITE_X, 0, (uint32_t)b, r);
-            ub[2 * b] = u53(r[0], r[1]);
-            if (2 * b + 1 < NT * L) ub[2 * b + 1] = u53(r[2], r[3]);
+            put_uniforms(ub, b, r, NT * L);
         }
     };
 
@@ -1406,14 +1425,18 @@ void gibbs_sweeps_kernel(const KernelParams p)
     constexpr bool OWNER_DRAW = K == 2 || (K == 3 && L <= 4 && !SIG && !SMOOTH);
     // SPLIT takes the statistics in two parts: the integer counts (all that the gamma and Dirichlet draws need:
     // publish_counts) and the pivoted sums (which enter the sig2 / mu draws only: publish_sums) -- the two halves of
-    // publish_stats below, statement for statement; every other flavour keeps publish_stats as it was.  The COUNTS half
-    // always describes the calling wave's OWN steps (it reads x, xnext, t0 and wave and ignores xs_, pv, tq0, dw: only
-    // publish_counts calls it).  The SUMS half takes the sums of the steps tq0 + l of the calling wave's lanes (states xs_,
-    // observations in its y[]) about the pivots pv and publishes them as wave dw's: a window's own wave passes its own
-    // (x, pivot, t0, wave); the helper wave stands in for wave 0.
+    // publish; every other flavour takes both at once.  The COUNTS half always describes the calling wave's OWN steps (it
+    // reads x, xnext, t0 and wave).  The SUMS half alone takes the sums of the steps tq0 + l of the calling wave's lanes
+    // (states xs_, observations in its y[]) about the pivots pv and publishes them as wave dw's: a window's own wave passes
+    // its own (x, pivot, t0, wave); the helper wave stands in for wave 0.  Beside the counts the sums are the calling wave's
+    // own as well, and are then named as the kernel's x, pivot, t0 and wave, not through the arguments: through the arguments,
+    // or called from inside one more lambda, the same statements moved registers in the K = 2 and K = 4 rows (profiles/r09).
     auto publish = [&](auto with_counts, auto with_sums, const int (&xs_)[L], const double (&pv)[K], int tq0, int dw) __attribute__((always_inline)) {
         constexpr bool COUNTS = decltype(with_counts)::value, SUMS = decltype(with_sums)::value;
-        static_assert(COUNTS != SUMS, "one half at a time: publish_stats is the whole");
+        const double* const pq = COUNTS ? pivot : pv;
+        const int& dq = COUNTS ? wave : dw;
+        const int* const xq = COUNTS ? x : xs_;
+        const int& tq = COUNTS ? t0 : tq0;
         unsigned pk[NPK];
         if constexpr (COUNTS) {
         // ---- transition counts C_ij: per-thread PB-bit fields -> 16-bit fields -> one DPP integer sum per word
@@ -1461,6 +1484,7 @@ void gibbs_sweeps_kernel(const KernelParams p)
         }
         wave_sum_words_lane63<NPK>(pk);
         }
+        if constexpr (COUNTS && SUMS) { STAMP(19); }
         if constexpr (SUMS) {
         // ---- pivoted sums by state: d1_i = sum (y - pivot_i), d2_i = sum (y - pivot_i)^2 over the observation
         // positions (and, on the signal path, the same two sums over the signal positions)
@@ -1473,13 +1497,13 @@ void gibbs_sweeps_kernel(const KernelParams p)
         }
 #pragma unroll
         for (int l = 0; l < L; ++l) {
-            double pvt = pv[0];
+            double pvt = pq[0];
 #pragma unroll
-            for (int k = 1; k < K; ++k) pvt = (xs_[l] == k) ? pv[k] : pvt;
+            for (int k = 1; k < K; ++k) pvt = (xq[l] == k) ? pq[k] : pvt;
             const double dl = y[l] - pvt;
-            const int t = tq0 + l;
+            const int t = tq + l;
             const bool issig = SIG && t >= sb && t < se;
-            const int xs = PADMARK ? (issig ? -1 : xs_[l]) : ((t < T && !issig) ? xs_[l] : -1);
+            const int xs = PADMARK ? (issig ? -1 : xq[l]) : ((t < T && !issig) ? xq[l] : -1);
 #pragma unroll
             for (int i = 0; i < K; ++i) {
                 const double dm = (xs == i) ? dl : 0.0;
@@ -1487,7 +1511,7 @@ void gibbs_sweeps_kernel(const KernelParams p)
                 d2[i] = fma(dm, dm, d2[i]);
             }
             if constexpr (SIG) {
-                const int xg = issig ? xs_[l] : -1;
+                const int xg = issig ? xq[l] : -1;
 #pragma unroll
                 for (int i = 0; i < K; ++i) {
                     const double dm = (xg == i) ? dl : 0.0;
@@ -1496,36 +1520,31 @@ void gibbs_sweeps_kernel(const KernelParams p)
                 }
             }
         }
-        if constexpr (SIG) {
-            static_assert(!SIG || K <= 4, "signal path: transposed reduce carries 2 x 4 slots");
-            double v8[8], o0, o1;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { v8[i] = i < K ? s1[i < K ? i : 0] : 0.0; v8[4 + i] = i < K ? s2[i < K ? i : 0] : 0.0; }
-            wave_sum8_transposed(v8, lane, o0, o1);
-            if ((lane & 0x3C) == 12) {
-                const int i0 = lane & 2, i1 = i0 + 1;
-                double* dst = (lane & 1) ? &sh.red_s2[dw][0] : &sh.red_s1[dw][0];
-                if (i0 < K) dst[i0] = o0;
-                if (i1 < K) dst[i1] = o1;
-            }
-        }
+        // transposed wave reduce of two rows of K <= 4 sums (a_, b_); lanes 12..15 hold the totals and store them as wave dq's
+        // (a macro: as a lambda or a function it moved registers in the base rows, profiles/r09)
+#define HMCG_REDUCE_ROWS(a_, b_, ra_, rb_)                                                                              \
+        do {                                                                                                            \
+            double v8[8], o0, o1;                                                                                       \
+            _Pragma("unroll") for (int i = 0; i < 4; ++i) { v8[i] = i < K ? a_[i < K ? i : 0] : 0.0; v8[4 + i] = i < K ? b_[i < K ? i : 0] : 0.0; } \
+            wave_sum8_transposed(v8, lane, o0, o1);                                                                     \
+            if ((lane & 0x3C) == 12) {                                                                                  \
+                const int i0 = lane & 2, i1 = i0 + 1;      /* state index of o0 / o1; lane&1 picks the row */           \
+                double* dst = (lane & 1) ? &rb_[dq][0] : &ra_[dq][0];                                                   \
+                if (i0 < K) dst[i0] = o0;                                                                               \
+                if (i1 < K) dst[i1] = o1;                                                                               \
+            }                                                                                                           \
+        } while (0)
+        static_assert(!SIG || K <= 4, "signal path: transposed reduce carries 2 x 4 slots");
+        if constexpr (SIG) HMCG_REDUCE_ROWS(s1, s2, sh.red_s1, sh.red_s2);
         if constexpr (K <= 4) {
-            double v8[8], o0, o1;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { v8[i] = i < K ? d1[i] : 0.0; v8[4 + i] = i < K ? d2[i] : 0.0; }
-            wave_sum8_transposed(v8, lane, o0, o1);
-            if ((lane & 0x3C) == 12) {                 // lanes 12..15 hold the totals
-                const int i0 = lane & 2, i1 = i0 + 1;  // state index of o0 / o1; lane&1 picks d1 or d2
-                double* dst = (lane & 1) ? &sh.red_d2[dw][0] : &sh.red_d1[dw][0];
-                if (i0 < K) dst[i0] = o0;
-                if (i1 < K) dst[i1] = o1;
-            }
+            HMCG_REDUCE_ROWS(d1, d2, sh.red_d1, sh.red_d2);
+#undef HMCG_REDUCE_ROWS
         } else {
 #pragma unroll
             for (int i = 0; i < K; ++i) { d1[i] = wave_sum(d1[i]); d2[i] = wave_sum(d2[i]); }
             if (lane == 0) {
 #pragma unroll
-                for (int i = 0; i < K; ++i) { sh.red_d1[dw][i] = d1[i]; sh.red_d2[dw][i] = d2[i]; }
+                for (int i = 0; i < K; ++i) { sh.red_d1[dq][i] = d1[i]; sh.red_d2[dq][i] = d2[i]; }
             }
         }
         }
@@ -1536,136 +1555,13 @@ void gibbs_sweeps_kernel(const KernelParams p)
             }
         }
         if constexpr (SUMS || !OWNER_DRAW) {
-            if (COUNTS ? tid == 0 : (dw == 0 && lane == 0)) {
+            if (COUNTS ? tid == 0 : (dq == 0 && lane == 0)) {
                 if constexpr (SUMS) {
 #pragma unroll
-                    for (int k = 0; k < K; ++k) sh.pivot[k] = pv[k];
+                    for (int k = 0; k < K; ++k) sh.pivot[k] = pq[k];
                 }
-                if constexpr (COUNTS) sh.x_end = x_end;
+                if constexpr (COUNTS && !OWNER_DRAW) sh.x_end = x_end;
             }
-        }
-    };
-    auto publish_stats = [&]() __attribute__((always_inline)) {
-        // ---- transition counts C_ij: per-thread PB-bit fields -> 16-bit fields -> one DPP integer sum per word
-        unsigned acc[NWORD];
-#pragma unroll
-        for (int wd = 0; wd < NWORD; ++wd) acc[wd] = 0;
-#pragma unroll
-        for (int l = 0; l < L; ++l) {
-            const int xn = (l + 1 < L) ? x[(l + 1 < L) ? l + 1 : l] : xnext;
-            const int code = PADCNT ? x[l] + K * xn : x[l] * K + xn;
-            const bool pv = (t0 + l + 1) < T;
-            if constexpr (PADCNT) {
-                // field j*K+i for the pair i -> j: a pair whose successor is padded (xn = K; a padded step is never
-                // followed by a real one) has code >= K*K, and all of those land in the spare field K*K
-                acc[0] += 1u << (PB * min(code, KK));
-            } else if constexpr (NWORD == 1) {
-                acc[0] += pv ? (1u << (PB * code)) : 0u;
-            } else {
-#pragma unroll
-                for (int wd = 0; wd < NWORD; ++wd) {
-                    const int rel = code - wd * FPW;
-                    acc[wd] += (pv && rel >= 0 && rel < FPW) ? (1u << (PB * rel)) : 0u;
-                }
-            }
-            if constexpr (SIG) {                       // M_i: signal steps in state i
-                const int t = t0 + l;
-                const bool sv = t >= sb && t < se;
-                const int c2 = KK + x[l];
-#pragma unroll
-                for (int wd = 0; wd < NWORD; ++wd) {
-                    const int rel = c2 - wd * FPW;
-                    acc[wd] += (sv && rel >= 0 && rel < FPW) ? (1u << (PB * rel)) : 0u;
-                }
-            }
-        }
-        unsigned pk[NPK];
-#pragma unroll
-        for (int d = 0; d < NPK; ++d) {
-            unsigned v = 0;
-#pragma unroll
-            for (int q = 0; q < Sh::FPK; ++q) {
-                const int e = Sh::FPK * d + q;
-                if (e < NF) v |= ((acc[e / FPW] >> (PB * (e % FPW))) & ((1u << PB) - 1u)) << (Sh::FW * q);
-            }
-            pk[d] = v;
-        }
-        wave_sum_words_lane63<NPK>(pk);
-        STAMP(19);
-        // ---- pivoted sums by state: d1_i = sum (y - pivot_i), d2_i = sum (y - pivot_i)^2 over the observation
-        // positions (and, on the signal path, the same two sums over the signal positions)
-        double d1[K], d2[K], s1[SIG ? K : 1], s2[SIG ? K : 1];
-#pragma unroll
-        for (int i = 0; i < K; ++i) { d1[i] = 0.0; d2[i] = 0.0; }
-        if constexpr (SIG) {
-#pragma unroll
-            for (int i = 0; i < K; ++i) { s1[i] = 0.0; s2[i] = 0.0; }
-        }
-#pragma unroll
-        for (int l = 0; l < L; ++l) {
-            double pvt = pivot[0];
-#pragma unroll
-            for (int k = 1; k < K; ++k) pvt = (x[l] == k) ? pivot[k] : pvt;
-            const double dl = y[l] - pvt;
-            const int t = t0 + l;
-            const bool issig = SIG && t >= sb && t < se;
-            const int xs = PADMARK ? (issig ? -1 : x[l]) : ((t < T && !issig) ? x[l] : -1);
-#pragma unroll
-            for (int i = 0; i < K; ++i) {
-                const double dm = (xs == i) ? dl : 0.0;
-                d1[i] += dm;
-                d2[i] = fma(dm, dm, d2[i]);
-            }
-            if constexpr (SIG) {
-                const int xg = issig ? x[l] : -1;
-#pragma unroll
-                for (int i = 0; i < K; ++i) {
-                    const double dm = (xg == i) ? dl : 0.0;
-                    s1[i] += dm;
-                    s2[i] = fma(dm, dm, s2[i]);
-                }
-            }
-        }
-        if constexpr (SIG) {
-            static_assert(!SIG || K <= 4, "signal path: transposed reduce carries 2 x 4 slots");
-            double v8[8], o0, o1;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { v8[i] = i < K ? s1[i < K ? i : 0] : 0.0; v8[4 + i] = i < K ? s2[i < K ? i : 0] : 0.0; }
-            wave_sum8_transposed(v8, lane, o0, o1);
-            if ((lane & 0x3C) == 12) {
-                const int i0 = lane & 2, i1 = i0 + 1;
-                double* dst = (lane & 1) ? &sh.red_s2[wave][0] : &sh.red_s1[wave][0];
-                if (i0 < K) dst[i0] = o0;
-                if (i1 < K) dst[i1] = o1;
-            }
-        }
-        if constexpr (K <= 4) {
-            double v8[8], o0, o1;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) { v8[i] = i < K ? d1[i] : 0.0; v8[4 + i] = i < K ? d2[i] : 0.0; }
-            wave_sum8_transposed(v8, lane, o0, o1);
-            if ((lane & 0x3C) == 12) {                 // lanes 12..15 hold the totals
-                const int i0 = lane & 2, i1 = i0 + 1;  // state index of o0 / o1; lane&1 picks d1 or d2
-                double* dst = (lane & 1) ? &sh.red_d2[wave][0] : &sh.red_d1[wave][0];
-                if (i0 < K) dst[i0] = o0;
-                if (i1 < K) dst[i1] = o1;
-            }
-        } else {
-#pragma unroll
-            for (int i = 0; i < K; ++i) { d1[i] = wave_sum(d1[i]); d2[i] = wave_sum(d2[i]); }
-            if (lane == 0) {
-#pragma unroll
-                for (int i = 0; i < K; ++i) { sh.red_d1[wave][i] = d1[i]; sh.red_d2[wave][i] = d2[i]; }
-            }
-        }
-        if (lane == 63) {
-#pragma unroll
-            for (int d = 0; d < NPK; ++d) sh.red_pk[wave][d] = pk[d];
-        }
-        if (tid == 0) {
-#pragma unroll
-            for (int k = 0; k < K; ++k) sh.pivot[k] = pivot[k];
-            if constexpr (!OWNER_DRAW) sh.x_end = x_end;
         }
     };
     auto publish_counts = [&]() __attribute__((always_inline)) { publish(std::true_type(), std::false_type(), x, pivot, t0, wave); };
@@ -1700,7 +1596,7 @@ void gibbs_sweeps_kernel(const KernelParams p)
     if constexpr (SIG) {
         if (p.sweep_begin % p.per_sample != 0) regen_y(p.sweep_begin / p.per_sample, false);   // resumed inside a sample
     }
-    if (!helper) publish_stats();
+    if (!helper) publish(std::true_type(), std::true_type(), x, pivot, t0, wave);
 
     // prologue: the first sweep's state-independent RNG parts
     if (p.sweep_begin < p.sweep_end && shadow_wave == 0) job_prep(p.sweep_begin);
@@ -1796,7 +1692,7 @@ void gibbs_sweeps_kernel(const KernelParams p)
                     STAMP(21);
                     SWEEP_BARRIER(2);                                      // Bb
                     STAMP(2);
-                    // The next sweep's RNG preparation (job_prep, statement for statement) as two stages with a barrier between
+                    // The next sweep's RNG preparation (job_prep's tasks) as two stages with a barrier between
                     // them: every lane's chain is cut in time, not by lanes -- Philox block, u53 and the log ahead of the cut;
                     // Box-Muller, the rho normalisation and the stores behind it -- and carries r[2], r[3], uraw and lg in
                     // registers.  Both stages of a sweep stand behind the same `more` condition, inside one loop iteration.
@@ -1809,20 +1705,8 @@ void gibbs_sweeps_kernel(const KernelParams p)
 #pragma unroll
                         for (int ps = 0; ps < NPASS; ++ps) {
                             const int task = ps * 64 + lane;
-                            const bool t_rho = task < K;
-                            const bool t_gx = !t_rho && task < K + 2 * NG;
-                            const bool t_z = !t_rho && !t_gx && task < 2 * K + 2 * NG;
-                            const bool t_gl = !t_rho && !t_gx && !t_z;
-                            const int gt = t_gx ? task - K : task - (2 * K + 2 * NG);
-                            const int role = gt >> 1, j = gt & 1;
-                            uint32_t site = SITE_RHO, elem = (uint32_t)task, idx = 0;
-                            if (t_gx || t_gl) {
-                                site = role < K ? SITE_SIG2 : SITE_A;
-                                elem = role < K ? (uint32_t)role : (uint32_t)(role - K);
-                                idx = 2u * (uint32_t)j + (t_gl ? 1u : 0u);
-                            } else if (t_z) {
-                                site = SITE_MU; elem = (uint32_t)(task - (K + 2 * NG));
-                            }
+                            HMCG_PREP_TASK_KIND(task);
+                            HMCG_PREP_TASK_BLOCK(task);
                             uint32_t r[4];
                             g.block(site, elem, idx, r);
                             puraw[ps] = u53(r[0], r[1]);
@@ -1836,24 +1720,9 @@ void gibbs_sweeps_kernel(const KernelParams p)
                         for (int ps = 0; ps < NPASS; ++ps) {
                             const int task = ps * 64 + lane;
                             const bool live = task < NTASK;
-                            const bool t_rho = task < K;
-                            const bool t_gx = !t_rho && task < K + 2 * NG;
-                            const bool t_z = !t_rho && !t_gx && task < 2 * K + 2 * NG;
-                            const bool t_gl = !t_rho && !t_gx && !t_z;
-                            const int gt = t_gx ? task - K : task - (2 * K + 2 * NG);
-                            const int role = gt >> 1, j = gt & 1;
+                            HMCG_PREP_TASK_KIND(task);
                             const double uraw = puraw[ps], lg = plg[ps];
-                            double val = lg;
-                            if (t_gx || t_z) val = sqrt_fast(-2.0 * lg) * cos2pi_fast(u53(pr2[ps], pr3[ps]));   // Box-Muller
-                            double rs = 0.0;
-#pragma unroll
-                            for (int i = 0; i < K; ++i) rs += -__shfl(lg, i, 64);
-                            if (live) {
-                                if (t_rho) rb.rho[task] = -lg * (1.0 / rs);
-                                else if (t_gx) rb.x[role][j] = val;
-                                else if (t_z) rb.z[task - (K + 2 * NG)] = val;
-                                else if (t_gl) { rb.lu[role][j] = val; rb.uu[role][j] = uraw; }
-                            }
+                            HMCG_PREP_TASK_FINISH(task, pr2[ps], pr3[ps]);
                         }
                     };
                     // The deal over the windows: the head of the preparation between Bb and Bc, where the
@@ -1902,7 +1771,7 @@ void gibbs_sweeps_kernel(const KernelParams p)
         ThetaBuf<K>& th = sh.th[par];
         if constexpr (SIG) {
             const int smp = sweep / p.per_sample;
-            if (sweep == smp * p.per_sample) { regen_y(smp, true); publish_stats(); }
+            if (sweep == smp * p.per_sample) { regen_y(smp, true); publish(std::true_type(), std::true_type(), x, pivot, t0, wave); }
         }
         SWEEP_BARRIER(0);                                                  // Ba: statistics (SPLIT: the counts) + rb[par] ready
         STAMP(0);
@@ -1916,12 +1785,14 @@ void gibbs_sweeps_kernel(const KernelParams p)
             const bool is_g = is_sig || is_A;
             const int role = is_sig ? lane : (is_A ? K + qi * K + qj : NG);
             double shape = 1.0, bpar = 1.0, Neff = 0.0, Ssum = 0.0, rnn = 0.0;
-            // transition count C_e of this lane's A role (e = role - K), summed over the waves' packed words
+            // adds field e_ of the packed counts, summed over the waves' words (a macro: as a lambda or a function the adds
+            // came out in another operand order, profiles/r09)
+#define HMCG_ADD_COUNT(acc_, e_) _Pragma("unroll") for (int ww = 0; ww < NW; ++ww) acc_ += (int)((sh.red_pk[ww][(e_) / Sh::FPK] >> (Sh::FW * ((e_) % Sh::FPK))) & ((1u << Sh::FW) - 1u))
+            // transition count C_e of this lane's A role (e = role - K)
             int cT = 0;
             {
                 const int e = is_A ? (PADCNT ? qj * K + qi : role - K) : 0;
-#pragma unroll
-                for (int ww = 0; ww < NW; ++ww) cT += (int)((sh.red_pk[ww][e / Sh::FPK] >> (Sh::FW * (e % Sh::FPK))) & ((1u << Sh::FW) - 1u));
+                HMCG_ADD_COUNT(cT, e);
                 cT = is_A ? cT : 0;
             }
             // N_i = sum_j C_ij + [X[T-1] == i]: quad sums of the A lanes, handed to the sig2 lanes as scalars
@@ -1940,7 +1811,7 @@ void gibbs_sweeps_kernel(const KernelParams p)
                 const int c = is_sig ? rowsum + ((sh.x_end == role) ? 1 : 0) : cT;
                 if (is_sig) {
                     if constexpr (SPLIT) {
-                        // what the count gives; what the sums add follows Ba2 (same statements as the block below)
+                        // what the count gives; what the sums add follows Ba2
                         Neff = (double)c;
                         shape = p.alpha + 0.5 * Neff;                                // :313
                         rnn = rcp_fast(Neff + p.nu);
@@ -1950,7 +1821,7 @@ void gibbs_sweeps_kernel(const KernelParams p)
                     for (int ww = 0; ww < NW; ++ww) { d1 += sh.red_d1[ww][role]; d2 += sh.red_d2[ww][role]; }
                     const double piv = sh.pivot[role];
                     const double beta = (sweep == 0) ? 1.0 : 2.0;                // quirk 2 (:179, :347)
-                    if constexpr (!SIG) {
+                    if constexpr (!SIG) {                                        // (twin: the SPLIT block behind Ba2 below; profiles/r09)
                         Neff = (double)c;
                         const double rn = c > 0 ? rcp_fast(Neff) : 0.0;
                         const double ybar = c > 0 ? piv + d1 * rn : 0.0;             // :259-265, :282-288
@@ -1963,11 +1834,7 @@ void gibbs_sweeps_kernel(const KernelParams p)
                     } else {
                         // observation set and signal set (src/Hmc.jl:254-314)
                         int Mi = 0;
-                        {
-                            const int e = KK + role;
-#pragma unroll
-                            for (int ww = 0; ww < NW; ++ww) Mi += (int)((sh.red_pk[ww][e / Sh::FPK] >> (Sh::FW * (e % Sh::FPK))) & ((1u << Sh::FW) - 1u));
-                        }
+                        HMCG_ADD_COUNT(Mi, KK + role);
                         const int Ni = c - Mi;
                         double g1 = 0.0, g2 = 0.0;
 #pragma unroll
@@ -1989,6 +1856,7 @@ void gibbs_sweeps_kernel(const KernelParams p)
                     shape = (double)(c + 1);                                     // :362-365
                 }
             }
+#undef HMCG_ADD_COUNT
             STAMP(17);
             double val = 1.0;
             if (is_g) {
@@ -2038,7 +1906,7 @@ void gibbs_sweeps_kernel(const KernelParams p)
                 STAMP(1);
                 SWEEP_BARRIER(1);                                              // Ba2: sums ready
                 STAMP(20);
-                if (is_sig) {
+                if (is_sig) {                                                    // (twin: the non-SPLIT !SIG block above; profiles/r09)
                     const int c = rowsum + ((sh.x_end == role) ? 1 : 0);
                     double d1 = 0.0, d2 = 0.0;
 #pragma unroll
@@ -2700,7 +2568,7 @@ void gibbs_sweeps_kernel(const KernelParams p)
             }
             STAMP(19);
         } else {
-            publish_stats();
+            publish(std::true_type(), std::true_type(), x, pivot, t0, wave);
             STAMP(13);
         }
     }
