@@ -23,17 +23,11 @@ ST_BAD_INVGAMMA, ST_EMIS_UNDERFLOW, ST_NONFINITE, ST_GAMMA_CAP, ST_BAD_T, ST_BAD
 ST_SKIPPED = ST_NONFINITE | ST_BAD_T | ST_BAD_RANGE      # the window was not computed at all
 
 HMCG_MAXTAIL = 256
-EXPORTS = ("hmcg_version", "hmcg_device_count", "hmcg_last_error", "hmcg_shutdown",
-           "hmcg_estimate_batch", "hmcg_estimate_batch_device", "hmcg_estimate_batch_multi",
-           "hmcg_save_results_csv", "hmcg_write_table_csv", "hmcg_format_float",
-           "hmcg_predictive_cdf", "hmcg_predictive_cdf_device", "hmcg_bias_moments", "hmcg_bias_moments_device",
-           "hmcg_mixture_moments", "hmcg_mixture_moments_device", "hmcg_chain_density", "hmcg_chain_density_device",
-           "hmcg_chain_autocorr", "hmcg_chain_autocorr_device")
 HMCG_MAXDEV = 16
 PRED_ROUND5 = 1
 HMCG_MAXGRID = 4096
 HMCG_PRED_MAXH = 1024           # largest horizon of the predictive CDFs
-PRED_SLAB = 1024                # draws per reduction slab (csrc/predictive_plan.hpp): the host entry uploads whole slabs
+PRED_SLAB = 1024                # draws per reduction slab (csrc/stat_plan.hpp): the host entry uploads whole slabs
 BIAS_ROUND5 = 1
 MIX_ROUND5 = 1
 MIX_STRIDE = 8                  # HMCG_MIX_STRIDE: doubles per (window, horizon) of the mixture-moment output
@@ -112,6 +106,17 @@ class MixMom(C.Structure):
                 ("horizons", C.c_int32 * HMCG_MAXH)]
 
 
+# The five draw statistics: the struct of a call, the stem of its two entries (hmcg_<stem>, hmcg_<stem>_device) and the ROUND5
+# bit of its flags.
+Stat = collections.namedtuple("Stat", "struct stem round5")
+STATS = {"predictive": Stat(Predictive, "predictive_cdf", PRED_ROUND5), "bias": Stat(Bias, "bias_moments", BIAS_ROUND5),
+         "mixmom": Stat(MixMom, "mixture_moments", MIX_ROUND5), "density": Stat(Density, "chain_density", DENS_ROUND5),
+         "autocorr": Stat(Autocorr, "chain_autocorr", ACF_ROUND5)}
+EXPORTS = ("hmcg_version", "hmcg_device_count", "hmcg_last_error", "hmcg_shutdown",
+           "hmcg_estimate_batch", "hmcg_estimate_batch_device", "hmcg_estimate_batch_multi",
+           "hmcg_save_results_csv", "hmcg_write_table_csv", "hmcg_format_float") + tuple(
+               "hmcg_" + s.stem + tail for s in STATS.values() for tail in ("", "_device"))
+
 _LIB = None
 
 
@@ -160,26 +165,9 @@ def load():
                             "this package has no CPU fallback" % SO_PATH)
         _share_torch_hip_runtime()
         L = C.CDLL(SO_PATH)
-        L.hmcg_version.restype = C.c_int
-        L.hmcg_device_count.restype = C.c_int
-        L.hmcg_last_error.restype = C.c_char_p
-        L.hmcg_shutdown.restype = None
-        L.hmcg_estimate_batch.restype = C.c_int
-        L.hmcg_estimate_batch_device.restype = C.c_int
-        L.hmcg_estimate_batch_multi.restype = C.c_int
-        L.hmcg_save_results_csv.restype = C.c_int
-        L.hmcg_write_table_csv.restype = C.c_int
-        L.hmcg_format_float.restype = C.c_int
-        L.hmcg_predictive_cdf.restype = C.c_int
-        L.hmcg_predictive_cdf_device.restype = C.c_int
-        L.hmcg_bias_moments.restype = C.c_int
-        L.hmcg_bias_moments_device.restype = C.c_int
-        L.hmcg_mixture_moments.restype = C.c_int
-        L.hmcg_mixture_moments_device.restype = C.c_int
-        L.hmcg_chain_density.restype = C.c_int
-        L.hmcg_chain_density_device.restype = C.c_int
-        L.hmcg_chain_autocorr.restype = C.c_int
-        L.hmcg_chain_autocorr_device.restype = C.c_int
+        for name in EXPORTS:
+            getattr(L, name).restype = C.c_int
+        L.hmcg_last_error.restype, L.hmcg_shutdown.restype = C.c_char_p, None
         _LIB = L
     return _LIB
 
@@ -427,16 +415,56 @@ def estimate_batch_device(cfg, dY, dT, dyreal, dmu, dsig2, dA, dpi_end, dfcast, 
     return _device_call(load().hmcg_estimate_batch_device, cfg, pointers, stream, timed)
 
 
+def _make_stat(name, W, cols, nd, nd_ld, device, round5, horizons=None):
+    """What the structs of STATS share: struct_size, W, K or C (`cols`), device, nd, nd_ld and the ROUND5 flag; with `horizons`
+    also n_h and the list (more than HMCG_MAXH raise here)."""
+    if horizons is not None and len(horizons) > HMCG_MAXH:
+        raise ValueError("at most %d horizons" % HMCG_MAXH)
+    st = STATS[name]
+    p = st.struct()
+    p.struct_size = C.sizeof(st.struct)
+    p.W, p.device, p.nd, p.nd_ld = int(W), int(device), int(nd), int(nd_ld)
+    setattr(p, "K" if hasattr(p, "K") else "C", int(cols))
+    p.flags = st.round5 if round5 else 0
+    if horizons is not None:
+        p.n_h = len(horizons)
+        for i, h in enumerate(horizons):
+            p.horizons[i] = int(h)
+    return p
+
+
+def _state_draws(A, **cols):
+    """The per-state draw arrays of a host entry, `cols` by name with mu first, each (W, K, nd), and A (W, K, K, nd) or None, as
+    contiguous float64: (arrays in the order given, A, (W, K, nd))."""
+    arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in cols.values()]
+    W, K, nd = arrs[0].shape
+    if any(a.shape != arrs[0].shape for a in arrs):
+        names = list(cols)
+        raise ValueError("%s and %s must share the shape (W, K, nd)" % (", ".join(names[:-1]), names[-1]))
+    if A is not None:
+        A = np.ascontiguousarray(A, dtype=np.float64)
+        if A.shape != (W, K, K, nd):
+            raise ValueError("A must have the shape (W, K, K, nd)")
+    return arrs, A, (W, K, nd)
+
+
+def _column_draws(x, nd):
+    """ONE draw array of a host entry with the draw index last, every axis between the first and the last flattened into
+    columns, as contiguous float64: (x, W, columns, nd -- None: all --, leading dimension)."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    W, ld = x.shape[0], x.shape[-1]
+    return x, W, int(np.prod(x.shape[1:-1], dtype=np.int64)), ld if nd is None else int(nd), ld
+
+
+def _tm(timing):
+    """The hmcg_timing argument of a host entry: a Timing to fill, or None."""
+    return C.byref(timing) if timing is not None else None
+
+
 def make_predictive(W, K, nd, nd_ld, G, horizons=(0,), device=0, round5=True):
     """hmcg_predictive of a call.  More than HMCG_MAXH horizons raise here; every other rule is the library's (HMCG_E_BADARG)."""
-    if len(horizons) > HMCG_MAXH:
-        raise ValueError("at most %d horizons" % HMCG_MAXH)
-    p = Predictive()
-    p.struct_size = C.sizeof(Predictive)
-    p.W, p.K, p.device, p.nd, p.nd_ld, p.G, p.n_h = int(W), int(K), int(device), int(nd), int(nd_ld), int(G), len(horizons)
-    for i, h in enumerate(horizons):
-        p.horizons[i] = int(h)
-    p.flags = PRED_ROUND5 if round5 else 0
+    p = _make_stat("predictive", W, K, nd, nd_ld, device, round5, horizons)
+    p.G = int(G)
     return p
 
 
@@ -446,21 +474,12 @@ def predictive_cdf_host(mu, sig2, pi_end, A, grid, horizons=(0,), device=0, roun
     (W, n_h, G): per window and horizon the mean over the draws of sum_k omega[k] Phi((grid[g] - mu[k]) / sqrt(sig2[k])),
     omega = pi_end A^h (calc_cdfs.jl:39-41 at h = 0).  round5 (default): every input is first rounded to 5 digits, as the cells
     of the per-draw CSV files are.  timing: a Timing to fill."""
-    mu = np.ascontiguousarray(mu, dtype=np.float64)
-    W, K, nd = mu.shape
-    sig2 = np.ascontiguousarray(sig2, dtype=np.float64)
-    pi_end = np.ascontiguousarray(pi_end, dtype=np.float64)
-    if sig2.shape != mu.shape or pi_end.shape != mu.shape:
-        raise ValueError("mu, sig2 and pi_end must share the shape (W, K, nd)")
-    if A is not None:
-        A = np.ascontiguousarray(A, dtype=np.float64)
-        if A.shape != (W, K, K, nd):
-            raise ValueError("A must have the shape (W, K, K, nd)")
+    (mu, sig2, pi_end), A, (W, K, nd) = _state_draws(A, mu=mu, sig2=sig2, pi_end=pi_end)
     grid = np.ascontiguousarray(grid, dtype=np.float64).reshape(-1)
     p = make_predictive(W, K, nd, nd, grid.size, horizons, device, round5)
     cdf = np.zeros((W, len(horizons), grid.size))
     _check(load().hmcg_predictive_cdf(C.byref(p), _np_ptr(mu), _np_ptr(sig2), _np_ptr(pi_end), _np_ptr(A), _np_ptr(grid),
-                                      _np_ptr(cdf), C.byref(timing) if timing is not None else None))
+                                      _np_ptr(cdf), _tm(timing)))
     return cdf
 
 
@@ -473,10 +492,8 @@ def predictive_cdf_device(pred, dmu, dsig2, dpi_end, dA, dgrid, dcdf, stream=Non
 
 def make_bias(W, K, nd, nd_ld, horizon=12, H=0, device=0, round5=True):
     """hmcg_bias of a call; every rule is the library's (HMCG_E_BADARG).  H: fcast has 2H columns per window (0 without fcast)."""
-    p = Bias()
-    p.struct_size = C.sizeof(Bias)
-    p.W, p.K, p.device, p.nd, p.nd_ld, p.horizon, p.H = int(W), int(K), int(device), int(nd), int(nd_ld), int(horizon), int(H)
-    p.flags = BIAS_ROUND5 if round5 else 0
+    p = _make_stat("bias", W, K, nd, nd_ld, device, round5)
+    p.horizon, p.H = int(horizon), int(H)
     return p
 
 
@@ -496,15 +513,7 @@ def bias_moments_host(mu, pi_end, A, fcast=None, horizon=12, device=0, round5=Tr
     column orders (bias_calcs.jl:49-51), totalbias = the mean of fcast[:, 1] (NaN without fcast), the mean and the covariance
     (divisor nd - 1) of [pi_end A^horizon | mu] over the draws.  round5 (default): every input is first rounded to 5 digits,
     as the cells of the per-draw CSV files are.  timing: a Timing to fill."""
-    mu = np.ascontiguousarray(mu, dtype=np.float64)
-    W, K, nd = mu.shape
-    pi_end = np.ascontiguousarray(pi_end, dtype=np.float64)
-    if pi_end.shape != mu.shape:
-        raise ValueError("mu and pi_end must share the shape (W, K, nd)")
-    if A is not None:
-        A = np.ascontiguousarray(A, dtype=np.float64)
-        if A.shape != (W, K, K, nd):
-            raise ValueError("A must have the shape (W, K, K, nd)")
+    (mu, pi_end), A, (W, K, nd) = _state_draws(A, mu=mu, pi_end=pi_end)
     H = 0
     if fcast is not None:
         fcast = np.ascontiguousarray(fcast, dtype=np.float64)
@@ -513,8 +522,7 @@ def bias_moments_host(mu, pi_end, A, fcast=None, horizon=12, device=0, round5=Tr
         H = fcast.shape[1] // 2
     p = make_bias(W, K, nd, nd, horizon, H, device, round5)
     out = np.zeros((W, bias_stride(K)))
-    _check(load().hmcg_bias_moments(C.byref(p), _np_ptr(mu), _np_ptr(pi_end), _np_ptr(A), _np_ptr(fcast), _np_ptr(out),
-                                    C.byref(timing) if timing is not None else None))
+    _check(load().hmcg_bias_moments(C.byref(p), _np_ptr(mu), _np_ptr(pi_end), _np_ptr(A), _np_ptr(fcast), _np_ptr(out), _tm(timing)))
     return out
 
 
@@ -527,15 +535,7 @@ def bias_moments_device(bias, dmu, dpi_end, dA, dfcast, dout, stream=None, timed
 
 def make_mixmom(W, K, nd, nd_ld, horizons=(0,), device=0, round5=True):
     """hmcg_mixmom of a call.  More than HMCG_MAXH horizons raise here; every other rule is the library's (HMCG_E_BADARG)."""
-    if len(horizons) > HMCG_MAXH:
-        raise ValueError("at most %d horizons" % HMCG_MAXH)
-    p = MixMom()
-    p.struct_size = C.sizeof(MixMom)
-    p.W, p.K, p.device, p.nd, p.nd_ld, p.n_h = int(W), int(K), int(device), int(nd), int(nd_ld), len(horizons)
-    for i, h in enumerate(horizons):
-        p.horizons[i] = int(h)
-    p.flags = MIX_ROUND5 if round5 else 0
-    return p
+    return _make_stat("mixmom", W, K, nd, nd_ld, device, round5, horizons)
 
 
 def unpack_mixture_moments(out):
@@ -553,20 +553,10 @@ def mixture_moments_host(mu, sig2, pi_end, A, horizons=(0,), device=0, round5=Tr
     sum_k omega_k N(mu_k, sig2_k), omega = pi_end A^h, pooled over the draws in closed form (skewness.jl and alt_forecasts.jl
     asked of the draws), and its within- / between-draw split.  round5 (default): every input is first rounded to 5 digits, as
     the cells of the per-draw CSV files are.  timing: a Timing to fill."""
-    mu = np.ascontiguousarray(mu, dtype=np.float64)
-    W, K, nd = mu.shape
-    sig2 = np.ascontiguousarray(sig2, dtype=np.float64)
-    pi_end = np.ascontiguousarray(pi_end, dtype=np.float64)
-    if sig2.shape != mu.shape or pi_end.shape != mu.shape:
-        raise ValueError("mu, sig2 and pi_end must share the shape (W, K, nd)")
-    if A is not None:
-        A = np.ascontiguousarray(A, dtype=np.float64)
-        if A.shape != (W, K, K, nd):
-            raise ValueError("A must have the shape (W, K, K, nd)")
+    (mu, sig2, pi_end), A, (W, K, nd) = _state_draws(A, mu=mu, sig2=sig2, pi_end=pi_end)
     p = make_mixmom(W, K, nd, nd, horizons, device, round5)
     out = np.zeros((W, len(horizons), MIX_STRIDE))
-    _check(load().hmcg_mixture_moments(C.byref(p), _np_ptr(mu), _np_ptr(sig2), _np_ptr(pi_end), _np_ptr(A), _np_ptr(out),
-                                       C.byref(timing) if timing is not None else None))
+    _check(load().hmcg_mixture_moments(C.byref(p), _np_ptr(mu), _np_ptr(sig2), _np_ptr(pi_end), _np_ptr(A), _np_ptr(out), _tm(timing)))
     return out
 
 
@@ -584,13 +574,11 @@ def make_density(W, Cn, nd, nd_ld, cuts=None, bins=64, trace=(0, 1), device=0, r
     cuts = (int(nd),) if cuts is None else tuple(int(c) for c in cuts)
     if len(cuts) > HMCG_MAXH:
         raise ValueError("at most %d cuts" % HMCG_MAXH)
-    p = Density()
-    p.struct_size = C.sizeof(Density)
-    p.W, p.C, p.device, p.nd, p.nd_ld, p.B, p.n_cuts = int(W), int(Cn), int(device), int(nd), int(nd_ld), int(bins), len(cuts)
+    p = _make_stat("density", W, Cn, nd, nd_ld, device, round5)
+    p.B, p.n_cuts = int(bins), len(cuts)
     for i, c in enumerate(cuts):
         p.cuts[i] = c
     p.trace_len, p.trace_stride = int(trace[0]), int(trace[1])
-    p.flags = DENS_ROUND5 if round5 else 0
     return p
 
 
@@ -614,10 +602,7 @@ def chain_density(x, cuts=None, bins=64, lo_hi=None, trace=(0, 1), nd=None, devi
     the running mean at (i + 1) * trace[1] draws, i < trace[0] (plots/mcplots.jl's plotchain and plotchainmean up to the
     drawing).  round5 (default): every value is first rounded to 5 digits, as the cells of the per-draw CSV files are.
     Returns the dict of unpack_chain_density, the column axis flattened.  timing: a Timing to fill."""
-    x = np.ascontiguousarray(x, dtype=np.float64)
-    W, ld = x.shape[0], x.shape[-1]
-    Cn = int(np.prod(x.shape[1:-1], dtype=np.int64))
-    nd = ld if nd is None else int(nd)
+    x, W, Cn, nd, ld = _column_draws(x, nd)
     p = make_density(W, Cn, nd, ld, cuts, bins, trace, device, round5)
     if lo_hi is not None:
         lo_hi = np.ascontiguousarray(lo_hi, dtype=np.float64)
@@ -629,7 +614,7 @@ def chain_density(x, cuts=None, bins=64, lo_hi=None, trace=(0, 1), nd=None, devi
     stats = np.zeros((W, Cn, nc, 2))
     tr = np.zeros((W, Cn, tl))
     _check(load().hmcg_chain_density(C.byref(p), _np_ptr(x), _np_ptr(lo_hi), _np_ptr(rng), _np_ptr(counts), _np_ptr(stats),
-                                     _np_ptr(tr) if tl else None, C.byref(timing) if timing is not None else None))
+                                     _np_ptr(tr) if tl else None, _tm(timing)))
     return unpack_chain_density(rng, counts, stats, tr)
 
 
@@ -643,10 +628,8 @@ def chain_density_device(dens, dx, dlo_hi, drange, dcounts, dstats, dtrace, stre
 def make_autocorr(W, Cn, nd, nd_ld, lags=255, device=0, round5=True):
     """hmcg_autocorr of a call over a draw array of Cn columns per window; lags = the largest lag L.  Every rule is the
     library's (HMCG_E_BADARG)."""
-    p = Autocorr()
-    p.struct_size = C.sizeof(Autocorr)
-    p.W, p.C, p.device, p.nd, p.nd_ld, p.L = int(W), int(Cn), int(device), int(nd), int(nd_ld), int(lags)
-    p.flags = ACF_ROUND5 if round5 else 0
+    p = _make_stat("autocorr", W, Cn, nd, nd_ld, device, round5)
+    p.L = int(lags)
     return p
 
 
@@ -671,15 +654,11 @@ def chain_autocorr(x, lags=255, nd=None, device=0, round5=True, timing=None):
     first nd draws (default: all).  Per window and column: the autocovariances at lags 0..lags and the convergence diagnostics
     of unpack_chain_autocorr.  round5 (default): every value is first rounded to 5 digits, as the cells of the per-draw CSV
     files are.  Returns the dict of unpack_chain_autocorr, the column axis flattened.  timing: a Timing to fill."""
-    x = np.ascontiguousarray(x, dtype=np.float64)
-    W, ld = x.shape[0], x.shape[-1]
-    Cn = int(np.prod(x.shape[1:-1], dtype=np.int64))
-    nd = ld if nd is None else int(nd)
+    x, W, Cn, nd, ld = _column_draws(x, nd)
     p = make_autocorr(W, Cn, nd, ld, lags, device, round5)
     acov = np.zeros((W, Cn, max(int(lags), 0) + 1))
     diag = np.zeros((W, Cn, ACF_STRIDE))
-    _check(load().hmcg_chain_autocorr(C.byref(p), _np_ptr(x), _np_ptr(acov), _np_ptr(diag),
-                                      C.byref(timing) if timing is not None else None))
+    _check(load().hmcg_chain_autocorr(C.byref(p), _np_ptr(x), _np_ptr(acov), _np_ptr(diag), _tm(timing)))
     return unpack_chain_autocorr(acov, diag)
 
 

@@ -23,7 +23,7 @@
 #include <stdint.h>
 
 #include "autocorr.hpp"
-#include "round5.hpp"
+#include "stat_device.hpp"
 
 namespace hmcg {
 
@@ -80,7 +80,7 @@ __global__ __launch_bounds__(ACF_NT) void autocorr_accumulate_kernel(const AcfPa
     double pvt;
     if (first) {
         const double f = col[p.pre];                     // pre == 0 here
-        pvt = p.round5 ? round5(f) : f;
+        pvt = stat_in(f, p.round5);
     } else pvt = *w_piv;
     const long long nslab = (p.n + PRED_SLAB - 1) / PRED_SLAB;
     const long long dend = p.d_origin + p.n;             // one past this launch's last draw
@@ -115,7 +115,7 @@ __global__ __launch_bounds__(ACF_NT) void autocorr_accumulate_kernel(const AcfPa
             const int i = tid + ACF_NT * k;
             const long long d = sd0 - pl.lags_r + i;
             if (i < nstage) {
-                const double xr = p.round5 ? round5(v[k]) : v[k];
+                const double xr = stat_in(v[k], p.round5);
                 st[ac_pos(i)] = (d >= lo && d < dend) ? xr - pvt : 0.0;
             }
         }
@@ -175,8 +175,7 @@ __global__ __launch_bounds__(ACF_NT) void autocorr_accumulate_kernel(const AcfPa
         }
 #pragma unroll
         for (int e = 0; e < ACF_SUMS; ++e) {
-#pragma unroll
-            for (int m = 32; m >= 1; m >>= 1) sm[e] += __shfl_xor(sm[e], m, 64);
+            HMCG_WAVE_SUM(sm[e]);
             if (lane == 0) sred[wv][e] = sm[e];
         }
 
@@ -265,7 +264,7 @@ __global__ __launch_bounds__(ACF_NT) void autocorr_finalize_kernel(const AcfPara
     }
     __syncthreads();
     if (tid != 0) return;
-    const double nan = __longlong_as_double(0x7ff8000000000000ll);
+    const double nan = stat_nan();
     const double sq = S1 * S1;
     const double corr = sq / n;
     const double dv = S2 - corr;
@@ -335,8 +334,7 @@ static bool acf_params(const AcfArgs& a, hmcg::AcfParams& p)
 {
     if (a.W < 1 || a.C < 1 || a.C > HMCG_MAXK * HMCG_MAXK || (long long)a.W * a.C > 0x7fffffffLL) return false;
     if (a.L < 0 || a.L > HMCG_ACF_MAXLAG || a.nd < 1 || (long long)a.L > a.nd - 1) return false;
-    if (a.n < 1 || a.d_origin < 0 || a.d_origin % PRED_SLAB != 0 || a.d_origin + a.n > a.nd) return false;
-    if (a.d_origin + a.n < a.nd && a.n % PRED_SLAB != 0) return false;
+    if (!chunk_origin_ok(a.d_origin, a.n, a.nd)) return false;
     if (a.pre != acf_pre(a.d_origin, a.L) || a.ld < a.pre + a.n) return false;
     if (!a.x || !a.work || !a.acov || !a.diag) return false;
     p = hmcg::AcfParams{};

@@ -12,7 +12,7 @@
 #include <cstdio>
 
 #include "../../include/hmcg.h"
-#include "predictive_plan.hpp"
+#include "stat_plan.hpp"
 
 #ifdef __HIPCC__
 #define HMCG_ACF_HD __host__ __device__ __forceinline__
@@ -24,7 +24,6 @@ namespace hmcg_host {
 
 constexpr int ACF_NT = 256;                  // threads per block
 constexpr int ACF_J = 8;                     // adjacent lags per thread = draws per register tile
-constexpr long long ACF_MAX_ND = 1LL << 53;  // n and n - l are fp64 factors and must be exact
 constexpr int ACF_SUMS = 6;                  // S1, S2 of [0, h), [h, n - h), [n - h, n)
 static_assert(PRED_SLAB % ACF_NT == 0 && PRED_SLAB % ACF_J == 0, "a slab is a whole number of tiles");
 static_assert(HMCG_ACF_MAXLAG <= PRED_SLAB, "the halo of a slab is at most one slab");
@@ -56,22 +55,13 @@ HMCG_ACF_HD long long acf_pre(long long d0, int L) { return d0 < (long long)L ? 
 // Argument rules shared by both entries; 0 or HMCG_E_BADARG with the reason in msg.  No pointer is followed.
 inline int check_autocorr(const hmcg_autocorr* p, const double* x, const double* acov, const double* diag, char* msg, size_t nmsg)
 {
-    if (!p) { snprintf(msg, nmsg, "hmcg_autocorr is NULL"); return HMCG_E_BADARG; }
-    if (p->struct_size != (int32_t)sizeof(hmcg_autocorr)) {
-        snprintf(msg, nmsg, "hmcg_autocorr.struct_size %d != %d", p->struct_size, (int)sizeof(hmcg_autocorr));
+    // n and n - l are fp64 factors
+    if (bad_struct(p, "hmcg_autocorr", msg, nmsg) || bad_W(p->W, msg, nmsg) || bad_C(p->C, msg, nmsg) || bad_nd(p->nd, msg, nmsg) ||
+        bad_exact_nd(p->nd, msg, nmsg) || bad_nd_ld(p->nd_ld, p->nd, msg, nmsg))
         return HMCG_E_BADARG;
-    }
-    if (p->W < 1) { snprintf(msg, nmsg, "W = %d: at least one window", p->W); return HMCG_E_BADARG; }
-    if (p->C < 1 || p->C > HMCG_MAXK * HMCG_MAXK) { snprintf(msg, nmsg, "C = %d columns outside 1..%d", p->C, HMCG_MAXK * HMCG_MAXK); return HMCG_E_BADARG; }
-    if (p->nd < 1) { snprintf(msg, nmsg, "nd = %lld: at least one draw", (long long)p->nd); return HMCG_E_BADARG; }
-    if (p->nd > ACF_MAX_ND) { snprintf(msg, nmsg, "nd = %lld exceeds 2^53, the largest exact divisor", (long long)p->nd); return HMCG_E_BADARG; }
-    if (p->nd_ld < p->nd) { snprintf(msg, nmsg, "nd_ld = %lld < nd = %lld", (long long)p->nd_ld, (long long)p->nd); return HMCG_E_BADARG; }
     if (p->L < 0 || p->L > HMCG_ACF_MAXLAG) { snprintf(msg, nmsg, "L = %d lags outside 0..%d", p->L, HMCG_ACF_MAXLAG); return HMCG_E_BADARG; }
     if ((long long)p->L > p->nd - 1) { snprintf(msg, nmsg, "L = %d exceeds nd - 1 = %lld", p->L, (long long)p->nd - 1); return HMCG_E_BADARG; }
-    if ((long long)p->W * p->C > 2147483647LL) {         // both kernels run one block per (window, column)
-        snprintf(msg, nmsg, "W * C exceeds one launch (2^31 - 1 blocks)");
-        return HMCG_E_BADARG;
-    }
+    if (bad_WC(p->W, p->C, msg, nmsg)) return HMCG_E_BADARG;        // both kernels
     if (!x || !acov || !diag) { snprintf(msg, nmsg, "x, acov and diag are required"); return HMCG_E_BADARG; }
     return 0;
 }

@@ -16,8 +16,8 @@
 // Shape: one block of 256 threads per (window, slab of PRED_SLAB draws); a slab is walked in tiles of 256 draws.
 //   phase A  thread t takes draw t of the tile: pi_end, A, mu and the forecast-error cell are read coalesced along d (every
 //            column one 2 KB line of consecutive doubles per tile), rounded as CSV cells under round5; omega = pi_end A^h by h
-//            row-vector x matrix products in registers, k ascending in every dot product -- the expression of predictive.hip,
-//            so both features give the same omega bits; v - p = [omega | mu | fe] - pivot goes to LDS, one row of 256 per column.
+//            row-vector x matrix products in registers (HMCG_OMEGA_STEP of stat_device.hpp, the one expression of all three
+//            features that use omega); v - p = [omega | mu | fe] - pivot goes to LDS, one row of 256 per column.
 //   phase B  the items (2K (2K + 1) / 2 pair sums, 2K + 1 plain sums) are dealt round-robin to the block's four waves, so a
 //            lane holds at most 39 fp64 accumulators at K = 8 instead of 153; lane l of every wave takes draws l, l + 64, l + 128,
 //            l + 192 of the tile in that order: one LDS read per column (conflict-free, consecutive lanes on consecutive
@@ -39,7 +39,7 @@
 #include <utility>
 
 #include "bias.hpp"
-#include "round5.hpp"
+#include "stat_device.hpp"
 
 namespace hmcg {
 
@@ -77,8 +77,6 @@ struct BiasParams {
     long long nslab, slab0, nslab_total;     // slabs of this launch; its first slab and the slab count of the whole run
     int horizon, round5;
 };
-
-__device__ __forceinline__ double bias_in(double x, int r5) { return r5 ? round5(x) : x; }
 
 // Item E of a draw whose columns are x[]: indices are constant expressions, so x[] and the accumulators stay in registers.
 template <int K, int E>
@@ -121,10 +119,7 @@ __global__ __launch_bounds__(BIAS_NT) void bias_moments_kernel(const BiasParams 
     __shared__ double V[NC * BIAS_NT];                  // [column][draw of the tile]: v - p
     __shared__ double P[NC];                            // the pivot
     const int tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
-    const int w = (int)((long long)blockIdx.x / p.nslab);
-    const long long s = (long long)blockIdx.x - (long long)w * p.nslab;
-    const long long dbeg = s * hmcg_host::PRED_SLAB;
-    const long long dend = dbeg + hmcg_host::PRED_SLAB < p.nd ? dbeg + hmcg_host::PRED_SLAB : p.nd;
+    HMCG_STAT_SLAB(w, s, dbeg, dend, p.nslab, p.nd);
     const int ntile = (int)((dend - dbeg + BIAS_NT - 1) / BIAS_NT);
     const double* mu = p.mu + (size_t)w * K * p.nd_ld;
     const double* pie = p.pi_end + (size_t)w * K * p.nd_ld;
@@ -141,41 +136,27 @@ __global__ __launch_bounds__(BIAS_NT) void bias_moments_kernel(const BiasParams 
     // it = -1: the pivot pass (thread 0 on draw 0), through the same code as every tile
 #pragma unroll 1
     for (int it = own_pivot ? -1 : 0; it < ntile; ++it) {
-        // wave-uniform 64-bit base + 32-bit lane offset: every column is one scalar-base load, no 64-bit address per column
-        const size_t base = it < 0 ? (size_t)0 : (size_t)dbeg;
-        const unsigned o = it < 0 ? 0u : (unsigned)(it * BIAS_NT + tid);
-        const bool valid = it < 0 ? tid == 0 : (long long)base + o < dend;
+        const auto [base, o, valid] = stat_tile(it, BIAS_NT, tid, dbeg, dend);
         double v[NC];
 #pragma unroll
         for (int c = 0; c < NC; ++c) v[c] = 0.0;
         if (valid) {
             double wv[K];
 #pragma unroll
-            for (int k = 0; k < K; ++k) wv[k] = bias_in((pie + (size_t)k * p.nd_ld + base)[o], p.round5);
+            for (int k = 0; k < K; ++k) wv[k] = stat_in((pie + (size_t)k * p.nd_ld + base)[o], p.round5);
             if (At) {
                 double a[K * K];
 #pragma unroll
-                for (int c = 0; c < K * K; ++c) a[c] = bias_in((At + (size_t)c * p.nd_ld + base)[o], p.round5);
+                for (int c = 0; c < K * K; ++c) a[c] = stat_in((At + (size_t)c * p.nd_ld + base)[o], p.round5);
 #pragma unroll 1
-                for (int step = 0; step < p.horizon; ++step) {
-                    double nw[K];
-#pragma unroll
-                    for (int c = 0; c < K; ++c) {
-                        double t = wv[0] * a[K * c];
-#pragma unroll
-                        for (int i = 1; i < K; ++i) t += wv[i] * a[i + K * c];
-                        nw[c] = t;
-                    }
-#pragma unroll
-                    for (int c = 0; c < K; ++c) wv[c] = nw[c];
-                }
+                for (int step = 0; step < p.horizon; ++step) HMCG_OMEGA_STEP(K, wv, a, 1);
             }
 #pragma unroll
             for (int k = 0; k < K; ++k) {
                 v[k] = wv[k];
-                v[K + k] = bias_in((mu + (size_t)k * p.nd_ld + base)[o], p.round5);
+                v[K + k] = stat_in((mu + (size_t)k * p.nd_ld + base)[o], p.round5);
             }
-            if (fc) v[NV] = bias_in((fc + base)[o], p.round5);
+            if (fc) v[NV] = stat_in((fc + base)[o], p.round5);
         }
         if (it < 0) {
             if (tid == 0) {
@@ -197,12 +178,11 @@ __global__ __launch_bounds__(BIAS_NT) void bias_moments_kernel(const BiasParams 
         __syncthreads();
     }
     if (own_pivot && s == 0 && tid < NC) p.piv[(size_t)w * NC + tid] = P[tid];
-    double* row = p.part + ((size_t)w * (size_t)p.nslab_total + (size_t)(p.slab0 + s)) * (size_t)ITEMS;
+    double* row = p.part + HMCG_STAT_ROW(w, p.nslab_total, p.slab0 + s, ITEMS);
 #pragma unroll
     for (int i = 0; i < PPW; ++i) {
         double t = acc[i];
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) t += __shfl_xor(t, m, 64);
+        HMCG_WAVE_SUM(t);
         const int e = q + BIAS_NW * i;
         if (lane == 0 && e < ITEMS) row[e] = t;
     }
@@ -220,8 +200,7 @@ __global__ __launch_bounds__(BIAS_FIN_NT) void bias_finalize_kernel(const double
     const int w = blockIdx.x, tid = threadIdx.x;
     for (int e = tid; e < ITEMS; e += BIAS_FIN_NT) {
         const double* col = part + (size_t)w * (size_t)nslab * (size_t)ITEMS + (size_t)e;
-        double sum = 0.0;
-        for (long long sl = 0; sl < nslab; ++sl) sum += col[(size_t)sl * (size_t)ITEMS];
+        HMCG_SLAB_SUM(sum, col, nslab, ITEMS);
         T[e] = sum;
     }
     __syncthreads();
@@ -246,7 +225,7 @@ __global__ __launch_bounds__(BIAS_FIN_NT) void bias_finalize_kernel(const double
         double u = 0.0;
         for (int b = 0; b < NV; ++b) u += R[b] * M[(b + K) % NV];
         o[0] = u;
-        o[1] = with_fc ? M[NV] : __builtin_nan("");
+        o[1] = with_fc ? M[NV] : stat_nan();
     }
 }
 
@@ -269,13 +248,10 @@ hipError_t launch_bias(const BiasArgs& a, hipStream_t stream)
     p.nd = a.nd; p.nd_ld = a.nd_ld; p.nslab = pred_slabs(a.nd); p.slab0 = a.slab0; p.nslab_total = a.nslab_total;
     p.horizon = a.horizon; p.round5 = a.round5 ? 1 : 0;
     if (a.horizon > 0 && !a.A) return hipErrorInvalidValue;
-    if (a.nd_ld < a.nd || p.slab0 < 0 || p.slab0 + p.nslab > p.nslab_total || (long long)a.W * p.nslab > 0x7fffffffLL) return hipErrorInvalidValue;
+    if (!slab_range_ok(a.W, a.nd, a.nd_ld, a.slab0, a.nslab_total)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((long long)a.W * p.nslab)), block(hmcg::BIAS_NT);
-#define HMCG_BIAS(K_) case K_: hipLaunchKernelGGL(hmcg::bias_moments_kernel<K_>, grid, block, 0, stream, p); break
-    switch (a.K) {
-        HMCG_BIAS(2); HMCG_BIAS(3); HMCG_BIAS(4); HMCG_BIAS(5); HMCG_BIAS(6); HMCG_BIAS(7); HMCG_BIAS(8);
-        default: return hipErrorInvalidValue;
-    }
+#define HMCG_BIAS(K_) hipLaunchKernelGGL(hmcg::bias_moments_kernel<K_>, grid, block, 0, stream, p)
+    HMCG_SWITCH_K(a.K, HMCG_BIAS)
 #undef HMCG_BIAS
     return hipGetLastError();
 }

@@ -36,7 +36,7 @@
 #include <stdint.h>
 
 #include "density.hpp"
-#include "round5.hpp"
+#include "stat_device.hpp"
 
 namespace hmcg {
 
@@ -85,6 +85,7 @@ __global__ __launch_bounds__(DN_NT) void density_range_kernel(const DensParams p
     __shared__ unsigned long long rk[DN_NW][DN_CB][2];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const long long nslab = (p.n + PRED_SLAB - 1) / PRED_SLAB;
+    // HMCG_STAT_SLAB of stat_device.hpp with a count in place of dend (as dend - dbeg this kernel compiles to other code)
     const int w = (int)((long long)blockIdx.x / nslab);
     const long long s = (long long)blockIdx.x - (long long)w * nslab;
     const long long dbeg = s * PRED_SLAB;
@@ -100,7 +101,7 @@ __global__ __launch_bounds__(DN_NT) void density_range_kernel(const DensParams p
 #pragma unroll
                 for (int k = 0; k < DN_TILES; ++k) {
                     const unsigned o = (unsigned)(k * DN_NT + tid);
-                    v[i][k] = o < cnt ? col[o] : __longlong_as_double(0x7ff8000000000000ll);
+                    v[i][k] = o < cnt ? col[o] : stat_nan();
                 }
             }
         }
@@ -110,7 +111,7 @@ __global__ __launch_bounds__(DN_NT) void density_range_kernel(const DensParams p
                 unsigned long long lo = DN_KMIN_NONE, hi = DN_KMAX_NONE;
 #pragma unroll
                 for (int k = 0; k < DN_TILES; ++k) {
-                    const double xr = p.round5 ? round5(v[i][k]) : v[i][k];
+                    const double xr = stat_in(v[i][k], p.round5);
                     if (isfinite(xr)) {
                         const unsigned long long key = dens_key(xr);
                         lo = key < lo ? key : lo;
@@ -150,7 +151,7 @@ __global__ __launch_bounds__(DN_NT) void density_resolve_kernel(const DensParams
     if (lo_hi) { lo = lo_hi[2 * i]; hi = lo_hi[2 * i + 1]; }
     else {
         const unsigned long long a = p.kmin[i], b = p.kmax[i];
-        const double nan = __longlong_as_double(0x7ff8000000000000ll);
+        const double nan = stat_nan();
         lo = a == DN_KMIN_NONE ? nan : dens_unkey(a);
         hi = a == DN_KMIN_NONE ? nan : dens_unkey(b);
     }
@@ -205,7 +206,8 @@ __global__ __launch_bounds__(DN_NT) void density_accumulate_kernel(const DensPar
 #pragma unroll
         for (int i = 0; i < DN_CB; ++i) {
             if (cb + i < ncols) {
-                // the pivot was rounded when it was filed; a launch that reads it from the data rounds it here
+                // the pivot was rounded when it was filed; a launch that reads it from the data rounds it here (stat_in of
+                // stat_device.hpp under one more condition)
                 const double pvt = (own_pivot && p.round5) ? round5(pv[i]) : pv[i];
                 const double width = hi[i] - lo[i];
                 const double scale = dB / width;
@@ -215,7 +217,7 @@ __global__ __launch_bounds__(DN_NT) void density_accumulate_kernel(const DensPar
 #pragma unroll
                 for (int k = 0; k < DN_TILES; ++k) {
                     const bool valid = (unsigned)(k * DN_NT + tid) < cnt;
-                    const double xr = p.round5 ? round5(v[i][k]) : v[i][k];
+                    const double xr = stat_in(v[i][k], p.round5);
                     if (valid && binned) {
                         int slot;
                         if (isnan(xr)) slot = p.B + 2;
@@ -233,11 +235,8 @@ __global__ __launch_bounds__(DN_NT) void density_accumulate_kernel(const DensPar
                     s1 += a[k];
                     s2 = fma(a[k], a[k], s2);
                 }
-#pragma unroll
-                for (int m = 32; m >= 1; m >>= 1) {
-                    s1 += __shfl_xor(s1, m, 64);
-                    s2 += __shfl_xor(s2, m, 64);
-                }
+                HMCG_WAVE_SUM(s1);
+                HMCG_WAVE_SUM(s2);
                 if (lane == 0) { red[wv][i][0] = s1; red[wv][i][1] = s2; }
                 if (tr_piece) {                              // block-uniform
                     double sc[DN_TILES];
@@ -286,7 +285,7 @@ __global__ __launch_bounds__(DN_NT) void density_accumulate_kernel(const DensPar
     if (own_pivot && q == 0) {
         for (int c = tid; c < ncols; c += DN_NT) {
             const double f = x0[(size_t)c * (size_t)p.nd_ld];
-            p.piv[(size_t)w * (size_t)p.C + (size_t)(c0 + c)] = p.round5 ? round5(f) : f;
+            p.piv[(size_t)w * (size_t)p.C + (size_t)(c0 + c)] = stat_in(f, p.round5);
         }
     }
     // the piece's counts into its segment's row; most bins of a posterior are empty
@@ -377,8 +376,7 @@ static bool dens_params(const DensArgs& a, hmcg::DensParams& p)
 {
     if (a.C < 1 || a.C > HMCG_MAXK * HMCG_MAXK || a.B < 1 || a.B > HMCG_DENS_MAXBINS || a.n_cuts < 1 || a.n_cuts > HMCG_MAXH) return false;
     if (a.trace_len < 0 || a.trace_len > HMCG_DENS_MAXTRACE || a.trace_stride < 1) return false;
-    if (a.nd < 1 || a.n < 1 || a.d_origin < 0 || a.d_origin % PRED_SLAB != 0 || a.d_origin + a.n > a.nd || a.nd_ld < a.n) return false;
-    if (a.d_origin + a.n < a.nd && a.n % PRED_SLAB != 0) return false;
+    if (a.nd < 1 || !chunk_origin_ok(a.d_origin, a.n, a.nd) || a.nd_ld < a.n) return false;
     for (int j = 0; j < a.n_cuts; ++j)
         if (a.cuts[j] < 1 || a.cuts[j] > a.nd || (j > 0 && a.cuts[j] <= a.cuts[j - 1])) return false;
     if ((long long)a.trace_len * a.trace_stride > a.nd) return false;

@@ -2,7 +2,7 @@
 // of its columns into groups that fit LDS.  Plain C++17 without a HIP header (in the manner of predictive_plan.hpp): a
 // g++-compiled program runs exactly the code the library runs, on the CPU; dens_piece is also what the kernels call.
 //
-// Pieces: the union of the slab boundaries of predictive_plan.hpp (multiples of PRED_SLAB, so an upload chunk of the host entry
+// Pieces: the union of the slab boundaries of stat_plan.hpp (multiples of PRED_SLAB, so an upload chunk of the host entry
 // is a whole number of pieces) and the cut points splits [0, nd) into dens_pieces() <= pred_slabs(nd) + n_cuts pieces
 // (d0, n, segment), n <= PRED_SLAB.  segment = the number of cuts <= d0: a piece of segment s lies inside the prefixes
 // cuts[s], cuts[s + 1], ... and in no shorter one; draws beyond the last cut form segment n_cuts and feed the automatic range
@@ -13,7 +13,7 @@
 #include <cstdio>
 
 #include "../../include/hmcg.h"
-#include "predictive_plan.hpp"
+#include "stat_plan.hpp"
 
 #ifdef __HIPCC__
 #define HMCG_DENS_HD __host__ __device__ __forceinline__
@@ -25,7 +25,6 @@ namespace hmcg_host {
 
 constexpr int DENS_SLOTS = 3;                // counters behind the B bins: below, above, nan
 constexpr int DENS_LDS_WORDS = 8192;         // 32-bit counters one block keeps in LDS (32 KB of the 160 KB a CU has)
-constexpr long long DENS_MAX_ND = 1LL << 53; // counts are 64-bit; n is a divisor in fp64 and must be exact
 
 struct DensPiece { long long d0, n; int segment; };
 
@@ -89,17 +88,10 @@ HMCG_DENS_HD int dens_groups(int C, int B)
 inline int check_density(const hmcg_density* p, const double* x, const double* lo_hi, const double* range, const int64_t* counts,
                          const double* stats, const double* trace, bool host, char* msg, size_t nmsg)
 {
-    if (!p) { snprintf(msg, nmsg, "hmcg_density is NULL"); return HMCG_E_BADARG; }
-    if (p->struct_size != (int32_t)sizeof(hmcg_density)) {
-        snprintf(msg, nmsg, "hmcg_density.struct_size %d != %d", p->struct_size, (int)sizeof(hmcg_density));
-        return HMCG_E_BADARG;
-    }
-    if (p->W < 1) { snprintf(msg, nmsg, "W = %d: at least one window", p->W); return HMCG_E_BADARG; }
-    if (p->C < 1 || p->C > HMCG_MAXK * HMCG_MAXK) { snprintf(msg, nmsg, "C = %d columns outside 1..%d", p->C, HMCG_MAXK * HMCG_MAXK); return HMCG_E_BADARG; }
+    if (bad_struct(p, "hmcg_density", msg, nmsg) || bad_W(p->W, msg, nmsg) || bad_C(p->C, msg, nmsg)) return HMCG_E_BADARG;
     if (p->B < 1 || p->B > HMCG_DENS_MAXBINS) { snprintf(msg, nmsg, "B = %d bins outside 1..%d", p->B, HMCG_DENS_MAXBINS); return HMCG_E_BADARG; }
-    if (p->nd < 1) { snprintf(msg, nmsg, "nd = %lld: at least one draw", (long long)p->nd); return HMCG_E_BADARG; }
-    if (p->nd > DENS_MAX_ND) { snprintf(msg, nmsg, "nd = %lld exceeds 2^53, the largest exact divisor", (long long)p->nd); return HMCG_E_BADARG; }
-    if (p->nd_ld < p->nd) { snprintf(msg, nmsg, "nd_ld = %lld < nd = %lld", (long long)p->nd_ld, (long long)p->nd); return HMCG_E_BADARG; }
+    // counts are 64-bit, but n is a divisor in fp64
+    if (bad_nd(p->nd, msg, nmsg) || bad_exact_nd(p->nd, msg, nmsg) || bad_nd_ld(p->nd_ld, p->nd, msg, nmsg)) return HMCG_E_BADARG;
     if (p->n_cuts < 1 || p->n_cuts > HMCG_MAXH) { snprintf(msg, nmsg, "n_cuts = %d outside 1..%d", p->n_cuts, HMCG_MAXH); return HMCG_E_BADARG; }
     for (int j = 0; j < p->n_cuts; ++j) {
         if (p->cuts[j] < 1 || p->cuts[j] > p->nd) {
@@ -124,10 +116,7 @@ inline int check_density(const hmcg_density* p, const double* x, const double* l
         snprintf(msg, nmsg, "W * pieces * column groups exceeds one launch (2^31 - 1 blocks)");
         return HMCG_E_BADARG;
     }
-    if ((long long)p->W * p->C > 2147483647LL) {         // the finalize kernel runs one block per (window, column)
-        snprintf(msg, nmsg, "W * C exceeds one launch (2^31 - 1 blocks)");
-        return HMCG_E_BADARG;
-    }
+    if (bad_WC(p->W, p->C, msg, nmsg)) return HMCG_E_BADARG;        // the finalize kernel
     if (!x || !range || !counts || !stats) { snprintf(msg, nmsg, "x, range, counts and stats are required"); return HMCG_E_BADARG; }
     if (!trace && p->trace_len > 0) { snprintf(msg, nmsg, "trace is NULL with trace_len > 0"); return HMCG_E_BADARG; }
     if (host && lo_hi)

@@ -1007,7 +1007,7 @@ double* pack_columns(const double* src, size_t cols, size_t ld, long long d0, si
     return dst + cols * n;
 }
 
-// The upload ring of a statistic's host entry.  The draws go up in chunks of whole slabs (predictive_plan.hpp): packed column by
+// The upload ring of a statistic's host entry.  The draws go up in chunks of whole slabs (stat_plan.hpp): packed column by
 // column into pinned staging (leading dimension = the chunk's draws), copied on the copy stream, reduced on the compute stream,
 // RING buffers deep, so chunk c + 1 is packed and copied while chunk c's kernel runs.  Every chunk adds to the same sums in the
 // work area; the caller finalizes at the end.  Both arenas are laid out once, before any pointer is taken: `io` (results and
@@ -1108,7 +1108,7 @@ struct UploadRing {
     }
 };
 
-// ---- predictive CDFs of the regime mixture (predictive.hip; argument rules and slab / chunk cut: predictive_plan.hpp) ----------
+// ---- predictive CDFs of the regime mixture (predictive.hip; argument rules: predictive_plan.hpp; slab / chunk cut: stat_plan.hpp) ----
 
 hmcg_host::PredictiveArgs predictive_args(const hmcg_predictive* p)
 {
@@ -1179,7 +1179,7 @@ int predictive_host(DeviceCtx& c, const hmcg_predictive* p, const double* mu, co
     return ring.report(predictive_shape(p), (int)ring.uploads + 1);
 }
 
-// ---- uncertainty-bias moments of the draws (bias.hip; argument rules: bias_plan.hpp; slab / chunk cut: predictive_plan.hpp) ------
+// ---- uncertainty-bias moments of the draws (bias.hip; argument rules: bias_plan.hpp; slab / chunk cut: stat_plan.hpp) ------------
 
 hmcg_host::BiasArgs bias_args(const hmcg_bias* p)
 {
@@ -1249,7 +1249,7 @@ int bias_host(DeviceCtx& c, const hmcg_bias* p, const double* mu, const double* 
 }
 
 // ---- predictive-mixture moments of the draws (mixmoments.hip; argument rules and the walk: mixmoments_plan.hpp; slab / chunk cut:
-// predictive_plan.hpp) -----------------------------------------------------------------------------------------------------------
+// stat_plan.hpp) -----------------------------------------------------------------------------------------------------------------
 
 hmcg_host::MixArgs mix_args(const hmcg_mixmom* p)
 {
@@ -1315,7 +1315,7 @@ int mix_host(DeviceCtx& c, const hmcg_mixmom* p, const double* mu, const double*
 }
 
 // ---- chain densities and running means of the draws (density.hip; argument rules, pieces and column groups: density_plan.hpp;
-// chunk cut: predictive_plan.hpp) -------------------------------------------------------------------------------------------------
+// chunk cut: stat_plan.hpp) -------------------------------------------------------------------------------------------------------
 
 hmcg_host::DensArgs dens_args(const hmcg_density* p)
 {
@@ -1401,7 +1401,7 @@ int dens_host(DeviceCtx& c, const hmcg_density* p, const double* x, const double
 }
 
 // ---- autocorrelation, effective sample size and split-R-hat of the draws (autocorr.hip; argument rules and thread split:
-// autocorr_plan.hpp; chunk cut: predictive_plan.hpp) ------------------------------------------------------------------------------
+// autocorr_plan.hpp; chunk cut: stat_plan.hpp) ------------------------------------------------------------------------------------
 
 hmcg_host::AcfArgs acf_args(const hmcg_autocorr* p)
 {

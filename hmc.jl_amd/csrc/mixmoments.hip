@@ -14,8 +14,8 @@
 // Shape: one block of 256 threads per (window, slab of PRED_SLAB draws); a slab is walked in tiles of 256 draws.  Thread t takes
 // draw t of the tile: pi_end, A, mu and sig2 are read coalesced along d (every column one 2 KB line of consecutive doubles per
 // tile, a scalar base and a 32-bit lane offset), rounded as CSV cells under round5.  A stays in registers; omega = pi_end A^h
-// by row-vector x matrix products, k ascending in every dot product -- the expression of predictive.hip and bias.hip, so all
-// three features hold the same omega bits.  The horizons are walked in ascending order along one chain (mix_walk): h_max
+// by row-vector x matrix products (HMCG_OMEGA_STEP of stat_device.hpp, the one expression of all three features that use
+// omega).  The horizons are walked in ascending order along one chain (mix_walk): h_max
 // products instead of the sum, the same bits for every horizon, equal bits for equal horizons.  At every stop of the walk the
 // thread adds the draw's nine terms to its own nine accumulators of that stop; the accumulators are indexed by unrolled,
 // constant stop numbers and stay in registers (the kernel is built for up to 2 and for up to HMCG_MAXH stops).  At the end
@@ -35,7 +35,7 @@
 #include <stdint.h>
 
 #include "mixmoments.hpp"
-#include "round5.hpp"
+#include "stat_device.hpp"
 
 namespace hmcg {
 
@@ -55,7 +55,7 @@ struct MixParams {
     int hz[HMCG_MAXH], slot[HMCG_MAXH];      // the ascending walk (mixmoments_plan.hpp)
 };
 
-// a[i] for a per-thread i without indexing the kernel arguments by a register
+// a[i] for a per-thread i without indexing the kernel arguments by a register (predictive.hip has the ladder inline, started at 0)
 __device__ __forceinline__ int mix_pick(const int* a, int i)
 {
     int r = a[0];
@@ -70,10 +70,7 @@ __global__ __launch_bounds__(MIX_NT) void mixmoments_kernel(const MixParams p)
     __shared__ double C[HMCG_MAXH], A0[HMCG_MAXH];      // per stop of the walk: the pivot and draw 0's a
     __shared__ double R[MIX_NW][NHC * MIX_ITEMS];
     const int tid = threadIdx.x, lane = tid & 63, q = tid >> 6;
-    const int w = (int)((long long)blockIdx.x / p.nslab);
-    const long long s = (long long)blockIdx.x - (long long)w * p.nslab;
-    const long long dbeg = s * hmcg_host::PRED_SLAB;
-    const long long dend = dbeg + hmcg_host::PRED_SLAB < p.nd ? dbeg + hmcg_host::PRED_SLAB : p.nd;
+    HMCG_STAT_SLAB(w, s, dbeg, dend, p.nslab, p.nd);
     const int ntile = (int)((dend - dbeg + MIX_NT - 1) / MIX_NT);
     const double* mu = p.mu + (size_t)w * K * p.nd_ld;
     const double* sg = p.sig2 + (size_t)w * K * p.nd_ld;
@@ -95,10 +92,7 @@ __global__ __launch_bounds__(MIX_NT) void mixmoments_kernel(const MixParams p)
     // it = -2, -1: the pivot passes (thread 0 on draw 0), through the same code as every tile
 #pragma unroll 1
     for (int it = own_pivot ? -2 : 0; it < ntile; ++it) {
-        // wave-uniform 64-bit base + 32-bit lane offset: every column is one scalar-base load, no 64-bit address per column
-        const size_t base = it < 0 ? (size_t)0 : (size_t)dbeg;
-        const unsigned o = it < 0 ? 0u : (unsigned)(it * MIX_NT + tid);
-        const bool valid = it < 0 ? tid == 0 : (long long)base + o < dend;
+        const auto [base, o, valid] = stat_tile(it, MIX_NT, tid, dbeg, dend);
         if (valid) {
             // every column is loaded before any is rounded: a rounding between two loads would make the second wait for the first
             double wv[K], m[K], v[K], a[K * K];
@@ -116,7 +110,7 @@ __global__ __launch_bounds__(MIX_NT) void mixmoments_kernel(const MixParams p)
                 m[k] = (mu + (size_t)k * p.nd_ld + base)[o];
                 v[k] = (sg + (size_t)k * p.nd_ld + base)[o];
             }
-            if (p.round5) {
+            if (p.round5) {                                      // stat_in of stat_device.hpp, taken once for all cells
 #pragma unroll
                 for (int k = 0; k < K; ++k) { wv[k] = round5(wv[k]); m[k] = round5(m[k]); v[k] = round5(v[k]); }
 #pragma unroll
@@ -128,18 +122,7 @@ __global__ __launch_bounds__(MIX_NT) void mixmoments_kernel(const MixParams p)
                 if (i < p.n_h) {
                     if (At) {
 #pragma unroll 1
-                        for (; step < p.hz[i]; ++step) {
-                            double nw[K];
-#pragma unroll
-                            for (int c = 0; c < K; ++c) {
-                                double t = wv[0] * a[K * c];
-#pragma unroll
-                                for (int r = 1; r < K; ++r) t += wv[r] * a[r + K * c];
-                                nw[c] = t;
-                            }
-#pragma unroll
-                            for (int c = 0; c < K; ++c) wv[c] = nw[c];
-                        }
+                        for (; step < p.hz[i]; ++step) HMCG_OMEGA_STEP(K, wv, a, 1);
                     }
                     const double c = C[i], a0 = A0[i];
                     double sw = wv[0];
@@ -187,8 +170,7 @@ __global__ __launch_bounds__(MIX_NT) void mixmoments_kernel(const MixParams p)
 #pragma unroll
             for (int e = 0; e < MIX_ITEMS; ++e) {
                 double t = acc[i][e];
-#pragma unroll
-                for (int x = 32; x >= 1; x >>= 1) t += __shfl_xor(t, x, 64);
+                HMCG_WAVE_SUM(t);
                 if (lane == 0) R[q][i * MIX_ITEMS + e] = t;
             }
         }
@@ -199,7 +181,7 @@ __global__ __launch_bounds__(MIX_NT) void mixmoments_kernel(const MixParams p)
         double t = R[0][tid];
 #pragma unroll
         for (int x = 1; x < MIX_NW; ++x) t += R[x][tid];
-        double* row = p.part + ((size_t)w * (size_t)p.nslab_total + (size_t)(p.slab0 + s)) * (size_t)(p.n_h * MIX_ITEMS);
+        double* row = p.part + HMCG_STAT_ROW(w, p.nslab_total, p.slab0 + s, p.n_h * MIX_ITEMS);
         row[mix_pick(p.slot, i) * MIX_ITEMS + e] = t;
     }
 }
@@ -214,7 +196,7 @@ __global__ __launch_bounds__(MIX_FIN_NT) void mixmoments_finalize_kernel(const d
     double T[MIX_ITEMS];
 #pragma unroll
     for (int e = 0; e < MIX_ITEMS; ++e) T[e] = 0.0;
-    for (long long sl = 0; sl < nslab; ++sl) {
+    for (long long sl = 0; sl < nslab; ++sl) {                   // HMCG_SLAB_SUM of stat_device.hpp, nine items per trip
 #pragma unroll
         for (int e = 0; e < MIX_ITEMS; ++e) T[e] += col[(size_t)sl * (size_t)(n_h * MIX_ITEMS) + e];
     }
@@ -260,18 +242,13 @@ hipError_t launch_mixmoments(const MixArgs& a, hipStream_t stream)
     p.part = a.part; p.piv = a.part + (size_t)a.W * (size_t)a.nslab_total * (size_t)a.n_h * (size_t)MIX_ITEMS;
     p.nd = a.nd; p.nd_ld = a.nd_ld; p.nslab = pred_slabs(a.nd); p.slab0 = a.slab0; p.nslab_total = a.nslab_total;
     p.n_h = a.n_h; p.round5 = a.round5 ? 1 : 0;
-    if (a.nd_ld < a.nd || p.slab0 < 0 || p.slab0 + p.nslab > p.nslab_total || (long long)a.W * p.nslab > 0x7fffffffLL) return hipErrorInvalidValue;
+    if (!slab_range_ok(a.W, a.nd, a.nd_ld, a.slab0, a.nslab_total)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((long long)a.W * p.nslab)), block(hmcg::MIX_NT);
     // two builds per K: accumulators for up to 2 stops of the walk (the production call: horizons 0 and 12) and for up to HMCG_MAXH
 #define HMCG_MIX(K_)                                                                                              \
-    case K_:                                                                                                      \
-        if (a.n_h <= 2) hipLaunchKernelGGL((hmcg::mixmoments_kernel<K_, 2>), grid, block, 0, stream, p);          \
-        else hipLaunchKernelGGL((hmcg::mixmoments_kernel<K_, HMCG_MAXH>), grid, block, 0, stream, p);             \
-        break
-    switch (a.K) {
-        HMCG_MIX(2); HMCG_MIX(3); HMCG_MIX(4); HMCG_MIX(5); HMCG_MIX(6); HMCG_MIX(7); HMCG_MIX(8);
-        default: return hipErrorInvalidValue;
-    }
+    if (a.n_h <= 2) hipLaunchKernelGGL((hmcg::mixmoments_kernel<K_, 2>), grid, block, 0, stream, p);              \
+    else hipLaunchKernelGGL((hmcg::mixmoments_kernel<K_, HMCG_MAXH>), grid, block, 0, stream, p)
+    HMCG_SWITCH_K(a.K, HMCG_MIX)
 #undef HMCG_MIX
     return hipGetLastError();
 }

@@ -9,7 +9,7 @@
 //
 // Shape: one block per (window, slab of PRED_SLAB draws, 128 (horizon, grid point) items).  A tile of 64 draws is staged in LDS --
 // per draw and state mu_k and c_k = 1 / (sqrt 2 * sqrt(sig2_k)) side by side, and the n_h * K weights, built per (draw, horizon) by
-// h successive row-vector x matrix products over the tile's transition draws (k ascending in every dot product).  Each thread then
+// h successive row-vector x matrix products over the tile's transition draws (HMCG_OMEGA_STEP of stat_device.hpp).  Each thread then
 // owns one (horizon, grid point) and walks the tile in draw order: every lane reads the same mu, c (one broadcast ds_read_b128),
 // Phi = erfc(-(y - mu) c) / 2.  fp64 VALU work by construction: 8 (3K [+ K^2]) bytes read per draw against K * n_h * G erfc.
 //
@@ -20,7 +20,7 @@
 #include <stdint.h>
 
 #include "predictive.hpp"
-#include "round5.hpp"
+#include "stat_device.hpp"
 
 namespace hmcg {
 
@@ -37,8 +37,6 @@ struct PredictiveParams {
     int hz[HMCG_MAXH];
 };
 
-__device__ __forceinline__ double pred_in(double x, int r5) { return r5 ? round5(x) : x; }
-
 template <int K>
 __global__ __launch_bounds__(PRED_NT) void predictive_cdf_kernel(const PredictiveParams p)
 {
@@ -48,14 +46,11 @@ __global__ __launch_bounds__(PRED_NT) void predictive_cdf_kernel(const Predictiv
     double* Ws = MC + PRED_TD * K * 2;                   // [PRED_TD][n_h][K]: weights of every horizon
     double* As = Ws + PRED_TD * n_h * K;                 // [K * K][PRED_TD]: transition draws (present with a horizon > 0)
     const int tid = threadIdx.x;
-    const int w = (int)((long long)blockIdx.x / p.nslab);
-    const long long s = (long long)blockIdx.x - (long long)w * p.nslab;
-    const long long dbeg = s * hmcg_host::PRED_SLAB;
-    const long long dend = dbeg + hmcg_host::PRED_SLAB < p.nd ? dbeg + hmcg_host::PRED_SLAB : p.nd;
+    HMCG_STAT_SLAB(w, s, dbeg, dend, p.nslab, p.nd);
     const int e = (int)blockIdx.y * PRED_NT + tid;       // this thread's item: horizon j, grid point g
     const bool live = e < p.items;
     const int j = live ? e / p.G : 0, g = live ? e - j * p.G : 0;
-    const double y = pred_in(p.grid[g], p.round5);
+    const double y = stat_in(p.grid[g], p.round5);
     const double* mu = p.mu + (size_t)w * K * p.nd_ld;
     const double* sig2 = p.sig2 + (size_t)w * K * p.nd_ld;
     const double* pie = p.pi_end + (size_t)w * K * p.nd_ld;
@@ -67,14 +62,14 @@ __global__ __launch_bounds__(PRED_NT) void predictive_cdf_kernel(const Predictiv
             const int k = q / PRED_TD, dd = q - k * PRED_TD;
             if (dd < nv) {
                 const size_t off = (size_t)k * p.nd_ld + (size_t)(d0 + dd);
-                MC[(dd * K + k) * 2] = pred_in(mu[off], p.round5);
-                MC[(dd * K + k) * 2 + 1] = 1.0 / (1.4142135623730951 * sqrt(pred_in(sig2[off], p.round5)));
+                MC[(dd * K + k) * 2] = stat_in(mu[off], p.round5);
+                MC[(dd * K + k) * 2 + 1] = 1.0 / (1.4142135623730951 * sqrt(stat_in(sig2[off], p.round5)));
             }
         }
         if (At) {
             for (int q = tid; q < K * K * PRED_TD; q += PRED_NT) {
                 const int c = q / PRED_TD, dd = q - c * PRED_TD;
-                if (dd < nv) As[q] = pred_in(At[(size_t)c * p.nd_ld + (size_t)(d0 + dd)], p.round5);
+                if (dd < nv) As[q] = stat_in(At[(size_t)c * p.nd_ld + (size_t)(d0 + dd)], p.round5);
             }
         }
         __syncthreads();
@@ -82,24 +77,13 @@ __global__ __launch_bounds__(PRED_NT) void predictive_cdf_kernel(const Predictiv
         for (int q = tid; q < n_h * PRED_TD; q += PRED_NT) {
             const int jh = q / PRED_TD, dd = q - jh * PRED_TD;
             if (dd >= nv) continue;
-            int h = 0;
+            int h = 0;                                   // mix_pick of mixmoments.hip, begun at 0; neither kernel takes the other's form
 #pragma unroll
             for (int i = 0; i < HMCG_MAXH; ++i) h = jh == i ? p.hz[i] : h;
             double wv[K];
 #pragma unroll
-            for (int k = 0; k < K; ++k) wv[k] = pred_in(pie[(size_t)k * p.nd_ld + (size_t)(d0 + dd)], p.round5);
-            for (int step = 0; step < h; ++step) {
-                double nw[K];
-#pragma unroll
-                for (int c = 0; c < K; ++c) {
-                    double t = wv[0] * As[(K * c) * PRED_TD + dd];
-#pragma unroll
-                    for (int i = 1; i < K; ++i) t += wv[i] * As[(i + K * c) * PRED_TD + dd];
-                    nw[c] = t;
-                }
-#pragma unroll
-                for (int c = 0; c < K; ++c) wv[c] = nw[c];
-            }
+            for (int k = 0; k < K; ++k) wv[k] = stat_in(pie[(size_t)k * p.nd_ld + (size_t)(d0 + dd)], p.round5);
+            for (int step = 0; step < h; ++step) HMCG_OMEGA_STEP(K, wv, As + dd, PRED_TD);
 #pragma unroll
             for (int k = 0; k < K; ++k) Ws[(dd * n_h + jh) * K + k] = wv[k];
         }
@@ -121,7 +105,7 @@ __global__ __launch_bounds__(PRED_NT) void predictive_cdf_kernel(const Predictiv
         }
         __syncthreads();
     }
-    if (live) p.part[((size_t)w * (size_t)p.nslab_total + (size_t)(p.slab0 + s)) * (size_t)p.items + (size_t)e] = acc;
+    if (live) p.part[HMCG_STAT_ROW(w, p.nslab_total, p.slab0 + s, p.items) + (size_t)e] = acc;
 }
 
 __global__ __launch_bounds__(PRED_FIN_NT) void predictive_finalize_kernel(const double* part, double* cdf, long long nslab, int items,
@@ -132,8 +116,7 @@ __global__ __launch_bounds__(PRED_FIN_NT) void predictive_finalize_kernel(const 
     const long long w = idx / items;
     const int e = (int)(idx - w * items);
     const double* col = part + (size_t)w * (size_t)nslab * (size_t)items + (size_t)e;
-    double sum = 0.0;
-    for (long long sl = 0; sl < nslab; ++sl) sum += col[(size_t)sl * (size_t)items];
+    HMCG_SLAB_SUM(sum, col, nslab, items);
     cdf[idx] = sum / nd;
 }
 
@@ -159,20 +142,18 @@ hipError_t launch_predictive(const PredictiveArgs& a, hipStream_t stream)
     for (int j = 0; j < HMCG_MAXH; ++j) { p.hz[j] = j < a.n_h ? a.horizons[j] : 0; with_A = with_A || p.hz[j] > 0; }
     if (with_A && !a.A) return hipErrorInvalidValue;
     if (!with_A) p.A = nullptr;
-    if (p.slab0 < 0 || p.slab0 + p.nslab > p.nslab_total || (long long)a.W * p.nslab > 0x7fffffffLL) return hipErrorInvalidValue;
+    // nd_ld >= nd is part of the rule; check_predictive has enforced it ahead of every launch already
+    if (!slab_range_ok(a.W, a.nd, a.nd_ld, a.slab0, a.nslab_total)) return hipErrorInvalidValue;
     const size_t lds = predictive_lds_bytes(a.K, a.n_h, with_A);
     const dim3 grid((unsigned)((long long)a.W * p.nslab), (unsigned)((p.items + hmcg::PRED_NT - 1) / hmcg::PRED_NT)), block(hmcg::PRED_NT);
 #define HMCG_PRED(K_)                                                                                                     \
-    case K_: {                                                                                                            \
+    {                                                                                                                     \
         hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(hmcg::predictive_cdf_kernel<K_>),               \
                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                         \
         if (e_ != hipSuccess) return e_;                                                                                   \
         hipLaunchKernelGGL(hmcg::predictive_cdf_kernel<K_>, grid, block, lds, stream, p);                                  \
-    } break
-    switch (a.K) {
-        HMCG_PRED(2); HMCG_PRED(3); HMCG_PRED(4); HMCG_PRED(5); HMCG_PRED(6); HMCG_PRED(7); HMCG_PRED(8);
-        default: return hipErrorInvalidValue;
     }
+    HMCG_SWITCH_K(a.K, HMCG_PRED)
 #undef HMCG_PRED
     return hipGetLastError();
 }

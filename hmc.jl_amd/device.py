@@ -80,13 +80,27 @@ class DevicePanel:
         self.last_timing = tm
         return tm.kernel_ms if tm is not None else None
 
+    def _draws(self, what, var="mu"):
+        """The panel's HBM draws of `var` for the statistic `what`, and their columns per window."""
+        if var not in _lib.DRAW_KEYS:
+            raise ValueError("var must be one of %s" % (_lib.DRAW_KEYS,))
+        x = getattr(self, var)
+        if x is None:
+            raise _lib.HmcgError("%s needs the draws in HBM: the panel was built with keep_draws=False" % what)
+        return x, int(x.numel() // (self.W * self.nrun))
+
+    def _done(self, tm, timed, out):
+        """The tail of a statistic: a timed call has waited and leaves its record in last_timing."""
+        if timed:
+            self.last_timing = tm
+        return out
+
     def predictive_cdf(self, grid, horizons=(0,), timed=False, round5=True):
         """Predictive CDFs of the regime mixture from the panel's own HBM draws (hmcg_predictive_cdf_device; calc_cdfs.jl at
         horizon 0, the weights pi_end A^h beyond it): a (W, n_h, G) tensor, the mean over the kept draws per window, horizon
         and grid point.  Enqueued on the library stream behind `run`; with timed=True the call waits and last_timing holds
         the HIP-event time, otherwise call sync() before reading the tensor."""
-        if self.mu is None:
-            raise _lib.HmcgError("predictive_cdf needs the draws in HBM: the panel was built with keep_draws=False")
+        self._draws("predictive_cdf")
         torch = self.torch
         g = torch.from_numpy(np.ascontiguousarray(grid, dtype=np.float64).reshape(-1)).to(self.dev)    # a blocking copy
         cdf = torch.empty((self.W, len(horizons), g.numel()), dtype=torch.float64, device=self.dev)
@@ -95,9 +109,7 @@ class DevicePanel:
         tm = _lib.predictive_cdf_device(pred, self.mu.data_ptr(), self.sig2.data_ptr(), self.pi_end.data_ptr(),
                                         self.A.data_ptr() if need_A else 0, g.data_ptr(), cdf.data_ptr(), None, timed)
         self._pred_grid = g                 # kept until the enqueued kernel has read it
-        if timed:
-            self.last_timing = tm
-        return cdf
+        return self._done(tm, timed, cdf)
 
     def bias_moments(self, horizon=12, timed=False, round5=True):
         """Uncertainty-bias moments from the panel's own HBM draws (hmcg_bias_moments_device; bias_calcs.jl:40-53): a
@@ -105,16 +117,13 @@ class DevicePanel:
         of [pi_end A^horizon | mu] over the kept draws (_lib.unpack_bias names the parts of its numpy copy).  Enqueued on the
         library stream behind `run`; with timed=True the call waits and last_timing holds the HIP-event time, otherwise call
         sync() before reading the tensor."""
-        if self.mu is None:
-            raise _lib.HmcgError("bias_moments needs the draws in HBM: the panel was built with keep_draws=False")
+        self._draws("bias_moments")
         H = len(self.horizons)
         out = self.torch.empty((self.W, _lib.bias_stride(self.K)), dtype=self.torch.float64, device=self.dev)
         bias = _lib.make_bias(self.W, self.K, self.nrun, self.nrun, horizon, H, self.device_index, round5)
         tm = _lib.bias_moments_device(bias, self.mu.data_ptr(), self.pi_end.data_ptr(), self.A.data_ptr() if int(horizon) > 0 else 0,
                                       self.fcast.data_ptr() if H > 0 else 0, out.data_ptr(), None, timed)
-        if timed:
-            self.last_timing = tm
-        return out
+        return self._done(tm, timed, out)
 
     def mixture_moments(self, horizons=(0,), timed=False, round5=True):
         """Moments of the predictive regime mixture from the panel's own HBM draws (hmcg_mixture_moments_device; skewness.jl
@@ -123,16 +132,13 @@ class DevicePanel:
         within-draw variance, the variance of the per-draw mean, the mean per-draw skewness and the mean weight
         (_lib.unpack_mixture_moments names the parts of its numpy copy).  Enqueued on the library stream behind `run`; with
         timed=True the call waits and last_timing holds the HIP-event time, otherwise call sync() before reading the tensor."""
-        if self.mu is None:
-            raise _lib.HmcgError("mixture_moments needs the draws in HBM: the panel was built with keep_draws=False")
+        self._draws("mixture_moments")
         hz = tuple(int(h) for h in horizons)
         out = self.torch.empty((self.W, len(hz), _lib.MIX_STRIDE), dtype=self.torch.float64, device=self.dev)
         mix = _lib.make_mixmom(self.W, self.K, self.nrun, self.nrun, hz, self.device_index, round5)
         tm = _lib.mixture_moments_device(mix, self.mu.data_ptr(), self.sig2.data_ptr(), self.pi_end.data_ptr(),
                                          self.A.data_ptr() if any(h > 0 for h in hz) else 0, out.data_ptr(), None, timed)
-        if timed:
-            self.last_timing = tm
-        return out
+        return self._done(tm, timed, out)
 
     def chain_density(self, var="mu", cuts=None, bins=64, lo_hi=None, trace=(0, 1), timed=False, round5=True):
         """Chain densities and running means of one variable's draws from the panel's own HBM draws
@@ -145,13 +151,8 @@ class DevicePanel:
         prefix, trace (W, C, length); _lib.unpack_chain_density names the parts of their numpy copies.  Enqueued on the library
         stream behind `run`; with timed=True the call waits and last_timing holds the HIP-event time, otherwise call sync()
         before reading the tensors."""
-        if var not in _lib.DRAW_KEYS:
-            raise ValueError("var must be one of %s" % (_lib.DRAW_KEYS,))
-        x = getattr(self, var)
-        if x is None:
-            raise _lib.HmcgError("chain_density needs the draws in HBM: the panel was built with keep_draws=False")
+        x, Cn = self._draws("chain_density", var)
         torch = self.torch
-        Cn = int(x.numel() // (self.W * self.nrun))
         dens = _lib.make_density(self.W, Cn, self.nrun, self.nrun, cuts, bins, trace, self.device_index, round5)
         f64 = dict(dtype=torch.float64, device=self.dev)
         lh = None
@@ -166,9 +167,7 @@ class DevicePanel:
                                        out["trace"].data_ptr() if dens.trace_len > 0 else 0, None, timed)
         if lh is not None and not timed:    # a timed call has waited; otherwise the enqueued kernels may still read it
             self._held.append(lh)
-        if timed:
-            self.last_timing = tm
-        return out
+        return self._done(tm, timed, out)
 
     def chain_autocorr(self, var="mu", lags=255, timed=False, round5=True):
         """Autocovariances and convergence diagnostics of one variable's draws from the panel's own HBM draws
@@ -177,20 +176,13 @@ class DevicePanel:
         tau, ess, mcse, pairs, truncated, rhat; _lib.unpack_chain_autocorr names the parts of their numpy copies.  Enqueued on the
         library stream behind `run`; with timed=True the call waits and last_timing holds the HIP-event time, otherwise call
         sync() before reading the tensors."""
-        if var not in _lib.DRAW_KEYS:
-            raise ValueError("var must be one of %s" % (_lib.DRAW_KEYS,))
-        x = getattr(self, var)
-        if x is None:
-            raise _lib.HmcgError("chain_autocorr needs the draws in HBM: the panel was built with keep_draws=False")
+        x, Cn = self._draws("chain_autocorr", var)
         torch = self.torch
-        Cn = int(x.numel() // (self.W * self.nrun))
         acf = _lib.make_autocorr(self.W, Cn, self.nrun, self.nrun, lags, self.device_index, round5)
         f64 = dict(dtype=torch.float64, device=self.dev)
         out = {"acov": torch.empty((self.W, Cn, max(int(lags), 0) + 1), **f64), "diag": torch.empty((self.W, Cn, _lib.ACF_STRIDE), **f64)}
         tm = _lib.chain_autocorr_device(acf, x.data_ptr(), out["acov"].data_ptr(), out["diag"].data_ptr(), None, timed)
-        if timed:
-            self.last_timing = tm
-        return out
+        return self._done(tm, timed, out)
 
     def sync(self):
         """Wait for the library stream (untimed runs are asynchronous)."""

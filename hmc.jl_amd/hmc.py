@@ -433,6 +433,15 @@ class BatchResult:
         return _unpack(self._res, w, o.Nrun, o.D, len(o.horizons), enddate(o))
 
 
+def _draw_vars(name, vars_):
+    """The argument `name` of estimatewindows, names of draw arrays, as a tuple (None stays None)."""
+    vars_ = None if vars_ is None else tuple(vars_)
+    for var in vars_ or ():
+        if var not in DENSITY_FILES:
+            raise ValueError("%s: %r is none of %s" % (name, var, tuple(DENSITY_FILES)))
+    return vars_
+
+
 def estimatewindows(rawdata, dates, endIndices, startIndex=1, keep_draws=False, device=0, window_ids=None, corr=False,
                     cdf_grid=None, cdf_horizons=(0,), bias_horizon=None, moment_horizons=None, density_vars=None,
                     density_cuts=None, density_bins=64, density_trace=(0, 1), acf_vars=None, acf_lags=255, **kwargs):
@@ -463,16 +472,7 @@ def estimatewindows(rawdata, dates, endIndices, startIndex=1, keep_draws=False, 
     and dropped likewise."""
     if startIndex != 1:
         raise ValueError("windows must start at index 1 (see estopt)")
-    if acf_vars is not None:
-        acf_vars = tuple(acf_vars)
-        for var in acf_vars:
-            if var not in DENSITY_FILES:
-                raise ValueError("acf_vars: %r is none of %s" % (var, tuple(DENSITY_FILES)))
-    if density_vars is not None:
-        density_vars = tuple(density_vars)
-        for var in density_vars:
-            if var not in DENSITY_FILES:
-                raise ValueError("density_vars: %r is none of %s" % (var, tuple(DENSITY_FILES)))
+    acf_vars, density_vars = _draw_vars("acf_vars", acf_vars), _draw_vars("density_vars", density_vars)
     rawdata = np.asarray(rawdata, dtype=np.float64)
     opts = [estopt(rawdata, dates, sampleRange=range(1, int(e) + 1), endIndex=int(e), **kwargs) for e in endIndices]
     o0 = opts[0]
@@ -936,13 +936,9 @@ def calccorr(datadir, startyear=1980, endyear=2018, startmonth=1, endmonth=2, re
     else:
         if getattr(result, "corr", None) is None:
             raise ValueError("result carries no correlation matrices (estimatewindows(..., corr=True))")
-        by_date = {str(enddate(o)): w for w, o in enumerate(result.opts)}
         o0 = result.opts[0]
         names = corrnames(o0.D, o0.horizons)
-        for d in dates:
-            if d not in by_date:
-                raise ValueError("no window ends on %s" % d)
-            mats.append(result.corr[by_date[d]])
+        mats = [result.corr[w] for w in _rows_of(result, dates)]
     os.makedirs(datadir, exist_ok=True)
     path = write_corr_workbook(os.path.join(datadir, "correlations.xlsx"), dates, names, mats)
     return path, dates, names, mats
@@ -957,13 +953,45 @@ def _normcdf(z):
         return (erfc(-np.asarray(z, dtype=np.float64) / math.sqrt(2.0)).astype(np.float64)) / 2.0
 
 
+def _rows_of(result, dates):
+    """The window of a BatchResult that ends on each of `dates`."""
+    by_date = {str(enddate(o)): w for w, o in enumerate(result.opts)}
+    for d in dates:
+        if d not in by_date:
+            raise ValueError("no window ends on %s" % d)
+    return [by_date[d] for d in dates]
+
+
+def _cells(datadir, stem, date):
+    """One date's per-draw file `<stem>_<date>.csv` without its date column: (column names, cells (n, C))."""
+    header, rows = _read_csv(os.path.join(datadir, "%s_%s.csv" % (stem, date)))
+    return header[1:], np.array([[float(x) for x in r[1:]] for r in rows])
+
+
+def _mixture_cells(datadir, date, horizons):
+    """means, vars_, pis (n, K) and, with a horizon > 0, trans (n, K * K) of one date: the files the mixture statistics read."""
+    means, vars_, pis = (_cells(datadir, stem, date)[1] for stem in ("filtered_means", "filtered_variances", "filtered_state_probs"))
+    return means, vars_, pis, (_cells(datadir, "filtered_trans_probs", date)[1] if any(h > 0 for h in horizons) else None)
+
+
+def _omega(pis, trans, h):
+    """pis * A^h per draw: pis (n, K), trans (n, K * K) in the file's column order (trans_i_j, i fastest; not read at h = 0).
+    One product at a time with i ascending, the library's expression (HMCG_OMEGA_STEP), so the file routes keep its bits."""
+    n, K = pis.shape
+    w = np.array(pis, dtype=np.float64)
+    if h > 0:
+        A = trans.reshape(n, K, K).transpose(0, 2, 1)                                       # A[d, i, j]
+    for _ in range(h):
+        nw = w[:, 0, None] * A[:, 0, :]
+        for i in range(1, K):
+            nw = nw + w[:, i, None] * A[:, i, :]
+        w = nw
+    return w
+
+
 def _cdfs_from_files(datadir, date, ys, horizons):
     """One date's expectationsbar (n_h, G) from its per-draw files, as calc_cdfs.jl:33-41 computes it on the host."""
-    def cells(stem):
-        _, rows = _read_csv(os.path.join(datadir, "%s_%s.csv" % (stem, date)))
-        return np.array([[float(x) for x in r[1:]] for r in rows])
-    means, vars_, pis = cells("filtered_means"), cells("filtered_variances"), cells("filtered_state_probs")
-    trans = cells("filtered_trans_probs") if any(h > 0 for h in horizons) else None
+    means, vars_, pis, trans = _mixture_cells(datadir, date, horizons)
     return _cdfs_from_cells(means, vars_, pis, trans, ys, horizons)
 
 
@@ -973,15 +1001,9 @@ def _cdfs_from_cells(means, vars_, pis, trans, ys, horizons):
     with np.errstate(invalid="ignore", divide="ignore"):
         z = (ys[None, :, None] - means[:, None, :]) / np.sqrt(vars_)[:, None, :]           # (n, G, K)
     phi = _normcdf(z)
-    A = None if trans is None else trans.reshape(n, K, K).transpose(0, 2, 1)               # columns trans_i_j, i fastest -> A[d, i, j]
     out = np.empty((len(horizons), len(ys)))
     for j, h in enumerate(horizons):
-        w = pis.copy()
-        for _ in range(h):                                                                  # S0 * A^h, one product at a time
-            nw = w[:, 0, None] * A[:, 0, :]
-            for i in range(1, K):
-                nw = nw + w[:, i, None] * A[:, i, :]
-            w = nw
+        w = _omega(pis, trans, h)                                                           # S0 * A^h
         f = w[:, None, 0] * phi[:, :, 0]
         for k in range(1, K):
             f = f + w[:, None, k] * phi[:, :, k]
@@ -1027,11 +1049,7 @@ def calccdfs(datadir, dates, ys=np.arange(-5, 15.25, .25), horizons=(0,), result
             raise ValueError("result carries no predictive CDFs (estimatewindows(..., cdf_grid=ys))")
         if not np.array_equal(result.cdf_grid, ys) or tuple(result.cdf_horizons) != horizons:
             raise ValueError("result was computed on another grid or other horizons")
-        by_date = {str(enddate(o)): w for w, o in enumerate(result.opts)}
-        for d in dates:
-            if d not in by_date:
-                raise ValueError("no window ends on %s" % d)
-        bar = np.array([result.cdf[by_date[d]] for d in dates]).reshape(len(dates), len(horizons), len(ys))
+        bar = np.array([result.cdf[w] for w in _rows_of(result, dates)]).reshape(len(dates), len(horizons), len(ys))
     return dates, ys, bar, finverse(bar)
 
 
@@ -1053,14 +1071,7 @@ def _bias_from_cells(means, states, trans, ferr, horizon):
     column order (trans_i_j, i fastest), ferr (n,) the forecast_error column of the first horizon or None.  Returns
     (uncbias, totalbias, mean (2K,), cov (2K, 2K)), the last two in the order futstate | means."""
     n, K = means.shape
-    fut = np.array(states, dtype=np.float64)
-    if horizon > 0:
-        A = trans.reshape(n, K, K).transpose(0, 2, 1)                                       # A[d, i, j]
-        for _ in range(horizon):                                                            # states' * A^h, one product at a time
-            nw = fut[:, 0, None] * A[:, 0, :]
-            for i in range(1, K):
-                nw = nw + fut[:, i, None] * A[:, i, :]
-            fut = nw
+    fut = _omega(states, trans, horizon)                                                    # states' * A^h
     v = np.hstack([fut, means])
     with np.errstate(invalid="ignore", divide="ignore"):
         mean = v.mean(axis=0)
@@ -1073,12 +1084,8 @@ def _bias_from_cells(means, states, trans, ferr, horizon):
 
 
 def _bias_from_files(datadir, date, horizon):
-    def cells(stem):
-        _, rows = _read_csv(os.path.join(datadir, "%s_%s.csv" % (stem, date)))
-        return np.array([[float(x) for x in r[1:]] for r in rows])
-    means, states = cells("filtered_means"), cells("filtered_state_probs")
-    trans = cells("filtered_trans_probs")
-    fc = cells("forecasts")
+    means, states, trans, fc = (_cells(datadir, stem, date)[1]
+                                for stem in ("filtered_means", "filtered_state_probs", "filtered_trans_probs", "forecasts"))
     return _bias_from_cells(means, states, trans, fc[:, 1], horizon)                        # forecasts[:, 3]: date, forecast, error
 
 
@@ -1105,11 +1112,7 @@ def calcbias(datadir, dates, horizon=12, result=None):
             raise ValueError("result carries no bias moments (estimatewindows(..., bias_horizon=h))")
         if b.horizon != horizon:
             raise ValueError("result was computed for another horizon")
-        by_date = {str(enddate(o)): w for w, o in enumerate(result.opts)}
-        for d in dates:
-            if d not in by_date:
-                raise ValueError("no window ends on %s" % d)
-        idx = [by_date[d] for d in dates]
+        idx = _rows_of(result, dates)
         unc, tot, mean, cov = b.uncerbias[idx], b.totalbias[idx], b.mean[idx], b.cov[idx]
     return dates, unc, tot, mean, cov
 
@@ -1129,15 +1132,9 @@ def _moments_from_cells(means, vars_, pis, trans, horizons):
     file's column order.  The library's algebra in numpy: per-draw closed-form moments about the pivot c = the mixture mean of
     draw 0, summed over the draws."""
     n, K = means.shape
-    A = None if trans is None else trans.reshape(n, K, K).transpose(0, 2, 1)               # columns trans_i_j, i fastest -> A[d, i, j]
     out = np.empty((len(horizons), _lib.MIX_STRIDE))
     for j, h in enumerate(horizons):
-        w = pis.copy()
-        for _ in range(h):                                                                  # pi_end * A^h, one product at a time
-            nw = w[:, 0, None] * A[:, 0, :]
-            for i in range(1, K):
-                nw = nw + w[:, i, None] * A[:, i, :]
-            w = nw
+        w = _omega(pis, trans, h)                                                           # pi_end * A^h
         with np.errstate(invalid="ignore", divide="ignore"):
             s = w.sum(axis=1)
             c = (w[0] * means[0]).sum() / s[0]
@@ -1159,12 +1156,7 @@ def _moments_from_cells(means, vars_, pis, trans, horizons):
 
 
 def _moments_from_files(datadir, date, horizons):
-    def cells(stem):
-        _, rows = _read_csv(os.path.join(datadir, "%s_%s.csv" % (stem, date)))
-        return np.array([[float(x) for x in r[1:]] for r in rows])
-    means, vars_, pis = cells("filtered_means"), cells("filtered_variances"), cells("filtered_state_probs")
-    trans = cells("filtered_trans_probs") if any(h > 0 for h in horizons) else None
-    return _moments_from_cells(means, vars_, pis, trans, horizons)
+    return _moments_from_cells(*_mixture_cells(datadir, date, horizons), horizons)
 
 
 def calcmoments(datadir, dates, horizons=(0,), result=None):
@@ -1189,11 +1181,7 @@ def calcmoments(datadir, dates, horizons=(0,), result=None):
         raise ValueError("result carries no mixture moments (estimatewindows(..., moment_horizons=hs))")
     if m.horizons != horizons:
         raise ValueError("result was computed for other horizons")
-    by_date = {str(enddate(o)): w for w, o in enumerate(result.opts)}
-    for d in dates:
-        if d not in by_date:
-            raise ValueError("no window ends on %s" % d)
-    idx = [by_date[d] for d in dates]
+    idx = _rows_of(result, dates)
     return dates, {name: getattr(m, name)[idx] for name in _lib.MIX_FIELDS}
 
 
@@ -1331,16 +1319,10 @@ def calcchain(datadir, dates, var="mu", cuts=None, bins=64, lo_hi=None, trace=(0
         if (cuts is not None and tuple(int(c) for c in cuts) != d.cuts) or int(bins) != d.bins or \
                 (int(trace[0]), int(trace[1])) != (d.trace.shape[2], d.trace_stride):
             raise ValueError("result was computed for other cuts, bins or trace")
-        by_date = {str(enddate(o)): w for w, o in enumerate(result.opts)}
-        for x in dates:
-            if x not in by_date:
-                raise ValueError("no window ends on %s" % x)
-        return dates, d.rows([by_date[x] for x in dates])
+        return dates, d.rows(_rows_of(result, dates))
     parts, columns, used = [], None, None
     for i, date in enumerate(dates):
-        header, rows = _read_csv(os.path.join(datadir, "%s_%s.csv" % (DENSITY_FILES[var], date)))
-        cells = np.array([[float(x) for x in r[1:]] for r in rows])
-        columns = header[1:]
+        columns, cells = _cells(datadir, DENSITY_FILES[var], date)
         ct = (cells.shape[0],) if cuts is None else tuple(int(c) for c in cuts)
         if used is not None and ct != used:
             raise ValueError("the dates' files differ in length: give cuts")
@@ -1536,16 +1518,10 @@ def calcess(datadir, dates, var="mu", lags=255, result=None):
         d = d[var]
         if int(lags) != d.lags:
             raise ValueError("result was computed for other lags")
-        by_date = {str(enddate(o)): w for w, o in enumerate(result.opts)}
-        for x in dates:
-            if x not in by_date:
-                raise ValueError("no window ends on %s" % x)
-        return dates, d.rows([by_date[x] for x in dates])
+        return dates, d.rows(_rows_of(result, dates))
     parts, columns = [], None
     for date in dates:
-        header, rows = _read_csv(os.path.join(datadir, "%s_%s.csv" % (DENSITY_FILES[var], date)))
-        cells = np.array([[float(x) for x in r[1:]] for r in rows])
-        columns = header[1:]
+        columns, cells = _cells(datadir, DENSITY_FILES[var], date)
         parts.append(_autocorr_from_cells(cells, lags))
     return dates, ChainAutocorr(var, columns, {k: np.array([q[k] for q in parts]) for k in ("acov",) + _lib.ACF_FIELDS})
 

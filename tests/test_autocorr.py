@@ -78,6 +78,32 @@ def test_misuse_is_refused_before_device_init(entry):
         _lib.chain_autocorr(np.zeros((1, 3, 4)), lags=4)
 
 
+# Two rules broken at once: the rule the entry names first, with its whole text.  The order is this feature's own; the texts of
+# the rules it shares with the other draw statistics come from csrc/stat_plan.hpp.
+DOUBLY_WRONG = [
+    (dict(struct_size=7, W=0), b"hmcg_autocorr.struct_size 7 != %d" % C.sizeof(_lib.Autocorr)),
+    (dict(W=0, nd_ld=39), b"W = 0: at least one window"),
+    (dict(C=65, nd=0), b"C = 65 columns outside 1..64"),
+    (dict(nd=0, nd_ld=-1), b"nd = 0: at least one draw"),
+    (dict(nd=2 ** 53 + 1, nd_ld=4), b"nd = 9007199254740993 exceeds 2^53, the largest exact divisor"),
+    (dict(nd_ld=39, L=-1), b"nd_ld = 39 < nd = 40"),
+    (dict(L=40, W=2 ** 29, C=64), b"L = 40 exceeds nd - 1 = 39"),
+]
+
+
+@pytest.mark.parametrize("fields, message", DOUBLY_WRONG)
+@pytest.mark.parametrize("entry", ["hmcg_chain_autocorr", "hmcg_chain_autocorr_device"])
+def test_first_rule_named_for_a_doubly_wrong_call(entry, fields, message):
+    lib = hmc_jl_amd.load()
+    buf = np.zeros(64)
+    ok = C.c_void_p(buf.ctypes.data)
+    p = _lib.make_autocorr(1, 3, 40, 40, 7)
+    for k, v in fields.items():
+        setattr(p, k, v)
+    rc = getattr(lib, entry)(C.byref(p), ok, ok, ok, *(([None] if entry.endswith("device") else []) + [None]))
+    assert rc == -1 and lib.hmcg_last_error() == message
+
+
 PLAN_MAIN = r"""
 #include <cstdio>
 #include "%s"

@@ -105,6 +105,35 @@ def test_misuse_is_refused_before_device_init(entry):
         _lib.make_density(1, 3, 40, 40, tuple(range(1, 10)))
 
 
+# Two rules broken at once: the rule the entry names first, with its whole text.  The order is this feature's own (B stands
+# between C and nd); the texts of the rules it shares with the other draw statistics come from csrc/stat_plan.hpp.
+DOUBLY_WRONG = [
+    (dict(struct_size=7, W=0), b"hmcg_density.struct_size 7 != %d" % C.sizeof(_lib.Density)),
+    (dict(W=0, nd_ld=3), b"W = 0: at least one window"),
+    (dict(C=0, nd=0), b"C = 0 columns outside 1..64"),
+    (dict(B=0, nd=0), b"B = 0 bins outside 1..512"),
+    (dict(nd=0, nd_ld=-1), b"nd = 0: at least one draw"),
+    (dict(nd=2 ** 53 + 1, nd_ld=4), b"nd = 9007199254740993 exceeds 2^53, the largest exact divisor"),
+    (dict(nd_ld=3, n_cuts=0), b"nd_ld = 3 < nd = 4"),
+    (dict(W=2 ** 29, C=64, trace_len=0), b"W * C exceeds one launch (2^31 - 1 blocks)"),
+]
+
+
+@pytest.mark.parametrize("fields, message", DOUBLY_WRONG)
+@pytest.mark.parametrize("entry", ["hmcg_chain_density", "hmcg_chain_density_device"])
+def test_first_rule_named_for_a_doubly_wrong_call(entry, fields, message):
+    lib = hmc_jl_amd.load()
+    buf = np.zeros(64)
+    ok = C.c_void_p(buf.ctypes.data)
+    p = _lib.make_density(1, 3, 4, 4, (3, 4), 8, (1, 2))
+    for k, v in fields.items():
+        setattr(p, k, v)
+    trace = None if fields.get("trace_len") == 0 else ok       # ... and with trace_len = 0 the missing x, were it reached
+    rc = getattr(lib, entry)(C.byref(p), None if trace is None else ok, None, ok, ok, ok, trace,
+                             *(([None] if entry.endswith("device") else []) + [None]))
+    assert rc == -1 and lib.hmcg_last_error() == message
+
+
 PLAN_MAIN = r"""
 #include <cstdio>
 #include <cstdlib>

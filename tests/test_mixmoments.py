@@ -75,6 +75,34 @@ def test_misuse_is_refused_before_device_init(entry):
         _lib.make_mixmom(1, 3, 4, 4, tuple(range(9)))
 
 
+# Two rules broken at once: the rule the entry names first, with its whole text.  The order is this feature's own (the horizons
+# stand between K and nd); the texts of the rules it shares with the other draw statistics come from csrc/stat_plan.hpp.
+DOUBLY_WRONG = [
+    (dict(struct_size=7, W=0), b"hmcg_mixmom.struct_size 7 != %d" % C.sizeof(_lib.MixMom)),
+    (dict(W=0, nd_ld=3), b"W = 0: at least one window"),
+    (dict(K=9, nd=0), b"K = 9 outside 2..8"),
+    (dict(n_h=9, nd_ld=3), b"n_h = 9 horizons outside 1..8"),
+    (dict(h1=-1, nd=0), b"horizon -1 outside 0..1024"),
+    (dict(nd=0, nd_ld=-1), b"nd = 0: at least one draw"),
+]
+
+
+@pytest.mark.parametrize("fields, message", DOUBLY_WRONG)
+@pytest.mark.parametrize("entry", ["hmcg_mixture_moments", "hmcg_mixture_moments_device"])
+def test_first_rule_named_for_a_doubly_wrong_call(entry, fields, message):
+    lib = hmc_jl_amd.load()
+    buf = np.zeros(64)
+    ok = C.c_void_p(buf.ctypes.data)
+    p = _lib.make_mixmom(1, 3, 4, 4, (0, 12))
+    for k, v in fields.items():
+        if k == "h1":
+            p.horizons[1] = v
+        else:
+            setattr(p, k, v)
+    rc = getattr(lib, entry)(C.byref(p), ok, ok, ok, ok, ok, *(([None] if entry.endswith("device") else []) + [None]))
+    assert rc == -1 and lib.hmcg_last_error() == message
+
+
 PLAN_MAIN = r"""
 #include <cstdio>
 #include "%s"

@@ -1,6 +1,6 @@
 """Predictive CDFs of the regime mixture (hmcg_predictive_cdf, calc_cdfs.jl): the parts that need no GPU -- the struct and the
-argument rules of the built library (checked before device init), the slab / chunk cut of csrc/predictive_plan.hpp run by a
-g++-compiled program, and the host-side file route of hmc.calccdfs against the direct formula."""
+argument rules of the built library (checked before device init), the slab / chunk cut of csrc/stat_plan.hpp (through
+predictive_plan.hpp) run by a g++-compiled program, and the host-side file route of hmc.calccdfs against the direct formula."""
 import ctypes as C
 import datetime as dt
 import math
@@ -70,6 +70,36 @@ def test_misuse_is_refused_before_device_init(entry):
         assert rc == -1 and text in lib.hmcg_last_error(), (fields, ptrs, rc, lib.hmcg_last_error())
 
 
+# Two rules broken at once: the rule the entry names first, with its whole text.  The order is this feature's own (G and the
+# horizons stand between K and nd); the texts of the rules it shares with the other draw statistics come from csrc/stat_plan.hpp.
+DOUBLY_WRONG = [
+    (dict(struct_size=7, W=0), b"hmcg_predictive.struct_size 7 != %d" % C.sizeof(_lib.Predictive)),
+    (dict(W=0, nd_ld=3), b"W = 0: at least one window"),
+    (dict(K=9, nd=0), b"K = 9 outside 2..8"),
+    (dict(G=0, nd=0), b"G = 0 grid points outside 1..4096"),
+    (dict(n_h=0, nd=0), b"n_h = 0 horizons outside 1..8"),
+    (dict(h0=-1, nd_ld=3), b"horizon -1 outside 0..1024"),
+    (dict(nd=0, nd_ld=-1), b"nd = 0: at least one draw"),
+    (dict(nd_ld=3, h0=2), b"nd_ld = 3 < nd = 4"),
+]
+
+
+@pytest.mark.parametrize("fields, message", DOUBLY_WRONG)
+@pytest.mark.parametrize("entry", ["hmcg_predictive_cdf", "hmcg_predictive_cdf_device"])
+def test_first_rule_named_for_a_doubly_wrong_call(entry, fields, message):
+    lib = hmc_jl_amd.load()
+    buf = np.zeros(64)
+    ok = C.c_void_p(buf.ctypes.data)
+    p = _lib.make_predictive(1, 3, 4, 4, 2, (0,))
+    for k, v in fields.items():
+        if k == "h0":
+            p.horizons[0] = v
+        else:
+            setattr(p, k, v)
+    rc = getattr(lib, entry)(C.byref(p), ok, ok, ok, None, ok, ok, *(([None] if entry.endswith("device") else []) + [None]))
+    assert rc == -1 and lib.hmcg_last_error() == message
+
+
 def test_host_entry_refuses_a_non_finite_grid():
     lib = hmc_jl_amd.load()
     buf = np.zeros(64)
@@ -109,9 +139,9 @@ int main(int argc, char** argv)
 
 
 def test_slab_and_chunk_layout(tmp_path):
-    """csrc/predictive_plan.hpp, compiled by g++ into a stand-alone program: chunks are whole slabs (the last one ends at nd),
-    start on slab boundaries and cover [0, nd) exactly once, for draw counts around the slab size and caps that are no slab
-    multiple; the cap is rounded UP to whole slabs."""
+    """csrc/predictive_plan.hpp and the cut it takes from stat_plan.hpp, compiled by g++ into a stand-alone program: chunks are
+    whole slabs (the last one ends at nd), start on slab boundaries and cover [0, nd) exactly once, for draw counts around the
+    slab size and caps that are no slab multiple; the cap is rounded UP to whole slabs."""
     S = _lib.PRED_SLAB
     src = tmp_path / "plan_main.cpp"
     src.write_text(PLAN_MAIN % os.path.join(ROOT, "hmc.jl_amd", "csrc", "predictive_plan.hpp"))
