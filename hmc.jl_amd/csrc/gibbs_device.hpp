@@ -915,9 +915,15 @@ __device__ __forceinline__ void sort_order(const double (&mu)[K], int (&order)[K
     }
 // ... and, from its log lg = log(1 - uraw) and the block's second half, what it leaves in rb (live: the task exists): Box-Muller
 // for the normals; rho ~ Dirichlet(ones(K)) (:350-356) is K exponentials normalised in element order (lanes 0..K-1 of pass 0)
-#define HMCG_PREP_TASK_FINISH(task_, r2_, r3_)                                                   \
+// (in two halves, for the rows that put a barrier between them: the value a normal task leaves, then the normalisation and
+//  the stores; val crosses the cut in a register)
+#define HMCG_PREP_TASK_VALUE(r2_, r3_)                                                           \
     double val = lg;                                                                             \
-    if (t_gx || t_z) val = sqrt_fast(-2.0 * lg) * cos2pi_fast(u53(r2_, r3_));                    \
+    if (t_gx || t_z) val = sqrt_fast(-2.0 * lg) * cos2pi_fast(u53(r2_, r3_))
+#define HMCG_PREP_TASK_FINISH(task_, r2_, r3_)                                                   \
+    HMCG_PREP_TASK_VALUE(r2_, r3_);                                                              \
+    HMCG_PREP_TASK_STORE(task_)
+#define HMCG_PREP_TASK_STORE(task_)                                                              \
     double rs = 0.0;                                                                             \
     _Pragma("unroll") for (int i = 0; i < K; ++i) rs += -__shfl(lg, i, 64);                      \
     if (live) {                                                                                  \
@@ -1423,6 +1429,14 @@ void gibbs_sweeps_kernel(const KernelParams p)
     // the draw behind Bd by every thread from sh.ulast / th.pi_end: the owner's form cost some of them a spilled VGPR or
     // scratch bytes (profiles/r08/isa_lint_tables_every_row.txt).
     constexpr bool OWNER_DRAW = K == 2 || (K == 3 && L <= 4 && !SIG && !SMOOTH);
+    // The six-barrier helper rows among them take X[T-1] out of the map phase altogether: nobody draws it ahead of Bd.  The
+    // maps of step T-1 and of the padded slots are the identity, so a thread's composed suffix is g_{t0+L} o ... o g_{T-2};
+    // helper DRAW_WAVE, idle between Bd and Be, draws the state from LDS (th.mu, th.pi_end, the step's uniform: the owner's
+    // statements in the owner's order) and stores sh.x_end ahead of Be; behind Be the own waves read it beside wmap[] and
+    // start the apply from it.  Every X, count and sum is the value the owner's form computed.
+    constexpr bool HELPER_DRAW = SPLIT && OWNER_DRAW;
+    constexpr int DRAW_WAVE = OUT_WAVE;
+    (void)HELPER_DRAW; (void)DRAW_WAVE;
     // SPLIT takes the statistics in two parts: the integer counts (all that the gamma and Dirichlet draws need:
     // publish_counts) and the pivoted sums (which enter the sig2 / mu draws only: publish_sums) -- the two halves of
     // publish; every other flavour takes both at once.  The COUNTS half always describes the calling wave's OWN steps (it
@@ -1725,6 +1739,36 @@ void gibbs_sweeps_kernel(const KernelParams p)
                             HMCG_PREP_TASK_FINISH(task, pr2[ps], pr3[ps]);
                         }
                     };
+                    // HELPER_DRAW: the tail cut once more, at Bd -- Box-Muller ahead of it, the rho normalisation and the stores
+                    // behind it (val joins uraw and lg in registers): the own waves no longer wait for wave NW - 1's draw of
+                    // X[T-1] at Bd, so the whole tail would be the last arrival there, and between Bd and Be this wave has
+                    // nothing else to do.  rb[(sweep + 1) & 1] is read next at sweep + 1's Ba.  (The cut just ahead of the stores,
+                    // with the draw's sort order and uniform fetched ahead of Bd, has the better barrier profile and no better
+                    // bench line: profiles/r11.)
+                    double pval[NPASS];
+                    auto prep_mid = [&]() __attribute__((always_inline)) {
+#pragma unroll
+                        for (int ps = 0; ps < NPASS; ++ps) {
+                            const int task = ps * 64 + lane;
+                            HMCG_PREP_TASK_KIND(task);
+                            (void)t_gl; (void)role; (void)j;
+                            const double lg = plg[ps];
+                            HMCG_PREP_TASK_VALUE(pr2[ps], pr3[ps]);
+                            pval[ps] = val;
+                        }
+                    };
+                    auto prep_end = [&](int sw) __attribute__((always_inline)) {
+                        RngBuf<K>& rb = sh.rb[sw & 1];
+#pragma unroll
+                        for (int ps = 0; ps < NPASS; ++ps) {
+                            const int task = ps * 64 + lane;
+                            const bool live = task < NTASK;
+                            HMCG_PREP_TASK_KIND(task);
+                            const double uraw = puraw[ps], lg = plg[ps], val = pval[ps];
+                            HMCG_PREP_TASK_STORE(task);
+                        }
+                    };
+                    (void)pval; (void)prep_mid; (void)prep_end;
                     // The deal over the windows: the head of the preparation between Bb and Bc, where the
                     // window's own waves are VALU-bound and a younger wave gets what they leave (measured unstamped: the whole
                     // job there made all eight waves wait for helper NW + 1 at Bc); its tail between Bc and Bd, where that
@@ -1738,8 +1782,41 @@ void gibbs_sweeps_kernel(const KernelParams p)
                     if (!first) job_outputs(sweep - 1);                      // the previous sweep's outputs and forecasts (see below)
                     STAMP(14);
                     SWEEP_BARRIER(3);                                      // Bc
-                    if (more && wave == PREP_WAVE) prep_tail(sweep + 1);
+                    if constexpr (HELPER_DRAW) {
+                        if (more && wave == PREP_WAVE) prep_mid();
+                    } else {
+                        if (more && wave == PREP_WAVE) prep_tail(sweep + 1);
+                    }
                     SWEEP_BARRIER(4);                                      // Bd
+                    if constexpr (HELPER_DRAW) {
+                        if (more && wave == PREP_WAVE) prep_end(sweep + 1);
+                        // X[T-1] of this sweep (sorted labels, :464), by all 64 lanes alike: pif[T-1,:] stands in th.pi_end since
+                        // Bd, the state means since Bb, the step's uniform in this sweep's buffer since Bb.  One batch of reads,
+                        // one wait; then the statements of the owner's draw in their order.  Read behind Be by the own waves and
+                        // behind the next Ba and Ba2 by wave 0: a barrier either way.
+                        if (wave == DRAW_WAVE) {
+                            const ThetaBuf<K>& th = sh.th[sweep & 1];
+                            double hmu[K], hpf[K];
+#pragma unroll
+                            for (int s = 0; s < K; ++s) { hmu[s] = th.mu[s]; hpf[s] = th.pi_end[s]; }
+                            const double hu = ux_of(sweep)[T - 1];
+                            __builtin_amdgcn_s_waitcnt(0xC07F);      // lgkmcnt(0)
+                            __builtin_amdgcn_sched_barrier(0);
+                            int horder[K];
+                            sort_order<K>(hmu, horder);
+                            int xlast = 0;
+                            double cp = 0.0;
+#pragma unroll
+                            for (int q = 0; q < K - 1; ++q) {
+                                double pq = 0.0;
+#pragma unroll
+                                for (int s = 0; s < K; ++s) pq = (horder[q] == s) ? hpf[s] : pq;
+                                cp += pq;
+                                xlast += (cp <= hu) ? 1 : 0;
+                            }
+                            if (lane == 0) sh.x_end = xlast;
+                        }
+                    }
                     SWEEP_BARRIER(5);                                      // Be
                     STAMP(11);
                     continue;
@@ -2328,7 +2405,8 @@ void gibbs_sweeps_kernel(const KernelParams p)
         // Bd and by wave 0's next parameter phase (sh.x_end: read after Ba and Ba2, written here between Bc and Bd -- two
         // barriers either way; the store moved behind Bd, on every wave's path, measured slower).  Nobody reads LDS for it
         // behind Bd.  The rows without OWNER_DRAW publish the uniform instead, and every thread draws X[T-1] redundantly
-        // after the barrier.
+        // after the barrier.  The HELPER_DRAW rows publish pif[T-1,:] only: a helper wave draws behind Bd, off every own
+        // wave's path.
         int xlast = 0;
         if (tid == owner) {
 #pragma unroll
@@ -2336,7 +2414,9 @@ void gibbs_sweeps_kernel(const KernelParams p)
                 if (l == l_last) {
 #pragma unroll
                     for (int s = 0; s < K; ++s) th.pi_end[s] = pf[l][s];
-                    if constexpr (OWNER_DRAW) {
+                    if constexpr (HELPER_DRAW) {
+                        // (helper DRAW_WAVE draws X[T-1] from these behind Bd)
+                    } else if constexpr (OWNER_DRAW) {
                         double cp = 0.0;
 #pragma unroll
                         for (int q = 0; q < K - 1; ++q) {
@@ -2503,7 +2583,8 @@ void gibbs_sweeps_kernel(const KernelParams p)
                 m |= (uint32_t)idx << (8 * s);
             }
             if constexpr (K < 4) m |= BMAP_IDENTITY & (0xFFFFFFFFu << (8 * K));       // unused bytes: identity
-            m = (l == dlast) ? bmap_const(xlast) : (l > dlast ? (PADMARK ? bmap_const(XPAD) : BMAP_IDENTITY) : m);
+            if constexpr (HELPER_DRAW) m = (l >= dlast) ? BMAP_IDENTITY : m;     // step T-1 and the padding: X[T-1] passes through
+            else m = (l == dlast) ? bmap_const(xlast) : (l > dlast ? (PADMARK ? bmap_const(XPAD) : BMAP_IDENTITY) : m);
             gmap[l] = m;
             G = bmap_compose(m, G);      // G = g_{t0+l} o (g_{t0+l+1} o ...)
         }
@@ -2536,6 +2617,7 @@ void gibbs_sweeps_kernel(const KernelParams p)
             uint32_t wm[NW];
 #pragma unroll
             for (int ww = 1; ww < NW; ++ww) wm[ww] = sh.wmap[ww];
+            if constexpr (HELPER_DRAW) x_end = sh.x_end;  // X[T-1], drawn by helper DRAW_WAVE ahead of Be: one more read, same wait
             __builtin_amdgcn_s_waitcnt(0xC07F);          // lgkmcnt(0)
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
@@ -2546,13 +2628,15 @@ void gibbs_sweeps_kernel(const KernelParams p)
         }
         const uint32_t Hx = (uint32_t)dpp_i32<DPP_WAVE_SHL1, 0xF>((int)BMAP_IDENTITY, (int)Hm);   // lane 63: identity
         const uint32_t Sfx = bmap_compose(Hx, Rw);     // everything after this thread's chunk
-        int sin = bmap_apply(Sfx, XPAD);               // constant map below T-1; the identity (-> XPAD) for the last thread
-        xnext = sin;
+        // constant map below T-1; the identity (-> XPAD) for the last thread.  (HELPER_DRAW: the maps end at step T-2 and are
+        // applied to X[T-1]; the owner's thread and those behind it have no successor)
+        int sin = bmap_apply(Sfx, HELPER_DRAW ? x_end : XPAD);
+        xnext = (HELPER_DRAW && dlast < L) ? XPAD : sin;
         if constexpr (!OWNER_DRAW) x_end = xlast;
 #pragma unroll
         for (int l = L - 1; l >= 0; --l) {
             sin = bmap_apply(gmap[l], sin);      // (slots at or beyond T: XPAD when PADMARK, else a value that is never read)
-            x[l] = sin;
+            x[l] = (HELPER_DRAW && l > dlast) ? XPAD : sin;       // (HELPER_DRAW: slot dlast takes X[T-1] through the identity)
         }
         // pivots for the next sweep's one-pass statistics: this sweep's state means (X labels are unsorted)
 #pragma unroll
