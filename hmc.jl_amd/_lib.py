@@ -40,6 +40,10 @@ ACF_ROUND5 = 1
 ACF_MAXLAG = 1024               # HMCG_ACF_MAXLAG
 ACF_STRIDE = 8                  # HMCG_ACF_STRIDE: doubles per (window, column) of the diagnostics block
 ACF_FIELDS = ("mean", "variance", "tau", "ess", "mcse", "pairs", "truncated", "rhat")
+ORD_ROUND5 = 1                  # include/hmcg_order.h
+ORD_MAXQ = 16                   # HMCG_ORD_MAXQ: probabilities of one call
+ORD_STRIDE = 4                  # HMCG_ORD_STRIDE: doubles per (window, column, probability)
+ORD_FIELDS = ("value", "lo", "hi", "g")
 
 
 def bias_stride(K):
@@ -117,6 +121,17 @@ EXPORTS = ("hmcg_version", "hmcg_device_count", "hmcg_last_error", "hmcg_shutdow
            "hmcg_save_results_csv", "hmcg_write_table_csv", "hmcg_format_float") + tuple(
                "hmcg_" + s.stem + tail for s in STATS.values() for tail in ("", "_device"))
 
+
+# What the library gained after include/hmcg.h was closed (version 109) is declared in companion headers and listed in companion
+# tables: STATS and EXPORTS above mirror hmcg.h and stay as they are.  include/hmcg_order.h:
+class Quantiles(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("device", C.c_int32),
+                ("nd", C.c_int64), ("nd_ld", C.c_int64), ("Q", C.c_int32), ("flags", C.c_int32),
+                ("probs", C.c_double * ORD_MAXQ)]
+
+
+ORDER_EXPORTS = ("hmcg_chain_quantiles", "hmcg_chain_quantiles_device")
+
 _LIB = None
 
 
@@ -165,7 +180,7 @@ def load():
                             "this package has no CPU fallback" % SO_PATH)
         _share_torch_hip_runtime()
         L = C.CDLL(SO_PATH)
-        for name in EXPORTS:
+        for name in EXPORTS + ORDER_EXPORTS:
             getattr(L, name).restype = C.c_int
         L.hmcg_last_error.restype, L.hmcg_shutdown.restype = C.c_char_p, None
         _LIB = L
@@ -667,6 +682,53 @@ def chain_autocorr_device(acf, dx, dacov, ddiag, stream=None, timed=False):
     Enqueued on `stream` (None: the library's own).  Returns the Timing struct when timed (the call then waits for completion),
     else None."""
     return _device_call(load().hmcg_chain_autocorr_device, acf, (dx, dacov, ddiag), stream, timed)
+
+
+def make_quantiles(W, Cn, nd, nd_ld, probs, device=0, round5=True):
+    """hmcg_quantiles of a call over a draw array of Cn columns per window.  More than ORD_MAXQ probabilities raise here; every
+    other rule is the library's (HMCG_E_BADARG)."""
+    probs = tuple(float(q) for q in probs)
+    if len(probs) > ORD_MAXQ:
+        raise ValueError("at most %d probabilities" % ORD_MAXQ)
+    p = Quantiles()
+    p.struct_size = C.sizeof(Quantiles)
+    p.W, p.C, p.device, p.nd, p.nd_ld = int(W), int(Cn), int(device), int(nd), int(nd_ld)
+    p.Q, p.flags = len(probs), ORD_ROUND5 if round5 else 0
+    for i, q in enumerate(probs):
+        p.probs[i] = q
+    return p
+
+
+def unpack_chain_quantiles(q, n):
+    """The two output blocks of hmcg_chain_quantiles -- q (W, C, Q, 4), n (W, C, 2) int64 -- as a dict of (W, C, Q) arrays:
+    value (the quantile), lo and hi (the order statistics x_(j) and x_(min(j + 1, m - 1)) that bracket it, bit copies of
+    draws) and g (the weight of hi); plus count (W, C) int64, the m draws ranked, and nan (W, C) int64, the NaNs left out."""
+    q, n = np.asarray(q), np.asarray(n)
+    out = {name: q[..., i].copy() for i, name in enumerate(ORD_FIELDS)}
+    out["count"], out["nan"] = n[..., 0].astype(np.int64), n[..., 1].astype(np.int64)
+    return out
+
+
+def chain_quantiles(x, probs, nd=None, device=0, round5=True, timing=None):
+    """hmcg_chain_quantiles over ONE host (numpy) draw array in a C-ABI layout with the draw index last -- mu / sig2 / pi_end
+    (W, K, nd), A (W, K, K, nd), fcast (W, 2H, nd); every axis between the first and the last counts as columns -- over its
+    first nd draws (default: all).  Per window, column and probability p: the exact quantile (numpy's / Julia's default
+    definition) selected on the device, with the two draws that bracket it.  round5 (default): every value is first rounded to
+    5 digits, as the cells of the per-draw CSV files are.  Returns the dict of unpack_chain_quantiles, the column axis
+    flattened.  timing: a Timing to fill."""
+    x, W, Cn, nd, ld = _column_draws(x, nd)
+    p = make_quantiles(W, Cn, nd, ld, probs, device, round5)
+    q = np.zeros((W, Cn, max(p.Q, 0), ORD_STRIDE))
+    n = np.zeros((W, Cn, 2), dtype=np.int64)
+    _check(load().hmcg_chain_quantiles(C.byref(p), _np_ptr(x), _np_ptr(q), _np_ptr(n), _tm(timing)))
+    return unpack_chain_quantiles(q, n)
+
+
+def chain_quantiles_device(qs, dx, dq, dn, stream=None, timed=False):
+    """hmcg_chain_quantiles_device over raw device pointers (ints, e.g. torch tensor.data_ptr()); qs: make_quantiles(...).
+    Enqueued on `stream` (None: the library's own).  Returns the Timing struct when timed (the call then waits for completion),
+    else None."""
+    return _device_call(load().hmcg_chain_quantiles_device, qs, (dx, dq, dn), stream, timed)
 
 
 def format_float(x):

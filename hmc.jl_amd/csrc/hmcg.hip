@@ -38,6 +38,7 @@
 #include "mixmoments.hpp"
 #include "density.hpp"
 #include "autocorr.hpp"
+#include "order.hpp"
 
 namespace {
 
@@ -1457,6 +1458,96 @@ int acf_host(DeviceCtx& c, const hmcg_autocorr* p, const double* x, double* acov
     return ring.report({W, 256, 0}, (int)ring.uploads + 1);
 }
 
+// ---- exact quantiles and credible limits of the draws (order.hip; argument rules, key, digit schedule and the cut of the columns
+// into upload groups: order_plan.hpp; ABI: include/hmcg_order.h) ------------------------------------------------------------------
+
+hmcg_host::OrdArgs ord_args(const hmcg_quantiles* p)
+{
+    hmcg_host::OrdArgs a{};
+    a.nd = p->nd; a.Q = p->Q; a.round5 = (p->flags & HMCG_ORD_ROUND5) != 0;
+    for (int i = 0; i < HMCG_ORD_MAXQ; ++i) a.probs[i] = i < p->Q ? p->probs[i] : 0.0;
+    return a;
+}
+
+// The selection keeps everything in LDS: no work area, so nothing of the context is shared with an earlier call.
+int ord_device(DeviceCtx& c, const hmcg_quantiles* p, const double* dx, double* dq, int64_t* dn, hipStream_t stream, hmcg_timing* timing)
+{
+    Arena none;
+    return stat_device(c, none, 0, stream, timing, {p->W, 1024, ord_lds_bytes()}, 1, [&]() -> int {
+        hmcg_host::OrdArgs a = ord_args(p);
+        a.x = dx; a.q = dq; a.n = dn; a.ncols = (long long)p->W * p->C; a.ld = p->nd_ld;
+        HIP_TRY(launch_chain_quantiles(a, stream));
+        return 0;
+    });
+}
+
+// Host entry on one device.  A selection needs its whole column resident, so this is not the draw-slab ring: the W * C columns
+// go up in groups of whole columns (order_plan.hpp), packed with leading dimension nd into pinned staging, copied on the copy
+// stream and selected on the compute stream, RING buffers deep: group g + 1 is packed and copied while group g's kernel runs.
+// Every group writes its own rows of q and n, fetched once at the end.
+int ord_host(DeviceCtx& c, const hmcg_quantiles* p, const double* x, double* q, int64_t* n, hmcg_timing* timing)
+{
+    const auto t_call = std::chrono::steady_clock::now();
+    const long long wc = (long long)p->W * p->C;
+    const size_t nd = (size_t)p->nd, ld = (size_t)p->nd_ld;
+    long long cap = 0;
+    if (const char* cenv = diag_env("HMCG_CHUNK_COLS")) cap = atoll(cenv);
+    const std::vector<OrdGroup> groups = ord_groups(wc, ord_group_cols(p->nd, wc, cap));
+    const int nbuf = (int)std::min<size_t>(RING, groups.size());
+    const size_t b_q = sizeof(double) * (size_t)wc * (size_t)p->Q * HMCG_ORD_STRIDE, b_n = sizeof(int64_t) * (size_t)wc * 2;
+    Layout d, h;
+    const size_t o_q = d.add(b_q), o_n = d.add(b_n);
+    h.add(b_q); h.add(b_n);
+    size_t o_d[RING] = {}, o_p[RING] = {};
+    const size_t b_group = sizeof(double) * (size_t)groups[0].n * nd;
+    for (int b = 0; b < nbuf; ++b) { o_d[b] = d.add(b_group); o_p[b] = h.add(b_group); }
+    if (c.dev.ensure(d.total) || c.pin.ensure(h.total)) {
+        set_err("workspace allocation failed (%zu B device, %zu B pinned)", d.total, h.total);
+        return HMCG_E_NOMEM;
+    }
+    Events tev;
+    hmcg_host::OrdArgs a = ord_args(p);
+    a.ld = p->nd;
+    size_t up = 0;
+    for (const OrdGroup& g : groups) {
+        const int b = (int)(up % (size_t)nbuf);
+        if (up >= (size_t)nbuf) HIP_TRY(hipEventSynchronize(c.evk[b]));          // the kernel that read this buffer pair is done
+        ++up;
+        double* pb = reinterpret_cast<double*>(c.pin.base + o_p[b]);
+        double* db = reinterpret_cast<double*>(c.dev.base + o_d[b]);
+        pack_columns(x + (size_t)g.c0 * ld, (size_t)g.n, ld, 0, nd, pb);
+        HIP_TRY(hipMemcpyAsync(db, pb, sizeof(double) * (size_t)g.n * nd, hipMemcpyHostToDevice, c.copy));
+        HIP_TRY(hipEventRecord(c.evc[b], c.copy));
+        HIP_TRY(hipStreamWaitEvent(c.stream, c.evc[b], 0));
+        hipEvent_t e[2] = {};
+        if (timing) {
+            for (hipEvent_t& ev : e) { HIP_TRY(hipEventCreate(&ev)); tev.ev.push_back(ev); }
+            HIP_TRY(hipEventRecord(e[0], c.stream));
+        }
+        a.x = db; a.ncols = g.n;
+        a.q = reinterpret_cast<double*>(c.dev.base + o_q) + (size_t)g.c0 * (size_t)p->Q * HMCG_ORD_STRIDE;
+        a.n = reinterpret_cast<int64_t*>(c.dev.base + o_n) + (size_t)g.c0 * 2;
+        HIP_TRY(launch_chain_quantiles(a, c.stream));
+        if (timing) HIP_TRY(hipEventRecord(e[1], c.stream));
+        HIP_TRY(hipEventRecord(c.evk[b], c.stream));
+    }
+    HIP_TRY(hipMemcpyAsync(c.pin.base + o_q, c.dev.base + o_q, o_n + b_n - o_q, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    memcpy(q, c.pin.base + o_q, b_q);
+    memcpy(n, c.pin.base + o_n, b_n);
+    if (timing) {
+        double kernel_ms = 0.0;
+        for (size_t i = 0; i + 1 < tev.ev.size(); i += 2) {
+            float ms = 0.f;
+            HIP_TRY(hipEventElapsedTime(&ms, tev.ev[i], tev.ev[i + 1]));
+            kernel_ms += ms;
+        }
+        const double call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+        fill_stat_timing(timing, c, {p->W, 1024, ord_lds_bytes()}, kernel_ms, (int)up, call_ms);
+    }
+    return 0;
+}
+
 // The prologue of a compute entry on one device.  The argument check comes first and needs no device: a caller on a machine
 // without one still gets the argument errors.  Then the context of p->device, its lock, the device made current, and body(context).
 template <class P, class Check, class Body>
@@ -1641,6 +1732,18 @@ int hmcg_chain_autocorr(const hmcg_autocorr* p, const double* x, double* acov, d
 {
     return entry(p, [&](char* msg, size_t n) { return check_autocorr(p, x, acov, diag, msg, n); },
                  [&](DeviceCtx& c) { return acf_host(c, p, x, acov, diag, timing); });
+}
+
+int hmcg_chain_quantiles_device(const hmcg_quantiles* p, const double* dx, double* dq, int64_t* dn, void* stream, hmcg_timing* timing)
+{
+    return entry(p, [&](char* msg, size_t n) { return check_quantiles(p, dx, dq, dn, msg, n); },
+                 [&](DeviceCtx& c) { return ord_device(c, p, dx, dq, dn, stream ? (hipStream_t)stream : c.stream, timing); });
+}
+
+int hmcg_chain_quantiles(const hmcg_quantiles* p, const double* x, double* q, int64_t* n, hmcg_timing* timing)
+{
+    return entry(p, [&](char* msg, size_t nmsg) { return check_quantiles(p, x, q, n, msg, nmsg); },
+                 [&](DeviceCtx& c) { return ord_host(c, p, x, q, n, timing); });
 }
 
 }  // extern "C"

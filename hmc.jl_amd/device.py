@@ -184,6 +184,21 @@ class DevicePanel:
         tm = _lib.chain_autocorr_device(acf, x.data_ptr(), out["acov"].data_ptr(), out["diag"].data_ptr(), None, timed)
         return self._done(tm, timed, out)
 
+    def chain_quantiles(self, var="mu", probs=(0.05, 0.5, 0.95), timed=False, round5=True):
+        """Exact quantiles of one variable's draws from the panel's own HBM draws (hmcg_chain_quantiles_device): a selection on
+        the device, no draw leaves it.  var: "mu", "sig2", "pi_end" (C = K columns), "A" (C = K * K) or "fcast" (C = 2H); probs:
+        at most 16 probabilities in [0, 1].  Returns a dict of tensors: q (W, C, Q, 4) = value, lo, hi, g per probability and
+        n (W, C, 2) int64 = the draws ranked and the NaNs; _lib.unpack_chain_quantiles names the parts of their numpy copies.
+        Enqueued on the library stream behind `run`; with timed=True the call waits and last_timing holds the HIP-event time,
+        otherwise call sync() before reading the tensors."""
+        x, Cn = self._draws("chain_quantiles", var)
+        torch = self.torch
+        qs = _lib.make_quantiles(self.W, Cn, self.nrun, self.nrun, probs, self.device_index, round5)
+        out = {"q": torch.empty((self.W, Cn, qs.Q, _lib.ORD_STRIDE), dtype=torch.float64, device=self.dev),
+               "n": torch.empty((self.W, Cn, 2), dtype=torch.int64, device=self.dev)}
+        tm = _lib.chain_quantiles_device(qs, x.data_ptr(), out["q"].data_ptr(), out["n"].data_ptr(), None, timed)
+        return self._done(tm, timed, out)
+
     def sync(self):
         """Wait for the library stream (untimed runs are asynchronous)."""
         self.torch.cuda.synchronize(self.dev)

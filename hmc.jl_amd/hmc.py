@@ -22,6 +22,8 @@ ABI.  Names, argument meaning and result layout follow the reference:
                         nested prefixes and the running mean (from the files or from the device); chainquantiles, chaindensity
     calcess             no reference script: autocovariances, integrated autocorrelation time, effective sample size, Monte-Carlo
                         standard error and split-R-hat of the draws (from the files or from the device); write_chain_ess
+    calcquantiles       no reference script: exact quantiles (median, credible limits) of the draws by selection (from the files
+                        or from the device); write_chain_quantiles
 
 New (the reference batches by launching one SLURM task per window,
 slurmscripts/base_estimation.sh:5): `estimatewindows`, one call for many windows.
@@ -408,6 +410,22 @@ class ChainAutocorr:
         return ChainAutocorr(self.var, self.columns, {k: getattr(self, k)[idx] for k in ("acov",) + _lib.ACF_FIELDS})
 
 
+class ChainQuantiles:
+    """Exact quantiles of one variable's draws over n windows (end dates), C columns and Q probabilities: value (n, C, Q) the
+    quantile at probs[i] (numpy's / Julia's default definition), lo and hi (n, C, Q) the two draws that bracket it, g their
+    weight (value = lo + g (hi - lo)); count and nan (n, C) int64 the draws ranked and the NaNs left out; columns: the C column
+    names of the per-draw file."""
+
+    def __init__(self, var, columns, probs, parts):
+        self.var, self.columns, self.probs = var, list(columns), tuple(float(p) for p in probs)
+        for name in _lib.ORD_FIELDS + ("count", "nan"):
+            setattr(self, name, parts[name])
+
+    def rows(self, idx):
+        """The same object restricted to the windows idx."""
+        return ChainQuantiles(self.var, self.columns, self.probs, {k: getattr(self, k)[idx] for k in _lib.ORD_FIELDS + ("count", "nan")})
+
+
 class BatchResult:
     """Result of estimatewindows: per-window posterior summaries (+ optional draws)."""
 
@@ -424,6 +442,7 @@ class BatchResult:
         self.moments = res.get("moments")      # with moment_horizons: MixtureMoments, (W, n_h) arrays
         self.density = res.get("density")      # with density_vars: {var: ChainDensity}
         self.autocorr = res.get("autocorr")    # with acf_vars: {var: ChainAutocorr}
+        self.quantiles = res.get("quantiles")  # with quantile_vars: {var: ChainQuantiles}
         self._res = res if keep_draws else None
 
     def samples(self, w):
@@ -444,7 +463,8 @@ def _draw_vars(name, vars_):
 
 def estimatewindows(rawdata, dates, endIndices, startIndex=1, keep_draws=False, device=0, window_ids=None, corr=False,
                     cdf_grid=None, cdf_horizons=(0,), bias_horizon=None, moment_horizons=None, density_vars=None,
-                    density_cuts=None, density_bins=64, density_trace=(0, 1), acf_vars=None, acf_lags=255, **kwargs):
+                    density_cuts=None, density_bins=64, density_trace=(0, 1), acf_vars=None, acf_lags=255, quantile_vars=None,
+                    quantile_probs=(0.05, 0.5, 0.95), **kwargs):
     """Batched estimatemodel over many expanding windows (one GPU call).
 
     Window w uses sampleRange = startIndex:endIndices[w], endIndex = endIndices[w]; the
@@ -469,10 +489,14 @@ def estimatewindows(rawdata, dates, endIndices, startIndex=1, keep_draws=False, 
     acf_vars: names among mu, sig2, pi_end, A, fcast -> BatchResult.autocorr, {var: ChainAutocorr}: per window and column the
     autocovariances up to lag acf_lags, the integrated autocorrelation time, effective sample size, Monte-Carlo standard error
     and split-R-hat, computed on the device from the 5-digit-rounded draws (_lib.chain_autocorr); the draw arrays are fetched
-    and dropped likewise."""
+    and dropped likewise.
+    quantile_vars: names among mu, sig2, pi_end, A, fcast -> BatchResult.quantiles, {var: ChainQuantiles}: per window and column
+    the exact quantiles at quantile_probs (at most 16) with the draws that bracket them, selected on the device from the
+    5-digit-rounded draws (_lib.chain_quantiles); the draw arrays are fetched and dropped likewise."""
     if startIndex != 1:
         raise ValueError("windows must start at index 1 (see estopt)")
     acf_vars, density_vars = _draw_vars("acf_vars", acf_vars), _draw_vars("density_vars", density_vars)
+    quantile_vars = _draw_vars("quantile_vars", quantile_vars)
     rawdata = np.asarray(rawdata, dtype=np.float64)
     opts = [estopt(rawdata, dates, sampleRange=range(1, int(e) + 1), endIndex=int(e), **kwargs) for e in endIndices]
     o0 = opts[0]
@@ -501,6 +525,8 @@ def estimatewindows(rawdata, dates, endIndices, startIndex=1, keep_draws=False, 
             want += tuple(density_vars)
         if acf_vars is not None:
             want += tuple(acf_vars)
+        if quantile_vars is not None:
+            want += tuple(quantile_vars)
         want = tuple(k for k in _lib.DRAW_KEYS if k in want) or False
     res = _lib.estimate_batch_host(Y, Tw, o0.D, o0.burnin, o0.Nrun, tuple(o0.horizons), yreal, seed=o0.seed,
                                    device=device, want_draws=want, window_ids=window_ids, want_corr=corr)
@@ -529,6 +555,10 @@ def estimatewindows(rawdata, dates, endIndices, startIndex=1, keep_draws=False, 
     if acf_vars is not None:
         res["autocorr"] = {var: ChainAutocorr(var, _density_columns(o0, var), _lib.chain_autocorr(res[var], acf_lags, device=device))
                            for var in acf_vars}
+    if quantile_vars is not None:
+        res["quantiles"] = {var: ChainQuantiles(var, _density_columns(o0, var), quantile_probs,
+                                                _lib.chain_quantiles(res[var], quantile_probs, device=device))
+                            for var in quantile_vars}
     return BatchResult(opts, res, keep_draws)
 
 
@@ -1535,4 +1565,84 @@ def write_chain_ess(path, dates, diag):
             rows.append([str(d), name] + [_fmt(getattr(diag, k)[w, c]) for k in ("mean", "variance", "tau", "ess", "mcse")] +
                         [str(int(diag.pairs[w, c])), str(int(diag.truncated[w, c])), _fmt(diag.rhat[w, c])])
     _write_csv(path, ["date", "column", "mean", "variance", "tau", "ess", "mcse", "pairs", "truncated", "rhat"], rows)
+    return path
+
+
+# ------------------------------------------------------------- exact quantiles, credible limits --
+
+def _quantiles_from_cells(cells, probs):
+    """The outputs of hmcg_chain_quantiles for one date from the cells (n, C) of its per-draw file, in numpy with the library's
+    rule (include/hmcg_order.h): NaNs left out, the rest sorted in the IEEE total order (-0.0 below +0.0: np.sort on the
+    order-preserving integer key), h = p (m - 1), j = floor(h), g = h - j, value = lo + g (hi - lo) clamped to hi, one rounded
+    operation per step.  Returns the parts of a ChainQuantiles without the window axis."""
+    n, Cn = cells.shape
+    Q = len(probs)
+    out = {k: np.full((Cn, Q), np.nan) for k in _lib.ORD_FIELDS}
+    out["count"], out["nan"] = np.zeros(Cn, dtype=np.int64), np.zeros(Cn, dtype=np.int64)
+    top = np.uint64(1) << np.uint64(63)
+    for c in range(Cn):
+        v = np.ascontiguousarray(cells[:, c], dtype=np.float64)
+        v = v[~np.isnan(v)]
+        m = v.size
+        out["count"][c], out["nan"][c] = m, n - m
+        if m == 0:
+            continue
+        u = v.view(np.uint64)
+        key = np.sort(np.where(u >> np.uint64(63) != 0, ~u, u | top))
+        s = np.where(key >> np.uint64(63) != 0, key & ~top, ~key).view(np.float64)
+        for i, p in enumerate(probs):
+            h = np.float64(p) * np.float64(m - 1)
+            j = int(np.floor(h))
+            g = h - np.float64(j)
+            lo, hi = s[j], s[min(j + 1, m - 1)]
+            with np.errstate(invalid="ignore", over="ignore"):
+                if g == 0.0 or lo == hi:
+                    value = lo
+                else:
+                    value = lo + g * (hi - lo)
+                    value = hi if value > hi else value
+            out["value"][c, i], out["lo"][c, i], out["hi"][c, i], out["g"][c, i] = value, lo, hi, g
+    return out
+
+
+def calcquantiles(datadir, dates, var="mu", probs=(0.05, 0.5, 0.95), result=None):
+    """Exact quantiles of one variable's chain per end date and column -- the median and the credible limits a report of the
+    fit starts with (numpy's / Julia's default quantile definition).  var: mu, sig2, pi_end, A or fcast.
+
+    result=None: every date's per-draw file (`filtered_means_<date>.csv` for mu; see calcchain) is read back, sorted and
+    evaluated on the host in numpy; no GPU is touched.
+    result = a BatchResult of estimatewindows(..., quantile_vars=(var, ...), quantile_probs=probs): the values were selected on
+    the device from the rounded draws; every date must be one of the result's end dates, and probs must be the result's.
+    Returns (dates, ChainQuantiles)."""
+    dates = [str(d) for d in dates]
+    probs = tuple(float(p) for p in probs)
+    if var not in DENSITY_FILES:
+        raise ValueError("var must be one of %s" % (tuple(DENSITY_FILES),))
+    if not 1 <= len(probs) <= _lib.ORD_MAXQ or not all(0.0 <= p <= 1.0 for p in probs):
+        raise ValueError("probs: 1..%d probabilities in [0, 1]" % _lib.ORD_MAXQ)
+    if result is not None:
+        d = getattr(result, "quantiles", None)
+        if d is None or var not in d:
+            raise ValueError("result carries no quantiles of %s (estimatewindows(..., quantile_vars=(%r,)))" % (var, var))
+        d = d[var]
+        if probs != d.probs:
+            raise ValueError("result was computed for other probabilities")
+        return dates, d.rows(_rows_of(result, dates))
+    parts, columns = [], None
+    for date in dates:
+        columns, cells = _cells(datadir, DENSITY_FILES[var], date)
+        parts.append(_quantiles_from_cells(cells, probs))
+    return dates, ChainQuantiles(var, columns, probs, {k: np.array([q[k] for q in parts]) for k in _lib.ORD_FIELDS + ("count", "nan")})
+
+
+def write_chain_quantiles(path, dates, q):
+    """`date,column,prob,value,lo,hi,g,count,nan`: one row per end date, column and probability of a ChainQuantiles.  Our
+    layout: the reference writes no such file."""
+    rows = []
+    for w, d in enumerate(dates):
+        for c, name in enumerate(q.columns):
+            for i, p in enumerate(q.probs):
+                rows.append([str(d), name, _fmt(p)] + [_fmt(getattr(q, k)[w, c, i]) for k in _lib.ORD_FIELDS] +
+                            [str(int(q.count[w, c])), str(int(q.nan[w, c]))])
+    _write_csv(path, ["date", "column", "prob"] + list(_lib.ORD_FIELDS) + ["count", "nan"], rows)
     return path

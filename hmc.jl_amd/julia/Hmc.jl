@@ -22,7 +22,8 @@
 # (hmcg_mixture_moments); calcskewness / altforecasts: the two scripts themselves, in closed form.  calcchain /
 # chain_density: the binned chain densities and running means plots/mcplots.jl and plots/timeseriesplots.jl draw
 # (hmcg_chain_density).  calcess / chain_autocorr: autocovariances, integrated autocorrelation time, effective sample size,
-# Monte-Carlo standard error and split-R-hat of the draws (hmcg_chain_autocorr; no reference script).  runaggregate /
+# Monte-Carlo standard error and split-R-hat of the draws (hmcg_chain_autocorr; no reference script).  calcquantiles /
+# chain_quantiles: the exact median and credible limits of the draws by selection (hmcg_chain_quantiles).  runaggregate /
 # calcdispersion of the reference work unchanged on the files written here (same names, columns and float text).
 #
 # Reference lines mirrored: estopt src/Hmc.jl:17-73, accessors :85-107, makedate :573-582,
@@ -174,6 +175,20 @@ struct hmcg_autocorr                  # include/hmcg.h: autocorrelation, effecti
     nd_ld::Int64
     L::Int32
     flags::Int32
+end
+const HMCG_ORD_ROUND5 = Int32(1)
+const HMCG_ORD_MAXQ = 16
+const HMCG_ORD_STRIDE = 4
+struct hmcg_quantiles                 # include/hmcg_order.h (the companion header): exact quantiles of the draws
+    struct_size::Int32
+    W::Int32
+    C::Int32
+    device::Int32
+    nd::Int64
+    nd_ld::Int64
+    Q::Int32
+    flags::Int32
+    probs::NTuple{16,Float64}
 end
 
 last_error() = unsafe_string(ccall((:hmcg_last_error, LIBHMCG), Cstring, ()))
@@ -616,6 +631,60 @@ function calcess(opts::Vector{estopt}, var::Symbol=:μ; lags::Integer=255, devic
     pick(s) = var == :πe ? s.πb[:, 1, :] : getfield(s, var)
     x = cat((pick(s) for s in samples)...; dims=var == :A ? 4 : 3)
     return ([enddate(o) for o in opts], chain_autocorr(x; lags=lags, device=device)...)
+end
+
+# ---- exact quantiles and credible limits of the draws (include/hmcg_order.h; no reference script; not run) -----------------------
+function _quantiles(W, C, nd, ld, probs, device, round5)
+    1 <= length(probs) <= HMCG_ORD_MAXQ || error("1..$(HMCG_ORD_MAXQ) probabilities")
+    p = ntuple(i -> i <= length(probs) ? Float64(probs[i]) : 0.0, HMCG_ORD_MAXQ)
+    return hmcg_quantiles(Int32(sizeof(hmcg_quantiles)), Int32(W), Int32(C), Int32(device), Int64(nd), Int64(ld), Int32(length(probs)),
+                          round5 ? HMCG_ORD_ROUND5 : Int32(0), p)
+end
+
+"""
+    chain_quantiles(x; probs=(0.05, 0.5, 0.95), device=0, round5=true) -> (q (4, Q, C, W), n (2, C, W))
+
+hmcg_chain_quantiles over ONE host draw array in a layout estimatewindows fills, draw index first and window last -- μ, σ, πe
+(nrun, K, W), A (nrun, K, K, W), forecasts (nrun, 2H, W); the axes between count as the C columns: per window, column and
+probability q = value, lo, hi, g -- the exact quantile (Julia's default definition), the two draws that bracket it and the
+weight of hi -- selected on the device; n = the draws ranked and the NaNs left out.
+"""
+function chain_quantiles(x::Array{Float64}; probs=(0.05, 0.5, 0.95), device::Integer=0, round5::Bool=true)
+    nrun, W = size(x, 1), size(x, ndims(x))
+    C = div(length(x), nrun * W)
+    q = Array{Float64}(undef, HMCG_ORD_STRIDE, length(probs), C, W)
+    n = Array{Int64}(undef, 2, C, W)
+    rc = GC.@preserve x q n ccall((:hmcg_chain_quantiles, LIBHMCG), Cint,
+        (Ref{hmcg_quantiles}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Cvoid}),
+        _quantiles(W, C, nrun, nrun, probs, device, round5), x, q, n, C_NULL)
+    rc == 0 || error("libhmcgibbs rc=$rc: $(last_error())")
+    return q, n
+end
+
+"""
+    chain_quantiles_device(W, C, nd, ld, dx, dq, dn; probs=(0.05, 0.5, 0.95), device=0, round5=true, stream=C_NULL)
+
+hmcg_chain_quantiles_device over device pointers; enqueued on `stream` (C_NULL: the library's own) and not waited for.
+"""
+function chain_quantiles_device(W, C, nd, ld, dx::Ptr{Float64}, dq::Ptr{Float64}, dn::Ptr{Int64}; probs=(0.05, 0.5, 0.95),
+                                device::Integer=0, round5::Bool=true, stream::Ptr{Cvoid}=C_NULL)
+    rc = ccall((:hmcg_chain_quantiles_device, LIBHMCG), Cint,
+               (Ref{hmcg_quantiles}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Cvoid}, Ptr{Cvoid}),
+               _quantiles(W, C, nd, ld, probs, device, round5), dx, dq, dn, stream, C_NULL)
+    rc == 0 || error("libhmcgibbs rc=$rc: $(last_error())")
+    return nothing
+end
+
+"""
+    calcquantiles(opts, var=:μ; probs=(0.05, 0.5, 0.95), device=0) -> (dates, q, n)
+
+Estimates the windows and selects the quantiles of one variable's chain (:μ, :σ, :πe, :A or :forecasts) on the device.
+"""
+function calcquantiles(opts::Vector{estopt}, var::Symbol=:μ; probs=(0.05, 0.5, 0.95), device::Integer=0)
+    samples, _, _ = estimatewindows(opts; device=device)
+    pick(s) = var == :πe ? s.πb[:, 1, :] : getfield(s, var)
+    x = cat((pick(s) for s in samples)...; dims=var == :A ? 4 : 3)
+    return ([enddate(o) for o in opts], chain_quantiles(x; probs=probs, device=device)...)
 end
 
 function _summary_rows(datadir, stem)
