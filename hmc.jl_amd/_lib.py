@@ -44,6 +44,12 @@ ORD_ROUND5 = 1                  # include/hmcg_order.h
 ORD_MAXQ = 16                   # HMCG_ORD_MAXQ: probabilities of one call
 ORD_STRIDE = 4                  # HMCG_ORD_STRIDE: doubles per (window, column, probability)
 ORD_FIELDS = ("value", "lo", "hi", "g")
+ERG_ROUND5 = 1                  # include/hmcg_ergodic.h
+
+
+def erg_cols(K):
+    """HMCG_ERG_COLS(K): per-draw columns of the ergodic moments (pi[K], dur[K], mean, variance)."""
+    return 2 * K + 2
 
 
 def bias_stride(K):
@@ -132,6 +138,15 @@ class Quantiles(C.Structure):
 
 ORDER_EXPORTS = ("hmcg_chain_quantiles", "hmcg_chain_quantiles_device")
 
+
+# include/hmcg_ergodic.h:
+class Ergodic(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("W", C.c_int32), ("K", C.c_int32), ("device", C.c_int32),
+                ("nd", C.c_int64), ("nd_ld", C.c_int64), ("flags", C.c_int32), ("reserved", C.c_int32)]
+
+
+ERGODIC_EXPORTS = ("hmcg_ergodic_moments", "hmcg_ergodic_moments_device")
+
 _LIB = None
 
 
@@ -180,7 +195,7 @@ def load():
                             "this package has no CPU fallback" % SO_PATH)
         _share_torch_hip_runtime()
         L = C.CDLL(SO_PATH)
-        for name in EXPORTS + ORDER_EXPORTS:
+        for name in EXPORTS + ORDER_EXPORTS + ERGODIC_EXPORTS:
             getattr(L, name).restype = C.c_int
         L.hmcg_last_error.restype, L.hmcg_shutdown.restype = C.c_char_p, None
         _LIB = L
@@ -729,6 +744,65 @@ def chain_quantiles_device(qs, dx, dq, dn, stream=None, timed=False):
     Enqueued on `stream` (None: the library's own).  Returns the Timing struct when timed (the call then waits for completion),
     else None."""
     return _device_call(load().hmcg_chain_quantiles_device, qs, (dx, dq, dn), stream, timed)
+
+
+def make_ergodic(W, K, nd, nd_ld, device=0, round5=True):
+    """hmcg_ergodic of a call; every rule is the library's (HMCG_E_BADARG)."""
+    p = Ergodic()
+    p.struct_size = C.sizeof(Ergodic)
+    p.W, p.K, p.device, p.nd, p.nd_ld = int(W), int(K), int(device), int(nd), int(nd_ld)
+    p.flags = ERG_ROUND5 if round5 else 0
+    return p
+
+
+def erg_names(K):
+    """The names of the HMCG_ERG_COLS(K) per-draw columns, in order."""
+    return tuple("pi%d" % (k + 1) for k in range(K)) + tuple("dur%d" % (k + 1) for k in range(K)) + ("mean", "variance")
+
+
+def unpack_ergodic(out, n, K, cols=None):
+    """The output blocks of hmcg_ergodic_moments -- out (W, C, 2), n (W, 2) int64, C = 2K + 2 -- as a dict: per window the mean
+    and the variance (divisor good - 1) over the good draws of pi (W, K) the stationary regime law, dur (W, K) the expected
+    durations, mean (W,) and variance (W,) the long-run mean and variance of the series: pi_mean, pi_var, dur_mean, dur_var,
+    mean_mean, mean_var, variance_mean, variance_var; good (W,) int64 the draws with all C columns finite, bad (W,) the rest;
+    `cols` (W, C, nd), the per-draw columns, when they were asked for."""
+    out, n = np.asarray(out), np.asarray(n)
+    res = {}
+    for name, sl in (("pi", slice(0, K)), ("dur", slice(K, 2 * K)), ("mean", 2 * K), ("variance", 2 * K + 1)):
+        res[name + "_mean"], res[name + "_var"] = out[:, sl, 0].copy(), out[:, sl, 1].copy()
+    res["good"], res["bad"] = n[:, 0].astype(np.int64), n[:, 1].astype(np.int64)
+    if cols is not None:
+        res["cols"] = cols
+    return res
+
+
+def ergodic_moments(mu, sig2, A, cols=False, nd=None, device=0, round5=True, timing=None):
+    """hmcg_ergodic_moments over host (numpy) draw arrays in the C-ABI layouts -- mu/sig2 (W, K, nd), A (W, K, K, nd) with
+    A[w, j, i, d] = draw d of A[i, j] -- as estimate_batch_host returns them, over their first nd draws (default: all).  Per
+    draw the stationary law of the regimes (GTH elimination on the off-diagonal cells; the diagonal of A is never read), the
+    expected durations and the long-run mean and variance; per window their mean and variance over the good draws.
+    cols=True also returns the per-draw columns (W, 2K + 2, nd), in the layout chain_quantiles / chain_density /
+    chain_autocorr take.  round5 (default): every input is first rounded to 5 digits, as the cells of the per-draw CSV files
+    are.  Returns the dict of unpack_ergodic.  timing: a Timing to fill."""
+    (mu, sig2), A, (W, K, ld) = _state_draws(A, mu=mu, sig2=sig2)
+    if A is None:
+        raise ValueError("A is required")
+    nd = ld if nd is None else int(nd)
+    p = make_ergodic(W, K, nd, ld, device, round5)
+    Cn = erg_cols(K)
+    out = np.zeros((W, Cn, 2))
+    n = np.zeros((W, 2), dtype=np.int64)
+    cl = np.full((W, Cn, ld), np.nan) if cols else None
+    _check(load().hmcg_ergodic_moments(C.byref(p), _np_ptr(mu), _np_ptr(sig2), _np_ptr(A), _np_ptr(cl), _np_ptr(out), _np_ptr(n),
+                                       _tm(timing)))
+    return unpack_ergodic(out, n, K, None if cl is None else cl[:, :, :nd])
+
+
+def ergodic_moments_device(erg, dmu, dsig2, dA, dcols, dout, dn, stream=None, timed=False):
+    """hmcg_ergodic_moments_device over raw device pointers (ints, e.g. torch tensor.data_ptr(); dcols 0 / None when the
+    per-draw columns are not kept); erg: make_ergodic(...).  Enqueued on `stream` (None: the library's own).  Returns the
+    Timing struct when timed (the call then waits for completion), else None."""
+    return _device_call(load().hmcg_ergodic_moments_device, erg, (dmu, dsig2, dA, dcols, dout, dn), stream, timed)
 
 
 def format_float(x):

@@ -39,6 +39,7 @@
 #include "density.hpp"
 #include "autocorr.hpp"
 #include "order.hpp"
+#include "ergodic.hpp"
 
 namespace {
 
@@ -133,6 +134,7 @@ struct DeviceCtx {
     Arena mix;                     // device entry of the predictive-mixture moments: the slab sums and pivots
     Arena dens;                    // device entry of the chain densities: the piece sums, pivots and range keys
     Arena acf;                     // device entry of the autocorrelations: the running lag sums, pivots and edge values
+    Arena erg;                     // device entry of the ergodic moments: the slab sums and pivots
     hmcg_hostutil::ScatterPool pool;              // host entries: helpers for the scatter into the caller's arrays
 };
 DeviceCtx g_ctx[HMCG_MAXDEV];
@@ -234,6 +236,7 @@ void destroy_context(DeviceCtx& c)
     c.mix.release();
     c.dens.release();
     c.acf.release();
+    c.erg.release();
     c.pool.stop();
     c.stream = c.copy = nullptr;
     c.ready = false;
@@ -1548,6 +1551,97 @@ int ord_host(DeviceCtx& c, const hmcg_quantiles* p, const double* x, double* q, 
     return 0;
 }
 
+// ---- ergodic regime law, durations and long-run moments of the draws (ergodic.hip; argument rules, work area and the per-draw
+// arithmetic: ergodic_plan.hpp; slab / chunk cut: stat_plan.hpp; ABI: include/hmcg_ergodic.h) -------------------------------------
+
+hmcg_host::ErgArgs erg_args(const hmcg_ergodic* p)
+{
+    hmcg_host::ErgArgs a{};
+    a.W = p->W; a.K = p->K; a.round5 = (p->flags & HMCG_ERG_ROUND5) != 0;
+    a.nslab_total = pred_slabs(p->nd);
+    return a;
+}
+
+int erg_device(DeviceCtx& c, const hmcg_ergodic* p, const double* dmu, const double* dsig2, const double* dA, double* dcols, double* dout,
+               int64_t* dn, hipStream_t stream, hmcg_timing* timing)
+{
+    const size_t work = sizeof(double) * erg_part_doubles(p->W, p->nd, p->K);
+    return stat_device(c, c.erg, work, stream, timing, {p->W, 256, 0}, 2, [&]() -> int {
+        hmcg_host::ErgArgs a = erg_args(p);
+        a.mu = dmu; a.sig2 = dsig2; a.A = dA; a.cols = dcols;
+        a.part = reinterpret_cast<double*>(c.erg.base);
+        a.nd = p->nd; a.nd_ld = p->nd_ld; a.slab0 = 0;
+        HIP_TRY(launch_ergodic(a, stream));
+        HIP_TRY(launch_ergodic_finalize(a.part, dout, reinterpret_cast<long long*>(dn), p->W, p->K, p->nd, stream));
+        return 0;
+    });
+}
+
+// Host entry on one device, through the upload ring: every chunk files its slabs' sums in the same table (the first one the
+// pivots too); one finalize at the end.  With cols a chunk buffer carries the chunk's per-draw columns behind its inputs: the
+// kernel writes them there, they are copied to the pinned twin behind the kernel, and scattered into the caller's array when
+// the ring comes back to that buffer (the ring has waited for the copy by then) or at the end.
+int erg_host(DeviceCtx& c, const hmcg_ergodic* p, const double* mu, const double* sig2, const double* A, double* cols, double* out,
+             int64_t* n, hmcg_timing* timing)
+{
+    const int K = p->K, W = p->W, C = erg_cols(K);
+    const size_t WK = (size_t)W * (size_t)K, ld = (size_t)p->nd_ld;
+    const int ncol = erg_columns(K) + (cols ? C : 0);
+    UploadRing ring(c, p->nd, W, ncol, timing);
+    const size_t b_out = sizeof(double) * (size_t)W * (size_t)C * 2, b_n = sizeof(int64_t) * (size_t)W * 2;
+    Layout io;
+    const size_t o_out = io.add(b_out), o_n = io.add(b_n);
+    int rc = ring.alloc(io, sizeof(double) * erg_part_doubles(W, p->nd, K), (size_t)W * (size_t)ncol * (size_t)ring.cdraws);
+    if (rc) return rc;
+    hmcg_host::ErgArgs a = erg_args(p);
+    a.part = reinterpret_cast<double*>(ring.work);
+    const size_t in_cols = (size_t)W * (size_t)erg_columns(K);       // a chunk's columns ahead of its per-draw columns
+    const PredChunk* held[RING] = {};                                // the chunk whose columns a buffer pair holds
+    auto slot = [&] { return (int)((ring.uploads - 1) % (size_t)ring.nbuf); };      // the buffer pair of the chunk being packed / launched
+    auto scatter = [&](int b) {
+        if (!held[b]) return;
+        const PredChunk& ch = *held[b];
+        const double* src = ring.pbuf[b] + in_cols * (size_t)ch.n;
+        for (size_t q = 0; q < (size_t)W * (size_t)C; ++q) memcpy(cols + q * ld + (size_t)ch.d0, src + q * (size_t)ch.n, sizeof(double) * (size_t)ch.n);
+        held[b] = nullptr;
+    };
+    // packed chunk: mu | sig2 | A (its diagonal columns left as they are: never read), each [W][columns][ch.n], then cols [W][C][ch.n]
+    rc = ring.run(
+        [&](const PredChunk& ch, double* pb) {
+            if (cols) scatter(slot());
+            double* e = pack_columns(mu, WK, ld, ch.d0, (size_t)ch.n, pb);
+            e = pack_columns(sig2, WK, ld, ch.d0, (size_t)ch.n, e);
+            for (size_t q = 0; q < WK * (size_t)K; ++q) {
+                const size_t ij = q % ((size_t)K * (size_t)K);
+                if (ij % (size_t)K != ij / (size_t)K) memcpy(e + q * (size_t)ch.n, A + q * ld + (size_t)ch.d0, sizeof(double) * (size_t)ch.n);
+            }
+            e += WK * (size_t)K * (size_t)ch.n;
+            return (size_t)(e - pb);
+        },
+        [&](const PredChunk& ch, double* db, hipStream_t s) -> int {
+            const size_t o_col = WK * (size_t)ch.n;
+            a.mu = db; a.sig2 = db + o_col; a.A = db + 2 * o_col; a.cols = cols ? db + in_cols * (size_t)ch.n : nullptr;
+            a.nd = ch.n; a.nd_ld = ch.n; a.slab0 = ch.d0 / PRED_SLAB;
+            HIP_TRY(launch_ergodic(a, s));
+            if (cols) {
+                const int b = slot();
+                HIP_TRY(hipMemcpyAsync(ring.pbuf[b] + in_cols * (size_t)ch.n, a.cols, sizeof(double) * (size_t)W * (size_t)C * (size_t)ch.n,
+                                       hipMemcpyDeviceToHost, s));
+                held[b] = &ch;
+            }
+            return 0;
+        });
+    if (rc) return rc;
+    HIP_TRY(launch_ergodic_finalize(a.part, reinterpret_cast<double*>(ring.dev + o_out), reinterpret_cast<long long*>(ring.dev + o_n), W, K,
+                                    p->nd, c.stream));
+    if ((rc = ring.fetch(0, io.total))) return rc;
+    if (cols)
+        for (int b = 0; b < ring.nbuf; ++b) scatter(b);
+    memcpy(out, ring.pin + o_out, b_out);
+    memcpy(n, ring.pin + o_n, b_n);
+    return ring.report({W, 256, 0}, (int)ring.uploads + 1);
+}
+
 // The prologue of a compute entry on one device.  The argument check comes first and needs no device: a caller on a machine
 // without one still gets the argument errors.  Then the context of p->device, its lock, the device made current, and body(context).
 template <class P, class Check, class Body>
@@ -1744,6 +1838,21 @@ int hmcg_chain_quantiles(const hmcg_quantiles* p, const double* x, double* q, in
 {
     return entry(p, [&](char* msg, size_t nmsg) { return check_quantiles(p, x, q, n, msg, nmsg); },
                  [&](DeviceCtx& c) { return ord_host(c, p, x, q, n, timing); });
+}
+
+int hmcg_ergodic_moments_device(const hmcg_ergodic* p, const double* dmu, const double* dsig2, const double* dA, double* dcols, double* dout,
+                                int64_t* dn, void* stream, hmcg_timing* timing)
+{
+    return entry(p, [&](char* msg, size_t nmsg) { return check_ergodic(p, dmu, dsig2, dA, dout, dn, msg, nmsg); }, [&](DeviceCtx& c) {
+        return erg_device(c, p, dmu, dsig2, dA, dcols, dout, dn, stream ? (hipStream_t)stream : c.stream, timing);
+    });
+}
+
+int hmcg_ergodic_moments(const hmcg_ergodic* p, const double* mu, const double* sig2, const double* A, double* cols, double* out, int64_t* n,
+                         hmcg_timing* timing)
+{
+    return entry(p, [&](char* msg, size_t nmsg) { return check_ergodic(p, mu, sig2, A, out, n, msg, nmsg); },
+                 [&](DeviceCtx& c) { return erg_host(c, p, mu, sig2, A, cols, out, n, timing); });
 }
 
 }  // extern "C"

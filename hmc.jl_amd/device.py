@@ -80,8 +80,15 @@ class DevicePanel:
         self.last_timing = tm
         return tm.kernel_ms if tm is not None else None
 
-    def _draws(self, what, var="mu"):
-        """The panel's HBM draws of `var` for the statistic `what`, and their columns per window."""
+    def _draws(self, what, var="mu", x=None):
+        """The panel's HBM draws of `var` for the statistic `what`, and their columns per window.  x: a (W, C, nrun) float64
+        tensor on the panel's device to take in their place, e.g. the per-draw columns of ergodic(cols=True)."""
+        if x is not None:
+            if x.dtype != self.torch.float64 or x.device != self.dev or x.dim() != 3 or x.shape[0] != self.W or x.shape[2] != self.nrun \
+                    or not x.is_contiguous():
+                raise ValueError("x must be a contiguous float64 (W, C, nrun) tensor on the panel's device")
+            self._held.append(x)                # kept until sync(): the enqueued kernels may still read it
+            return x, int(x.shape[1])
         if var not in _lib.DRAW_KEYS:
             raise ValueError("var must be one of %s" % (_lib.DRAW_KEYS,))
         x = getattr(self, var)
@@ -140,7 +147,7 @@ class DevicePanel:
                                          self.A.data_ptr() if any(h > 0 for h in hz) else 0, out.data_ptr(), None, timed)
         return self._done(tm, timed, out)
 
-    def chain_density(self, var="mu", cuts=None, bins=64, lo_hi=None, trace=(0, 1), timed=False, round5=True):
+    def chain_density(self, var="mu", cuts=None, bins=64, lo_hi=None, trace=(0, 1), timed=False, round5=True, x=None):
         """Chain densities and running means of one variable's draws from the panel's own HBM draws
         (hmcg_chain_density_device; plots/mcplots.jl's plotchain and plotchainmean, plots/timeseriesplots.jl's plot_mean /
         plot_var up to the drawing).  var: "mu", "sig2", "pi_end" (C = K columns), "A" (C = K * K, column i + K * j = A[i, j])
@@ -151,7 +158,7 @@ class DevicePanel:
         prefix, trace (W, C, length); _lib.unpack_chain_density names the parts of their numpy copies.  Enqueued on the library
         stream behind `run`; with timed=True the call waits and last_timing holds the HIP-event time, otherwise call sync()
         before reading the tensors."""
-        x, Cn = self._draws("chain_density", var)
+        x, Cn = self._draws("chain_density", var, x)
         torch = self.torch
         dens = _lib.make_density(self.W, Cn, self.nrun, self.nrun, cuts, bins, trace, self.device_index, round5)
         f64 = dict(dtype=torch.float64, device=self.dev)
@@ -169,14 +176,14 @@ class DevicePanel:
             self._held.append(lh)
         return self._done(tm, timed, out)
 
-    def chain_autocorr(self, var="mu", lags=255, timed=False, round5=True):
+    def chain_autocorr(self, var="mu", lags=255, timed=False, round5=True, x=None):
         """Autocovariances and convergence diagnostics of one variable's draws from the panel's own HBM draws
         (hmcg_chain_autocorr_device).  var: "mu", "sig2", "pi_end" (C = K columns), "A" (C = K * K) or "fcast" (C = 2H); lags: the
         largest lag L (0..1024, below nrun).  Returns a dict of tensors: acov (W, C, lags + 1), diag (W, C, 8) = mean, variance,
         tau, ess, mcse, pairs, truncated, rhat; _lib.unpack_chain_autocorr names the parts of their numpy copies.  Enqueued on the
         library stream behind `run`; with timed=True the call waits and last_timing holds the HIP-event time, otherwise call
         sync() before reading the tensors."""
-        x, Cn = self._draws("chain_autocorr", var)
+        x, Cn = self._draws("chain_autocorr", var, x)
         torch = self.torch
         acf = _lib.make_autocorr(self.W, Cn, self.nrun, self.nrun, lags, self.device_index, round5)
         f64 = dict(dtype=torch.float64, device=self.dev)
@@ -184,19 +191,39 @@ class DevicePanel:
         tm = _lib.chain_autocorr_device(acf, x.data_ptr(), out["acov"].data_ptr(), out["diag"].data_ptr(), None, timed)
         return self._done(tm, timed, out)
 
-    def chain_quantiles(self, var="mu", probs=(0.05, 0.5, 0.95), timed=False, round5=True):
+    def chain_quantiles(self, var="mu", probs=(0.05, 0.5, 0.95), timed=False, round5=True, x=None):
         """Exact quantiles of one variable's draws from the panel's own HBM draws (hmcg_chain_quantiles_device): a selection on
-        the device, no draw leaves it.  var: "mu", "sig2", "pi_end" (C = K columns), "A" (C = K * K) or "fcast" (C = 2H); probs:
+        the device, no draw leaves it.  x: a (W, C, nrun) tensor to take in place of a variable (see _draws).  var: "mu", "sig2", "pi_end" (C = K columns), "A" (C = K * K) or "fcast" (C = 2H); probs:
         at most 16 probabilities in [0, 1].  Returns a dict of tensors: q (W, C, Q, 4) = value, lo, hi, g per probability and
         n (W, C, 2) int64 = the draws ranked and the NaNs; _lib.unpack_chain_quantiles names the parts of their numpy copies.
         Enqueued on the library stream behind `run`; with timed=True the call waits and last_timing holds the HIP-event time,
         otherwise call sync() before reading the tensors."""
-        x, Cn = self._draws("chain_quantiles", var)
+        x, Cn = self._draws("chain_quantiles", var, x)
         torch = self.torch
         qs = _lib.make_quantiles(self.W, Cn, self.nrun, self.nrun, probs, self.device_index, round5)
         out = {"q": torch.empty((self.W, Cn, qs.Q, _lib.ORD_STRIDE), dtype=torch.float64, device=self.dev),
                "n": torch.empty((self.W, Cn, 2), dtype=torch.int64, device=self.dev)}
         tm = _lib.chain_quantiles_device(qs, x.data_ptr(), out["q"].data_ptr(), out["n"].data_ptr(), None, timed)
+        return self._done(tm, timed, out)
+
+    def ergodic(self, cols=False, timed=False, round5=True):
+        """The ergodic regime law, expected durations and long-run mean and variance from the panel's own HBM draws
+        (hmcg_ergodic_moments_device): the limit h -> infinity of the weights pi_end A^h.  Returns a dict of tensors: out
+        (W, 2K + 2, 2) = mean and variance over the good draws of pi[K], dur[K], the long-run mean and the long-run variance,
+        n (W, 2) int64 = the good draws (every column finite) and the rest, and with cols=True cols (W, 2K + 2, nrun), the
+        per-draw columns, which chain_quantiles / chain_density / chain_autocorr take as x=; _lib.unpack_ergodic names the
+        parts of their numpy copies.  Enqueued on the library stream behind `run`; with timed=True the call waits and
+        last_timing holds the HIP-event time, otherwise call sync() before reading the tensors."""
+        self._draws("ergodic")
+        torch = self.torch
+        Cn = _lib.erg_cols(self.K)
+        erg = _lib.make_ergodic(self.W, self.K, self.nrun, self.nrun, self.device_index, round5)
+        out = {"out": torch.empty((self.W, Cn, 2), dtype=torch.float64, device=self.dev),
+               "n": torch.empty((self.W, 2), dtype=torch.int64, device=self.dev)}
+        if cols:
+            out["cols"] = torch.empty((self.W, Cn, self.nrun), dtype=torch.float64, device=self.dev)
+        tm = _lib.ergodic_moments_device(erg, self.mu.data_ptr(), self.sig2.data_ptr(), self.A.data_ptr(),
+                                         out["cols"].data_ptr() if cols else 0, out["out"].data_ptr(), out["n"].data_ptr(), None, timed)
         return self._done(tm, timed, out)
 
     def sync(self):

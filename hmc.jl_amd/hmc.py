@@ -24,6 +24,8 @@ ABI.  Names, argument meaning and result layout follow the reference:
                         standard error and split-R-hat of the draws (from the files or from the device); write_chain_ess
     calcquantiles       no reference script: exact quantiles (median, credible limits) of the draws by selection (from the files
                         or from the device); write_chain_quantiles
+    calcergodic         no reference script: the stationary regime law, expected durations and long-run mean and variance of
+                        the draws, the limit of pi_end A^h (from the files or from the device); write_ergodic
 
 New (the reference batches by launching one SLURM task per window,
 slurmscripts/base_estimation.sh:5): `estimatewindows`, one call for many windows.
@@ -443,6 +445,7 @@ class BatchResult:
         self.density = res.get("density")      # with density_vars: {var: ChainDensity}
         self.autocorr = res.get("autocorr")    # with acf_vars: {var: ChainAutocorr}
         self.quantiles = res.get("quantiles")  # with quantile_vars: {var: ChainQuantiles}
+        self.ergodic = res.get("ergodic")      # with ergodic=True: the dict of _lib.unpack_ergodic, one row per window
         self._res = res if keep_draws else None
 
     def samples(self, w):
@@ -464,7 +467,7 @@ def _draw_vars(name, vars_):
 def estimatewindows(rawdata, dates, endIndices, startIndex=1, keep_draws=False, device=0, window_ids=None, corr=False,
                     cdf_grid=None, cdf_horizons=(0,), bias_horizon=None, moment_horizons=None, density_vars=None,
                     density_cuts=None, density_bins=64, density_trace=(0, 1), acf_vars=None, acf_lags=255, quantile_vars=None,
-                    quantile_probs=(0.05, 0.5, 0.95), **kwargs):
+                    quantile_probs=(0.05, 0.5, 0.95), ergodic=False, **kwargs):
     """Batched estimatemodel over many expanding windows (one GPU call).
 
     Window w uses sampleRange = startIndex:endIndices[w], endIndex = endIndices[w]; the
@@ -492,7 +495,11 @@ def estimatewindows(rawdata, dates, endIndices, startIndex=1, keep_draws=False, 
     and dropped likewise.
     quantile_vars: names among mu, sig2, pi_end, A, fcast -> BatchResult.quantiles, {var: ChainQuantiles}: per window and column
     the exact quantiles at quantile_probs (at most 16) with the draws that bracket them, selected on the device from the
-    5-digit-rounded draws (_lib.chain_quantiles); the draw arrays are fetched and dropped likewise."""
+    5-digit-rounded draws (_lib.chain_quantiles); the draw arrays are fetched and dropped likewise.
+    ergodic=True -> BatchResult.ergodic, the dict of _lib.unpack_ergodic: per window the mean and variance over the good draws
+    of the stationary regime law, the expected durations and the long-run mean and variance of the series (the limit of
+    pi_end A^h), computed on the device from the 5-digit-rounded draws (_lib.ergodic_moments); mu, sig2 and A are fetched and
+    dropped likewise."""
     if startIndex != 1:
         raise ValueError("windows must start at index 1 (see estopt)")
     acf_vars, density_vars = _draw_vars("acf_vars", acf_vars), _draw_vars("density_vars", density_vars)
@@ -527,6 +534,8 @@ def estimatewindows(rawdata, dates, endIndices, startIndex=1, keep_draws=False, 
             want += tuple(acf_vars)
         if quantile_vars is not None:
             want += tuple(quantile_vars)
+        if ergodic:
+            want += ("mu", "sig2", "A")
         want = tuple(k for k in _lib.DRAW_KEYS if k in want) or False
     res = _lib.estimate_batch_host(Y, Tw, o0.D, o0.burnin, o0.Nrun, tuple(o0.horizons), yreal, seed=o0.seed,
                                    device=device, want_draws=want, window_ids=window_ids, want_corr=corr)
@@ -559,6 +568,8 @@ def estimatewindows(rawdata, dates, endIndices, startIndex=1, keep_draws=False, 
         res["quantiles"] = {var: ChainQuantiles(var, _density_columns(o0, var), quantile_probs,
                                                 _lib.chain_quantiles(res[var], quantile_probs, device=device))
                             for var in quantile_vars}
+    if ergodic:
+        res["ergodic"] = _lib.ergodic_moments(res["mu"], res["sig2"], res["A"], device=device)
     return BatchResult(opts, res, keep_draws)
 
 
@@ -1645,4 +1656,116 @@ def write_chain_quantiles(path, dates, q):
                 rows.append([str(d), name, _fmt(p)] + [_fmt(getattr(q, k)[w, c, i]) for k in _lib.ORD_FIELDS] +
                             [str(int(q.count[w, c])), str(int(q.nan[w, c]))])
     _write_csv(path, ["date", "column", "prob"] + list(_lib.ORD_FIELDS) + ["count", "nan"], rows)
+    return path
+
+
+# ------------------------------------------------- ergodic regime law, durations, long-run moments --
+
+def _ergodic_columns(means, vars_, trans):
+    """The per-draw columns (C, n), C = 2K + 2, of hmcg_ergodic_moments from the cells of one date's files -- means, vars_
+    (n, K), trans (n, K * K) in the file's column order (trans_i_j, i fastest) -- in numpy by the rule of
+    include/hmcg_ergodic.h: the stationary law by the GTH elimination on the off-diagonal cells (the diagonal is never read),
+    dur = 1 / the off-diagonal row sum, the long-run mean and variance; one rounded operation per step, in the header's order."""
+    n, K = means.shape
+    A = np.asarray(trans, dtype=np.float64).reshape(n, K, K).transpose(2, 1, 0)             # A[i, j, d], row i the from-state
+    P = [[None if i == j else A[i, j].copy() for j in range(K)] for i in range(K)]
+    mu, s2 = np.asarray(means, dtype=np.float64).T, np.asarray(vars_, dtype=np.float64).T
+    with np.errstate(all="ignore"):
+        dur = []
+        for i in range(K):
+            cells = [P[i][j] for j in range(K) if j != i]
+            s = cells[0]
+            for c in cells[1:]:
+                s = s + c
+            dur.append(1.0 / s)
+        for m in range(K - 1, 0, -1):
+            S = P[m][0]
+            for j in range(1, m):
+                S = S + P[m][j]
+            for i in range(m):
+                P[i][m] = P[i][m] / S
+            for i in range(m):
+                for j in range(m):
+                    if i != j:
+                        P[i][j] = P[i][j] + P[i][m] * P[m][j]
+        x = [np.ones(n)]
+        for j in range(1, K):
+            t = x[0] * P[0][j]
+            for i in range(1, j):
+                t = t + x[i] * P[i][j]
+            x.append(t)
+        tot = x[0]
+        for k in range(1, K):
+            tot = tot + x[k]
+        pi = [xk / tot for xk in x]
+        mean = pi[0] * mu[0]
+        for k in range(1, K):
+            mean = mean + pi[k] * mu[k]
+        within = pi[0] * s2[0]
+        for k in range(1, K):
+            within = within + pi[k] * s2[k]
+        between = None
+        for k in range(K):
+            e = mu[k] - mean
+            t = pi[k] * (e * e)
+            between = t if between is None else between + t
+        return np.array(pi + dur + [mean, within + between])
+
+
+def _ergodic_pool(cols):
+    """out (C, 2) and n (2,) of hmcg_ergodic_moments from one window's per-draw columns (C, n): mean and variance over the good
+    draws (all C values finite) about the pivot, the columns of draw 0 when it is good and zeros otherwise."""
+    good = np.isfinite(cols).all(axis=0)
+    g = int(good.sum())
+    piv = cols[:, 0] if good[0] else np.zeros(cols.shape[0])
+    with np.errstate(all="ignore"):
+        a = cols[:, good] - piv[:, None]
+        S1, S2, gg = a.sum(axis=1), (a * a).sum(axis=1), np.float64(g)
+        out = np.stack([piv + S1 / gg, (S2 - S1 * S1 / gg) / (gg - 1.0)], axis=1)
+    return out, np.array([g, cols.shape[1] - g], dtype=np.int64)
+
+
+def calcergodic(datadir, dates, result=None, cols=False):
+    """The limit h -> infinity of the regime weights pi_end A^h, per end date: the stationary (ergodic) law of the regimes, the
+    expected duration of each regime, and the long-run mean and variance of the series, each as the mean and the variance over
+    the draws -- where inflation settles, against which a 12-month forecast is read.  Per draw the law comes from the GTH
+    elimination on the off-diagonal cells of the transition matrix (exact to a few roundings on nearly reducible and on
+    rounded matrices, where a linear solve is not); a draw with a non-finite column (an absorbing state) is left out and counted.
+
+    result=None: every date's `filtered_means_`, `filtered_variances_` and `filtered_trans_probs_<date>.csv` are read back
+    and evaluated on the host in numpy; no GPU is touched.  cols=True adds "cols" (n_dates, 2K + 2, n), the per-draw columns.
+    result = a BatchResult of estimatewindows(..., ergodic=True): the values were computed on the device from the rounded
+    draws; every date must be one of the result's end dates.
+    Returns (dates, e): the dict of _lib.unpack_ergodic over the dates."""
+    dates = [str(d) for d in dates]
+    if result is not None:
+        e = getattr(result, "ergodic", None)
+        if e is None:
+            raise ValueError("result carries no ergodic moments (estimatewindows(..., ergodic=True))")
+        idx = _rows_of(result, dates)
+        return dates, {k: v[idx] for k, v in e.items()}
+    outs, ns, cls, K = [], [], [], 0
+    for date in dates:
+        means, vars_, trans = (_cells(datadir, stem, date)[1] for stem in ("filtered_means", "filtered_variances", "filtered_trans_probs"))
+        K = means.shape[1]
+        c = _ergodic_columns(means, vars_, trans)
+        o, n = _ergodic_pool(c)
+        outs.append(o), ns.append(n), cls.append(c)
+    if not dates:
+        return dates, {}
+    return dates, _lib.unpack_ergodic(np.array(outs), np.array(ns), K, np.array(cls) if cols else None)
+
+
+def write_ergodic(path, dates, e):
+    """`date,column,mean,variance,good,bad`: one row per end date and per-draw column (pi1.., dur1.., mean, variance) of the
+    dict calcergodic returns.  Our layout: the reference writes no such file."""
+    K = e["pi_mean"].shape[1]
+    names = _lib.erg_names(K)
+    rows = []
+    for w, d in enumerate(dates):
+        mean = list(e["pi_mean"][w]) + list(e["dur_mean"][w]) + [e["mean_mean"][w], e["variance_mean"][w]]
+        var = list(e["pi_var"][w]) + list(e["dur_var"][w]) + [e["mean_var"][w], e["variance_var"][w]]
+        for c, name in enumerate(names):
+            rows.append([str(d), name, _fmt(mean[c]), _fmt(var[c]), str(int(e["good"][w])), str(int(e["bad"][w]))])
+    _write_csv(path, ["date", "column", "mean", "variance", "good", "bad"], rows)
     return path

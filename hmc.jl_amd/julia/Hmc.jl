@@ -23,7 +23,8 @@
 # chain_density: the binned chain densities and running means plots/mcplots.jl and plots/timeseriesplots.jl draw
 # (hmcg_chain_density).  calcess / chain_autocorr: autocovariances, integrated autocorrelation time, effective sample size,
 # Monte-Carlo standard error and split-R-hat of the draws (hmcg_chain_autocorr; no reference script).  calcquantiles /
-# chain_quantiles: the exact median and credible limits of the draws by selection (hmcg_chain_quantiles).  runaggregate /
+# chain_quantiles: the exact median and credible limits of the draws by selection (hmcg_chain_quantiles).  calcergodic /
+# ergodic_moments: the stationary regime law, durations and long-run moments of the draws (hmcg_ergodic_moments).  runaggregate /
 # calcdispersion of the reference work unchanged on the files written here (same names, columns and float text).
 #
 # Reference lines mirrored: estopt src/Hmc.jl:17-73, accessors :85-107, makedate :573-582,
@@ -189,6 +190,17 @@ struct hmcg_quantiles                 # include/hmcg_order.h (the companion head
     Q::Int32
     flags::Int32
     probs::NTuple{16,Float64}
+end
+const HMCG_ERG_ROUND5 = Int32(1)
+struct hmcg_ergodic                   # include/hmcg_ergodic.h (a companion header): ergodic law, durations, long-run moments
+    struct_size::Int32
+    W::Int32
+    K::Int32
+    device::Int32
+    nd::Int64
+    nd_ld::Int64
+    flags::Int32
+    reserved::Int32
 end
 
 last_error() = unsafe_string(ccall((:hmcg_last_error, LIBHMCG), Cstring, ()))
@@ -685,6 +697,61 @@ function calcquantiles(opts::Vector{estopt}, var::Symbol=:μ; probs=(0.05, 0.5, 
     pick(s) = var == :πe ? s.πb[:, 1, :] : getfield(s, var)
     x = cat((pick(s) for s in samples)...; dims=var == :A ? 4 : 3)
     return ([enddate(o) for o in opts], chain_quantiles(x; probs=probs, device=device)...)
+end
+
+# ---- ergodic regime law, durations and long-run moments of the draws (include/hmcg_ergodic.h; no reference script; not run) --------
+_ergodic(W, K, nd, ld, device, round5) =
+    hmcg_ergodic(Int32(sizeof(hmcg_ergodic)), Int32(W), Int32(K), Int32(device), Int64(nd), Int64(ld), round5 ? HMCG_ERG_ROUND5 : Int32(0), Int32(0))
+
+"""
+    ergodic_moments(μ, σ, A; cols=false, device=0, round5=true) -> (out (2, 2K + 2, W), n (2, W), cols (nrun, 2K + 2, W) or nothing)
+
+hmcg_ergodic_moments over host draw arrays in the layouts estimatewindows fills -- μ, σ (nrun, K, W), A (nrun, K, K, W): per
+draw the stationary law of the regimes (GTH elimination on the off-diagonal cells; the diagonal of A is never read), the
+expected durations and the long-run mean and variance, the limit of πe A^h; out = their mean and variance over the good
+draws (every column finite), n = the good draws and the rest; cols = the per-draw columns, in the layout chain_quantiles,
+chain_density and chain_autocorr take.
+"""
+function ergodic_moments(μ::Array{Float64,3}, σ::Array{Float64,3}, A::Array{Float64,4}; cols::Bool=false, device::Integer=0,
+                         round5::Bool=true)
+    nrun, K, W = size(μ)
+    C = 2K + 2
+    out = Array{Float64}(undef, 2, C, W)
+    n = Array{Int64}(undef, 2, W)
+    cl = cols ? Array{Float64}(undef, nrun, C, W) : nothing
+    pc = cols ? pointer(cl) : Ptr{Float64}(C_NULL)
+    rc = GC.@preserve μ σ A out n cl ccall((:hmcg_ergodic_moments, LIBHMCG), Cint,
+        (Ref{hmcg_ergodic}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Cvoid}),
+        _ergodic(W, K, nrun, nrun, device, round5), μ, σ, A, pc, out, n, C_NULL)
+    rc == 0 || error("libhmcgibbs rc=$rc: $(last_error())")
+    return out, n, cl
+end
+
+"""
+    ergodic_moments_device(W, K, nd, ld, dμ, dσ, dA, dcols, dout, dn; device=0, round5=true, stream=C_NULL)
+
+hmcg_ergodic_moments_device over device pointers (dcols = C_NULL when the per-draw columns are not kept); enqueued on `stream`
+(C_NULL: the library's own) and not waited for.
+"""
+function ergodic_moments_device(W, K, nd, ld, dμ::Ptr{Float64}, dσ::Ptr{Float64}, dA::Ptr{Float64}, dcols::Ptr{Float64},
+                                dout::Ptr{Float64}, dn::Ptr{Int64}; device::Integer=0, round5::Bool=true, stream::Ptr{Cvoid}=C_NULL)
+    rc = ccall((:hmcg_ergodic_moments_device, LIBHMCG), Cint,
+               (Ref{hmcg_ergodic}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int64}, Ptr{Cvoid}, Ptr{Cvoid}),
+               _ergodic(W, K, nd, ld, device, round5), dμ, dσ, dA, dcols, dout, dn, stream, C_NULL)
+    rc == 0 || error("libhmcgibbs rc=$rc: $(last_error())")
+    return nothing
+end
+
+"""
+    calcergodic(opts; cols=false, device=0) -> (dates, out, n, cols)
+
+Estimates the windows and takes the ergodic law, durations and long-run moments of their draws on the device.
+"""
+function calcergodic(opts::Vector{estopt}; cols::Bool=false, device::Integer=0)
+    samples, _, _ = estimatewindows(opts; device=device)
+    cat3(f) = cat((f(s) for s in samples)...; dims=3)
+    A = cat((s.A for s in samples)...; dims=4)
+    return ([enddate(o) for o in opts], ergodic_moments(cat3(s -> s.μ), cat3(s -> s.σ), A; cols=cols, device=device)...)
 end
 
 function _summary_rows(datadir, stem)
