@@ -45,6 +45,13 @@ ORD_MAXQ = 16                   # HMCG_ORD_MAXQ: probabilities of one call
 ORD_STRIDE = 4                  # HMCG_ORD_STRIDE: doubles per (window, column, probability)
 ORD_FIELDS = ("value", "lo", "hi", "g")
 ERG_ROUND5 = 1                  # include/hmcg_ergodic.h
+FAN_ROUND5 = 1                  # include/hmcg_fan.h
+FAN_MAXP = 16                   # HMCG_FAN_MAXP: probabilities of one call
+FAN_MAXROUNDS = 10              # HMCG_FAN_MAXROUNDS
+FAN_ROUNDS_DEFAULT = 4          # what rounds = 0 means
+FAN_STRIDE = 5                  # HMCG_FAN_STRIDE: doubles per (window, horizon, probability)
+FAN_FIELDS = ("quantile", "lo", "hi", "Flo", "Fhi")
+FAN_NAN, FAN_UNREACHED, FAN_FLAT = 1, 2, 4
 
 
 def erg_cols(K):
@@ -147,6 +154,17 @@ class Ergodic(C.Structure):
 
 ERGODIC_EXPORTS = ("hmcg_ergodic_moments", "hmcg_ergodic_moments_device")
 
+
+# include/hmcg_fan.h:
+class Fan(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("W", C.c_int32), ("K", C.c_int32), ("device", C.c_int32),
+                ("nd", C.c_int64), ("nd_ld", C.c_int64), ("n_h", C.c_int32), ("n_p", C.c_int32),
+                ("horizons", C.c_int32 * HMCG_MAXH), ("rounds", C.c_int32), ("flags", C.c_int32),
+                ("probs", C.c_double * FAN_MAXP), ("reserved", C.c_int64)]
+
+
+FAN_EXPORTS = ("hmcg_predictive_quantiles", "hmcg_predictive_quantiles_device")
+
 _LIB = None
 
 
@@ -195,7 +213,7 @@ def load():
                             "this package has no CPU fallback" % SO_PATH)
         _share_torch_hip_runtime()
         L = C.CDLL(SO_PATH)
-        for name in EXPORTS + ORDER_EXPORTS + ERGODIC_EXPORTS:
+        for name in EXPORTS + ORDER_EXPORTS + ERGODIC_EXPORTS + FAN_EXPORTS:
             getattr(L, name).restype = C.c_int
         L.hmcg_last_error.restype, L.hmcg_shutdown.restype = C.c_char_p, None
         _LIB = L
@@ -803,6 +821,61 @@ def ergodic_moments_device(erg, dmu, dsig2, dA, dcols, dout, dn, stream=None, ti
     per-draw columns are not kept); erg: make_ergodic(...).  Enqueued on `stream` (None: the library's own).  Returns the
     Timing struct when timed (the call then waits for completion), else None."""
     return _device_call(load().hmcg_ergodic_moments_device, erg, (dmu, dsig2, dA, dcols, dout, dn), stream, timed)
+
+
+def make_fan(W, K, nd, nd_ld, probs, horizons=(0,), rounds=0, device=0, round5=True):
+    """hmcg_fan of a call.  More than HMCG_MAXH horizons or FAN_MAXP probabilities raise here; every other rule is the library's
+    (HMCG_E_BADARG).  rounds: 1..FAN_MAXROUNDS, 0 for the default of 4."""
+    probs = tuple(float(q) for q in probs)
+    if len(probs) > FAN_MAXP:
+        raise ValueError("at most %d probabilities" % FAN_MAXP)
+    if len(horizons) > HMCG_MAXH:
+        raise ValueError("at most %d horizons" % HMCG_MAXH)
+    p = Fan()
+    p.struct_size = C.sizeof(Fan)
+    p.W, p.K, p.device, p.nd, p.nd_ld = int(W), int(K), int(device), int(nd), int(nd_ld)
+    p.n_h, p.n_p, p.rounds, p.flags = len(horizons), len(probs), int(rounds), FAN_ROUND5 if round5 else 0
+    for j, h in enumerate(horizons):
+        p.horizons[j] = int(h)
+    for i, q in enumerate(probs):
+        p.probs[i] = q
+    return p
+
+
+def unpack_fan(out, rng, flag):
+    """The three output blocks of hmcg_predictive_quantiles -- out (W, n_h, n_p, 5), range (W, 2), flag (W, n_h, n_p) int32 -- as
+    a dict: quantile, lo, hi (the last bracket), Flo, Fhi (the computed CDF at its ends), each (W, n_h, n_p); range (W, 2), the
+    40-standard-deviation reach of the window's components; flag (FAN_NAN | FAN_UNREACHED | FAN_FLAT)."""
+    out = np.asarray(out)
+    res = {name: out[..., i].copy() for i, name in enumerate(FAN_FIELDS)}
+    res["range"], res["flag"] = np.asarray(rng).copy(), np.asarray(flag).copy()
+    return res
+
+
+def predictive_quantiles(mu, sig2, pi_end, A, probs, horizons=(0,), rounds=0, nd=None, device=0, round5=True, timing=None):
+    """hmcg_predictive_quantiles over host (numpy) draw arrays in the C-ABI layouts -- mu/sig2/pi_end (W, K, nd), A (W, K, K, nd)
+    with A[w, j, i, d] = draw d of A[i, j] (None when every horizon is 0) -- as estimate_batch_host returns them, over their first
+    nd draws (default: all).  Per window, horizon and probability p the quantile of the predictive law, the mixture of nd * K
+    normals whose CDF predictive_cdf_host evaluates: the median, the forecast bands of a fan chart, value-at-risk levels.  The
+    CDF is inverted by grid refinement, `rounds` rounds (default 4: |F(q) - p| below 1e-10).  round5 (default): every input is
+    first rounded to 5 digits, as the cells of the per-draw CSV files are.  Returns the dict of unpack_fan.  timing: a Timing to
+    fill."""
+    (mu, sig2, pi_end), A, (W, K, ld) = _state_draws(A, mu=mu, sig2=sig2, pi_end=pi_end)
+    nd = ld if nd is None else int(nd)
+    p = make_fan(W, K, nd, ld, probs, horizons, rounds, device, round5)
+    out = np.zeros((W, p.n_h, p.n_p, FAN_STRIDE))
+    rng = np.zeros((W, 2))
+    flag = np.zeros((W, p.n_h, p.n_p), dtype=np.int32)
+    _check(load().hmcg_predictive_quantiles(C.byref(p), _np_ptr(mu), _np_ptr(sig2), _np_ptr(pi_end), _np_ptr(A), _np_ptr(out),
+                                            _np_ptr(rng), _np_ptr(flag), _tm(timing)))
+    return unpack_fan(out, rng, flag)
+
+
+def predictive_quantiles_device(fan, dmu, dsig2, dpi_end, dA, dout, drange, dflag, stream=None, timed=False):
+    """hmcg_predictive_quantiles_device over raw device pointers (ints, e.g. torch tensor.data_ptr(); dA 0 / None when every
+    horizon is 0); fan: make_fan(...).  Enqueued on `stream` (None: the library's own).  Returns the Timing struct when timed
+    (the call then waits for completion), else None."""
+    return _device_call(load().hmcg_predictive_quantiles_device, fan, (dmu, dsig2, dpi_end, dA, dout, drange, dflag), stream, timed)
 
 
 def format_float(x):

@@ -40,6 +40,7 @@
 #include "autocorr.hpp"
 #include "order.hpp"
 #include "ergodic.hpp"
+#include "fan.hpp"
 
 namespace {
 
@@ -135,6 +136,7 @@ struct DeviceCtx {
     Arena dens;                    // device entry of the chain densities: the piece sums, pivots and range keys
     Arena acf;                     // device entry of the autocorrelations: the running lag sums, pivots and edge values
     Arena erg;                     // device entry of the ergodic moments: the slab sums and pivots
+    Arena fan;                     // device entry of the predictive quantiles: the slab sums
     hmcg_hostutil::ScatterPool pool;              // host entries: helpers for the scatter into the caller's arrays
 };
 DeviceCtx g_ctx[HMCG_MAXDEV];
@@ -237,6 +239,7 @@ void destroy_context(DeviceCtx& c)
     c.dens.release();
     c.acf.release();
     c.erg.release();
+    c.fan.release();
     c.pool.stop();
     c.stream = c.copy = nullptr;
     c.ready = false;
@@ -1642,6 +1645,106 @@ int erg_host(DeviceCtx& c, const hmcg_ergodic* p, const double* mu, const double
     return ring.report({W, 256, 0}, (int)ring.uploads + 1);
 }
 
+// ---- predictive quantiles of the regime mixture (fan.hip; argument rules, work area and the arithmetic outside the CDF:
+// fan_plan.hpp; slab / chunk cut: stat_plan.hpp; ABI: include/hmcg_fan.h) -------------------------------------------------------------
+
+hmcg_host::FanArgs fan_args(const hmcg_fan* p)
+{
+    hmcg_host::FanArgs a{};
+    a.W = p->W; a.K = p->K; a.n_h = p->n_h; a.n_p = p->n_p;
+    for (int j = 0; j < HMCG_MAXH; ++j) a.horizons[j] = j < p->n_h ? p->horizons[j] : 0;
+    for (int i = 0; i < HMCG_FAN_MAXP; ++i) a.probs[i] = i < p->n_p ? p->probs[i] : 0.0;
+    a.round5 = (p->flags & HMCG_FAN_ROUND5) != 0;
+    a.nslab_total = pred_slabs(p->nd);
+    return a;
+}
+
+StatShape fan_shape(const hmcg_fan* p) { return {p->W, 0, (int32_t)fan_lds_bytes(p->K, p->n_h, fan_max_horizon(*p) > 0)}; }
+
+int fan_device(DeviceCtx& c, const hmcg_fan* p, const double* dmu, const double* dsig2, const double* dpi_end, const double* dA, double* dout,
+               double* drange, int32_t* dflag, hipStream_t stream, hmcg_timing* timing)
+{
+    const size_t work = sizeof(double) * fan_part_doubles(p->W, p->nd, p->n_h, p->n_p);
+    const int R = fan_rounds(*p);
+    return stat_device(c, c.fan, work, stream, timing, fan_shape(p), 2 + 2 * R, [&]() -> int {
+        hmcg_host::FanArgs a = fan_args(p);
+        a.mu = dmu; a.sig2 = dsig2; a.pi_end = dpi_end; a.A = dA; a.out = dout; a.range = drange; a.flag = dflag;
+        a.part = reinterpret_cast<double*>(c.fan.base);
+        a.nd = p->nd; a.nd_ld = p->nd_ld; a.slab0 = 0;
+        HIP_TRY(launch_fan_range(a, stream));
+        HIP_TRY(launch_fan_range_finalize(a, stream));
+        for (int r = 1; r <= R; ++r) {
+            HIP_TRY(launch_fan_eval(a, r, stream));
+            HIP_TRY(launch_fan_step(a, r, r == R, p->nd, stream));
+        }
+        return 0;
+    });
+}
+
+// Host entry on one device: R + 1 passes of the upload ring, which keeps its position from one pass to the next -- the range
+// pass (mu and sig2 alone), then one pass per round, each followed on the compute stream by the kernel that closes it.  The
+// brackets stay on the device between the passes; out, range and flag come back once, at the end.
+int fan_host(DeviceCtx& c, const hmcg_fan* p, const double* mu, const double* sig2, const double* pi_end, const double* A, double* out,
+             double* range, int32_t* flag, hmcg_timing* timing)
+{
+    const bool with_A = fan_max_horizon(*p) > 0;
+    const size_t WK = (size_t)p->W * (size_t)p->K, ld = (size_t)p->nd_ld;
+    const int ncol = fan_columns(*p), R = fan_rounds(*p);
+    UploadRing ring(c, p->nd, p->W, ncol, timing);
+    const size_t n_q = (size_t)p->W * (size_t)p->n_h * (size_t)p->n_p;
+    const size_t b_out = sizeof(double) * n_q * HMCG_FAN_STRIDE, b_range = sizeof(double) * (size_t)p->W * 2, b_flag = sizeof(int32_t) * n_q;
+    Layout io;
+    const size_t o_out = io.add(b_out), o_range = io.add(b_range), o_flag = io.add(b_flag);
+    int rc = ring.alloc(io, sizeof(double) * fan_part_doubles(p->W, p->nd, p->n_h, p->n_p), (size_t)p->W * (size_t)ncol * (size_t)ring.cdraws);
+    if (rc) return rc;
+    hmcg_host::FanArgs a = fan_args(p);
+    a.part = reinterpret_cast<double*>(ring.work);
+    a.out = reinterpret_cast<double*>(ring.dev + o_out); a.range = reinterpret_cast<double*>(ring.dev + o_range);
+    a.flag = reinterpret_cast<int32_t*>(ring.dev + o_flag);
+    auto place = [&](const PredChunk& ch, double* db) {
+        const size_t o_col = WK * (size_t)ch.n;
+        a.mu = db; a.sig2 = db + o_col; a.pi_end = db + 2 * o_col; a.A = with_A ? db + 3 * o_col : nullptr;
+        a.nd = ch.n; a.nd_ld = ch.n; a.slab0 = ch.d0 / PRED_SLAB;
+    };
+    // packed chunk of the range pass: mu | sig2, each [W][K][ch.n]
+    rc = ring.run(
+        [&](const PredChunk& ch, double* pb) {
+            double* e = pack_columns(mu, WK, ld, ch.d0, (size_t)ch.n, pb);
+            e = pack_columns(sig2, WK, ld, ch.d0, (size_t)ch.n, e);
+            return (size_t)(e - pb);
+        },
+        [&](const PredChunk& ch, double* db, hipStream_t s) -> int {
+            place(ch, db);
+            HIP_TRY(launch_fan_range(a, s));
+            return 0;
+        });
+    if (rc) return rc;
+    HIP_TRY(launch_fan_range_finalize(a, c.stream));
+    // packed chunk of a round: mu | sig2 | pi_end | A, each [W][columns][ch.n]
+    for (int r = 1; r <= R; ++r) {
+        rc = ring.run(
+            [&](const PredChunk& ch, double* pb) {
+                double* e = pack_columns(mu, WK, ld, ch.d0, (size_t)ch.n, pb);
+                e = pack_columns(sig2, WK, ld, ch.d0, (size_t)ch.n, e);
+                e = pack_columns(pi_end, WK, ld, ch.d0, (size_t)ch.n, e);
+                if (with_A) e = pack_columns(A, WK * (size_t)p->K, ld, ch.d0, (size_t)ch.n, e);
+                return (size_t)(e - pb);
+            },
+            [&](const PredChunk& ch, double* db, hipStream_t s) -> int {
+                place(ch, db);
+                HIP_TRY(launch_fan_eval(a, r, s));
+                return 0;
+            });
+        if (rc) return rc;
+        HIP_TRY(launch_fan_step(a, r, r == R, p->nd, c.stream));
+    }
+    if ((rc = ring.fetch(0, io.total))) return rc;
+    memcpy(out, ring.pin + o_out, b_out);
+    memcpy(range, ring.pin + o_range, b_range);
+    memcpy(flag, ring.pin + o_flag, b_flag);
+    return ring.report(fan_shape(p), (int)ring.uploads + 1 + R);
+}
+
 // The prologue of a compute entry on one device.  The argument check comes first and needs no device: a caller on a machine
 // without one still gets the argument errors.  Then the context of p->device, its lock, the device made current, and body(context).
 template <class P, class Check, class Body>
@@ -1853,6 +1956,22 @@ int hmcg_ergodic_moments(const hmcg_ergodic* p, const double* mu, const double* 
 {
     return entry(p, [&](char* msg, size_t nmsg) { return check_ergodic(p, mu, sig2, A, out, n, msg, nmsg); },
                  [&](DeviceCtx& c) { return erg_host(c, p, mu, sig2, A, cols, out, n, timing); });
+}
+
+int hmcg_predictive_quantiles_device(const hmcg_fan* p, const double* dmu, const double* dsig2, const double* dpi_end, const double* dA,
+                                     double* dout, double* drange, int32_t* dflag, void* stream, hmcg_timing* timing)
+{
+    return entry(p, [&](char* msg, size_t nmsg) { return check_fan(p, dmu, dsig2, dpi_end, dA, dout, drange, dflag, msg, nmsg); },
+                 [&](DeviceCtx& c) {
+        return fan_device(c, p, dmu, dsig2, dpi_end, dA, dout, drange, dflag, stream ? (hipStream_t)stream : c.stream, timing);
+    });
+}
+
+int hmcg_predictive_quantiles(const hmcg_fan* p, const double* mu, const double* sig2, const double* pi_end, const double* A, double* out,
+                              double* range, int32_t* flag, hmcg_timing* timing)
+{
+    return entry(p, [&](char* msg, size_t nmsg) { return check_fan(p, mu, sig2, pi_end, A, out, range, flag, msg, nmsg); },
+                 [&](DeviceCtx& c) { return fan_host(c, p, mu, sig2, pi_end, A, out, range, flag, timing); });
 }
 
 }  // extern "C"

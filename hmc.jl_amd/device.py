@@ -226,6 +226,25 @@ class DevicePanel:
                                          out["cols"].data_ptr() if cols else 0, out["out"].data_ptr(), out["n"].data_ptr(), None, timed)
         return self._done(tm, timed, out)
 
+    def fan(self, probs, horizons=(0,), rounds=0, timed=False, round5=True):
+        """Quantiles of the predictive regime mixture from the panel's own HBM draws (hmcg_predictive_quantiles_device): per
+        window, horizon and probability the quantile of the law whose CDF predictive_cdf evaluates -- the median, the forecast
+        bands of a fan chart, value-at-risk levels --, by `rounds` rounds of grid refinement (0: the default, 4).  Returns a
+        dict of tensors: out (W, n_h, n_p, 5) = quantile, lo, hi, Flo, Fhi, range (W, 2) and flag (W, n_h, n_p) int32;
+        _lib.unpack_fan names the parts of their numpy copies.  Enqueued on the library stream behind `run`; with timed=True
+        the call waits and last_timing holds the HIP-event time, otherwise call sync() before reading the tensors."""
+        self._draws("fan")
+        torch = self.torch
+        hz = tuple(int(h) for h in horizons)
+        fan = _lib.make_fan(self.W, self.K, self.nrun, self.nrun, probs, hz, rounds, self.device_index, round5)
+        out = {"out": torch.empty((self.W, fan.n_h, fan.n_p, _lib.FAN_STRIDE), dtype=torch.float64, device=self.dev),
+               "range": torch.empty((self.W, 2), dtype=torch.float64, device=self.dev),
+               "flag": torch.empty((self.W, fan.n_h, fan.n_p), dtype=torch.int32, device=self.dev)}
+        tm = _lib.predictive_quantiles_device(fan, self.mu.data_ptr(), self.sig2.data_ptr(), self.pi_end.data_ptr(),
+                                              self.A.data_ptr() if any(h > 0 for h in hz) else 0, out["out"].data_ptr(),
+                                              out["range"].data_ptr(), out["flag"].data_ptr(), None, timed)
+        return self._done(tm, timed, out)
+
     def sync(self):
         """Wait for the library stream (untimed runs are asynchronous)."""
         self.torch.cuda.synchronize(self.dev)

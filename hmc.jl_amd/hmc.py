@@ -26,6 +26,9 @@ ABI.  Names, argument meaning and result layout follow the reference:
                         or from the device); write_chain_quantiles
     calcergodic         no reference script: the stationary regime law, expected durations and long-run mean and variance of
                         the draws, the limit of pi_end A^h (from the files or from the device); write_ergodic
+    calcfan             no reference script (calc_cdfs.jl only plots `finverse`): quantiles of the predictive regime mixture --
+                        median, forecast bands, value at risk -- per end date and horizon (from the files or from the
+                        device); write_fan
 
 New (the reference batches by launching one SLURM task per window,
 slurmscripts/base_estimation.sh:5): `estimatewindows`, one call for many windows.
@@ -446,6 +449,7 @@ class BatchResult:
         self.autocorr = res.get("autocorr")    # with acf_vars: {var: ChainAutocorr}
         self.quantiles = res.get("quantiles")  # with quantile_vars: {var: ChainQuantiles}
         self.ergodic = res.get("ergodic")      # with ergodic=True: the dict of _lib.unpack_ergodic, one row per window
+        self.fan = res.get("fan")              # with fan_probs: the dict of _lib.unpack_fan plus probs, horizons, rounds
         self._res = res if keep_draws else None
 
     def samples(self, w):
@@ -467,7 +471,7 @@ def _draw_vars(name, vars_):
 def estimatewindows(rawdata, dates, endIndices, startIndex=1, keep_draws=False, device=0, window_ids=None, corr=False,
                     cdf_grid=None, cdf_horizons=(0,), bias_horizon=None, moment_horizons=None, density_vars=None,
                     density_cuts=None, density_bins=64, density_trace=(0, 1), acf_vars=None, acf_lags=255, quantile_vars=None,
-                    quantile_probs=(0.05, 0.5, 0.95), ergodic=False, **kwargs):
+                    quantile_probs=(0.05, 0.5, 0.95), ergodic=False, fan_probs=None, fan_horizons=(0,), fan_rounds=0, **kwargs):
     """Batched estimatemodel over many expanding windows (one GPU call).
 
     Window w uses sampleRange = startIndex:endIndices[w], endIndex = endIndices[w]; the
@@ -499,7 +503,12 @@ def estimatewindows(rawdata, dates, endIndices, startIndex=1, keep_draws=False, 
     ergodic=True -> BatchResult.ergodic, the dict of _lib.unpack_ergodic: per window the mean and variance over the good draws
     of the stationary regime law, the expected durations and the long-run mean and variance of the series (the limit of
     pi_end A^h), computed on the device from the 5-digit-rounded draws (_lib.ergodic_moments); mu, sig2 and A are fetched and
-    dropped likewise."""
+    dropped likewise.
+    fan_probs: at most 16 probabilities strictly inside (0, 1) -> BatchResult.fan, the dict of _lib.unpack_fan (quantile, lo, hi,
+    Flo, Fhi (W, n_h, n_p), range, flag) with probs, horizons and rounds: per window, horizon of fan_horizons and probability
+    the quantile of the predictive regime mixture -- the median, the bands of a fan chart, value-at-risk levels --, the CDF of
+    cdf_grid inverted on the device by fan_rounds rounds of grid refinement (0: the default, 4) from the 5-digit-rounded draws
+    (_lib.predictive_quantiles); its draw arrays are fetched and dropped likewise."""
     if startIndex != 1:
         raise ValueError("windows must start at index 1 (see estopt)")
     acf_vars, density_vars = _draw_vars("acf_vars", acf_vars), _draw_vars("density_vars", density_vars)
@@ -536,6 +545,8 @@ def estimatewindows(rawdata, dates, endIndices, startIndex=1, keep_draws=False, 
             want += tuple(quantile_vars)
         if ergodic:
             want += ("mu", "sig2", "A")
+        if fan_probs is not None:
+            want += ("mu", "sig2", "pi_end") + (("A",) if any(int(h) > 0 for h in fan_horizons) else ())
         want = tuple(k for k in _lib.DRAW_KEYS if k in want) or False
     res = _lib.estimate_batch_host(Y, Tw, o0.D, o0.burnin, o0.Nrun, tuple(o0.horizons), yreal, seed=o0.seed,
                                    device=device, want_draws=want, window_ids=window_ids, want_corr=corr)
@@ -570,6 +581,11 @@ def estimatewindows(rawdata, dates, endIndices, startIndex=1, keep_draws=False, 
                             for var in quantile_vars}
     if ergodic:
         res["ergodic"] = _lib.ergodic_moments(res["mu"], res["sig2"], res["A"], device=device)
+    if fan_probs is not None:
+        hz = tuple(int(h) for h in fan_horizons)
+        res["fan"] = _lib.predictive_quantiles(res["mu"], res["sig2"], res["pi_end"], res.get("A") if any(h > 0 for h in hz) else None,
+                                               fan_probs, hz, fan_rounds, device=device)
+        res["fan"].update(probs=tuple(float(q) for q in fan_probs), horizons=hz, rounds=int(fan_rounds))
     return BatchResult(opts, res, keep_draws)
 
 
@@ -1768,4 +1784,115 @@ def write_ergodic(path, dates, e):
         for c, name in enumerate(names):
             rows.append([str(d), name, _fmt(mean[c]), _fmt(var[c]), str(int(e["good"][w])), str(int(e["bad"][w]))])
     _write_csv(path, ["date", "column", "mean", "variance", "good", "bad"], rows)
+    return path
+
+
+# ------------------------------------------------------- predictive quantiles of the regime mixture: the fan chart --
+
+def _fan_points(lo, hi, M):
+    """y_0..y_M of a bracket: step = (hi - lo) / M, y_m = lo + m * step, y_M = hi (include/hmcg_fan.h)."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        step = (hi - lo) / float(M)
+        y = lo + np.arange(M + 1, dtype=np.float64) * step
+    y[M] = hi
+    return y
+
+
+def _fan_cell(y, F, p):
+    """The cell (lo, hi, Flo, Fhi) below the first point with F >= p, the last cell if there is none (a NaN compares false)."""
+    with np.errstate(invalid="ignore"):
+        hit = np.flatnonzero(F[1:] >= p)
+    m = int(hit[0]) + 1 if hit.size else len(y) - 1
+    return y[m - 1], y[m], F[m - 1], F[m]
+
+
+def _fan_from_cells(means, vars_, pis, trans, probs, horizons, rounds):
+    """out (n_h, n_p, 5), range (2,), flag (n_h, n_p) of hmcg_predictive_quantiles from the cells of one date's files -- (n, K)
+    each, trans (n, K * K) in the file's column order -- by the rules of include/hmcg_fan.h in float64 numpy: the range
+    pass, round 1 on 129 points, rounds of 31 interior points, the cell choice and the finish."""
+    n, K = means.shape
+    R = _lib.FAN_ROUNDS_DEFAULT if int(rounds) == 0 else int(rounds)
+    slab = _lib.PRED_SLAB
+    erfc = np.frompyfunc(math.erfc, 1, 1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        reach = 40.0 * np.sqrt(vars_)
+        lo0, hi0 = np.fmin.reduce((means - reach).reshape(-1)), np.fmax.reduce((means + reach).reshape(-1))
+        c = 1.0 / (1.4142135623730951 * np.sqrt(vars_))
+    out = np.empty((len(horizons), len(probs), _lib.FAN_STRIDE))
+    flag = np.zeros((len(horizons), len(probs)), dtype=np.int32)
+    for j, h in enumerate(horizons):
+        w = _omega(pis, trans, h)
+
+        def F(y):
+            with np.errstate(invalid="ignore", over="ignore"):
+                f = None
+                for k in range(K):
+                    ph = 0.5 * erfc(-((y[None, :] - means[:, k, None]) * c[:, k, None])).astype(np.float64)
+                    f = w[:, k, None] * ph if k == 0 else w[:, k, None] * ph + f
+                tot = np.zeros(len(y))
+                for s in range(0, n, slab):                                                 # draw order inside a slab, then slab order
+                    tot = tot + np.cumsum(f[s:s + slab], axis=0)[-1]
+                return tot / float(n)
+        y = _fan_points(lo0, hi0, 128)
+        Fy = F(y)
+        cells = [_fan_cell(y, Fy, p) for p in probs]
+        for _ in range(1, R):
+            ys = [_fan_points(b[0], b[1], 32) for b in cells]
+            Fi = F(np.concatenate([v[1:32] for v in ys])).reshape(len(probs), 31)
+            cells = [_fan_cell(ys[i], np.concatenate(([b[2]], Fi[i], [b[3]])), probs[i]) for i, b in enumerate(cells)]
+        for i, ((lo, hi, Flo, Fhi), p) in enumerate(zip(cells, probs)):
+            with np.errstate(invalid="ignore", over="ignore"):
+                if np.isnan(Flo) or np.isnan(Fhi):
+                    q, flag[j, i] = np.nan, _lib.FAN_NAN
+                elif not Fhi - Flo > 0.0:
+                    q, flag[j, i] = lo, _lib.FAN_FLAT
+                elif p > Fhi:
+                    q, flag[j, i] = hi, _lib.FAN_UNREACHED
+                else:
+                    q = lo + (hi - lo) * ((p - Flo) / (Fhi - Flo))
+            out[j, i] = (q, lo, hi, Flo, Fhi)
+    return out, np.array([lo0, hi0]), flag
+
+
+def calcfan(datadir, dates, probs, horizons=(0,), result=None, rounds=0):
+    """The fan chart: per end date, horizon and probability the quantile of the predictive law -- the mixture of the regimes'
+    normals pooled over the draws, whose CDF calccdfs evaluates on a grid -- so the median, the 68 % and 95 % forecast bands
+    (probs 0.025, 0.16, 0.5, 0.84, 0.975) and value-at-risk levels come as numbers and not off a plot of `finverse`.
+    horizons: 0 = the end date; h > 0 weights the states by pi_i A_i^h.  The CDF is inverted by grid refinement
+    (include/hmcg_fan.h): `rounds` rounds, 0 for the default of 4, which leaves |F(q) - p| below 1e-10.
+
+    result=None: every date's `filtered_means_`, `filtered_variances_`, `filtered_state_probs_<date>.csv` (and
+    `filtered_trans_probs_<date>.csv` with a horizon > 0) are read back and evaluated on the host in numpy; no GPU is touched.
+    result = a BatchResult of estimatewindows(..., fan_probs=probs, fan_horizons=horizons, fan_rounds=rounds): the quantiles
+    were computed on the device from the rounded draws; every date must be one of the result's end dates.
+    Returns (dates, f): the dict of _lib.unpack_fan over the dates, with probs, horizons and rounds."""
+    dates = [str(d) for d in dates]
+    probs, horizons = tuple(float(q) for q in probs), tuple(int(h) for h in horizons)
+    if result is not None:
+        f = getattr(result, "fan", None)
+        if f is None:
+            raise ValueError("result carries no predictive quantiles (estimatewindows(..., fan_probs=probs))")
+        if f["probs"] != probs or f["horizons"] != horizons or f["rounds"] != int(rounds):
+            raise ValueError("result was computed for other probabilities, horizons or rounds")
+        idx = _rows_of(result, dates)
+        return dates, {k: (v[idx] if isinstance(v, np.ndarray) else v) for k, v in f.items()}
+    if not 1 <= len(probs) <= _lib.FAN_MAXP or not all(0.0 < q < 1.0 for q in probs):
+        raise ValueError("probs: 1..%d probabilities strictly inside (0, 1)" % _lib.FAN_MAXP)
+    if not 0 <= int(rounds) <= _lib.FAN_MAXROUNDS:
+        raise ValueError("rounds outside 0..%d" % _lib.FAN_MAXROUNDS)
+    parts = [_fan_from_cells(*_mixture_cells(datadir, d, horizons), probs, horizons, rounds) for d in dates]
+    f = _lib.unpack_fan(np.array([o for o, _, _ in parts]).reshape(len(dates), len(horizons), len(probs), _lib.FAN_STRIDE),
+                        np.array([r for _, r, _ in parts]).reshape(len(dates), 2),
+                        np.array([g for _, _, g in parts], dtype=np.int32).reshape(len(dates), len(horizons), len(probs)))
+    f.update(probs=probs, horizons=horizons, rounds=int(rounds))
+    return dates, f
+
+
+def write_fan(path, dates, f):
+    """`date,horizon,p,quantile,lo,hi,flag`: one row per end date, horizon and probability of the dict calcfan returns, float
+    text as in the other files (_fmt).  Our layout: the reference writes no such file."""
+    rows = [[str(d), str(int(h)), _fmt(p), _fmt(f["quantile"][w, j, i]), _fmt(f["lo"][w, j, i]), _fmt(f["hi"][w, j, i]),
+             str(int(f["flag"][w, j, i]))]
+            for w, d in enumerate(dates) for j, h in enumerate(f["horizons"]) for i, p in enumerate(f["probs"])]
+    _write_csv(path, ["date", "horizon", "p", "quantile", "lo", "hi", "flag"], rows)
     return path

@@ -24,7 +24,8 @@
 # (hmcg_chain_density).  calcess / chain_autocorr: autocovariances, integrated autocorrelation time, effective sample size,
 # Monte-Carlo standard error and split-R-hat of the draws (hmcg_chain_autocorr; no reference script).  calcquantiles /
 # chain_quantiles: the exact median and credible limits of the draws by selection (hmcg_chain_quantiles).  calcergodic /
-# ergodic_moments: the stationary regime law, durations and long-run moments of the draws (hmcg_ergodic_moments).  runaggregate /
+# ergodic_moments: the stationary regime law, durations and long-run moments of the draws (hmcg_ergodic_moments).  calcfan /
+# predictive_quantiles: the median, forecast bands and value-at-risk levels of the predictive mixture (hmcg_predictive_quantiles).  runaggregate /
 # calcdispersion of the reference work unchanged on the files written here (same names, columns and float text).
 #
 # Reference lines mirrored: estopt src/Hmc.jl:17-73, accessors :85-107, makedate :573-582,
@@ -201,6 +202,24 @@ struct hmcg_ergodic                   # include/hmcg_ergodic.h (a companion head
     nd_ld::Int64
     flags::Int32
     reserved::Int32
+end
+const HMCG_FAN_ROUND5 = Int32(1)
+const HMCG_FAN_MAXP = 16
+const HMCG_FAN_STRIDE = 5
+struct hmcg_fan                       # include/hmcg_fan.h (a companion header): quantiles of the predictive regime mixture
+    struct_size::Int32
+    W::Int32
+    K::Int32
+    device::Int32
+    nd::Int64
+    nd_ld::Int64
+    n_h::Int32
+    n_p::Int32
+    horizons::NTuple{8,Int32}
+    rounds::Int32
+    flags::Int32
+    probs::NTuple{16,Float64}
+    reserved::Int64
 end
 
 last_error() = unsafe_string(ccall((:hmcg_last_error, LIBHMCG), Cstring, ()))
@@ -752,6 +771,85 @@ function calcergodic(opts::Vector{estopt}; cols::Bool=false, device::Integer=0)
     cat3(f) = cat((f(s) for s in samples)...; dims=3)
     A = cat((s.A for s in samples)...; dims=4)
     return ([enddate(o) for o in opts], ergodic_moments(cat3(s -> s.μ), cat3(s -> s.σ), A; cols=cols, device=device)...)
+end
+
+# ---- quantiles of the predictive regime mixture: the fan chart (include/hmcg_fan.h; no reference script; not run) ----------------
+function _fan(W, K, nd, ld, probs, horizons, rounds, device, round5)
+    length(probs) <= HMCG_FAN_MAXP || error("at most $HMCG_FAN_MAXP probabilities")
+    length(horizons) <= 8 || error("at most 8 horizons")
+    hz = ntuple(j -> j <= length(horizons) ? Int32(horizons[j]) : Int32(0), 8)
+    ps = ntuple(i -> i <= length(probs) ? Float64(probs[i]) : 0.0, 16)
+    return hmcg_fan(Int32(sizeof(hmcg_fan)), Int32(W), Int32(K), Int32(device), Int64(nd), Int64(ld), Int32(length(horizons)),
+                    Int32(length(probs)), hz, Int32(rounds), round5 ? HMCG_FAN_ROUND5 : Int32(0), ps, Int64(0))
+end
+
+"""
+    predictive_quantiles(μ, σ, πe, A, probs; horizons=(0,), rounds=0, device=0, round5=true)
+        -> (out (5, n_p, n_h, W), range (2, W), flag (n_p, n_h, W))
+
+hmcg_predictive_quantiles over host draw arrays in the layouts estimatewindows fills -- μ, σ, πe (nrun, K, W), A (nrun, K, K, W)
+or nothing when every horizon is 0: per window, horizon and probability the quantile of the predictive law, the mixture of
+nrun * K normals whose CDF predictive_cdf evaluates (the median, the forecast bands of a fan chart, value-at-risk levels), by
+`rounds` rounds of grid refinement (0: the default, 4).  out = quantile, lo, hi, Flo, Fhi; flag 1 = NaN, 2 = p not reached,
+4 = a flat last cell.
+"""
+function predictive_quantiles(μ::Array{Float64,3}, σ::Array{Float64,3}, πe::Array{Float64,3}, A::Union{Array{Float64,4},Nothing}, probs;
+                              horizons=(0,), rounds::Integer=0, device::Integer=0, round5::Bool=true)
+    nrun, K, W = size(μ)
+    out = Array{Float64}(undef, HMCG_FAN_STRIDE, length(probs), length(horizons), W)
+    rng = Array{Float64}(undef, 2, W)
+    flag = Array{Int32}(undef, length(probs), length(horizons), W)
+    pa = A === nothing ? Ptr{Float64}(C_NULL) : pointer(A)
+    rc = GC.@preserve μ σ πe A out rng flag ccall((:hmcg_predictive_quantiles, LIBHMCG), Cint,
+        (Ref{hmcg_fan}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Cvoid}),
+        _fan(W, K, nrun, nrun, probs, horizons, rounds, device, round5), μ, σ, πe, pa, out, rng, flag, C_NULL)
+    rc == 0 || error("libhmcgibbs rc=$rc: $(last_error())")
+    return out, rng, flag
+end
+
+"""
+    predictive_quantiles_device(W, K, nd, ld, probs, dμ, dσ, dπe, dA, dout, drange, dflag; horizons=(0,), rounds=0, device=0,
+                                round5=true, stream=C_NULL)
+
+hmcg_predictive_quantiles_device over device pointers (dA = C_NULL when every horizon is 0); enqueued on `stream` (C_NULL: the
+library's own) and not waited for.
+"""
+function predictive_quantiles_device(W, K, nd, ld, probs, dμ::Ptr{Float64}, dσ::Ptr{Float64}, dπe::Ptr{Float64}, dA::Ptr{Float64},
+                                     dout::Ptr{Float64}, drange::Ptr{Float64}, dflag::Ptr{Int32}; horizons=(0,), rounds::Integer=0,
+                                     device::Integer=0, round5::Bool=true, stream::Ptr{Cvoid}=C_NULL)
+    rc = ccall((:hmcg_predictive_quantiles_device, LIBHMCG), Cint,
+               (Ref{hmcg_fan}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Int32}, Ptr{Cvoid}, Ptr{Cvoid}),
+               _fan(W, K, nd, ld, probs, horizons, rounds, device, round5), dμ, dσ, dπe, dA, dout, drange, dflag, stream, C_NULL)
+    rc == 0 || error("libhmcgibbs rc=$rc: $(last_error())")
+    return nothing
+end
+
+"""
+    calcfan(opts, probs; horizons=(0,), rounds=0, device=0) -> (dates, out, range, flag)
+
+Estimates the windows and takes the quantiles of their predictive law on the device: the fan chart per end date and horizon.
+"""
+function calcfan(opts::Vector{estopt}, probs; horizons=(0,), rounds::Integer=0, device::Integer=0)
+    samples, _, _ = estimatewindows(opts; device=device)
+    cat3(f) = cat((f(s) for s in samples)...; dims=3)
+    A = any(h -> h > 0, horizons) ? cat((s.A for s in samples)...; dims=4) : nothing
+    μ, σ, πe = cat3(s -> s.μ), cat3(s -> s.σ), cat3(s -> s.πb[:, 1, :])
+    return ([enddate(o) for o in opts], predictive_quantiles(μ, σ, πe, A, probs; horizons=horizons, rounds=rounds, device=device)...)
+end
+
+"""
+    write_fan(path, dates, probs, horizons, out, flag)
+
+`date,horizon,p,quantile,lo,hi,flag`: one row per end date, horizon and probability.
+"""
+function write_fan(path, dates, probs, horizons, out, flag)
+    open(path, "w") do io
+        println(io, "date,horizon,p,quantile,lo,hi,flag")
+        for (w, d) in enumerate(dates), (j, h) in enumerate(horizons), (i, p) in enumerate(probs)
+            println(io, join((d, h, p, out[1, i, j, w], out[2, i, j, w], out[3, i, j, w], flag[i, j, w]), ','))
+        end
+    end
+    return path
 end
 
 function _summary_rows(datadir, stem)
