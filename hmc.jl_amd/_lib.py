@@ -52,6 +52,10 @@ FAN_ROUNDS_DEFAULT = 4          # what rounds = 0 means
 FAN_STRIDE = 5                  # HMCG_FAN_STRIDE: doubles per (window, horizon, probability)
 FAN_FIELDS = ("quantile", "lo", "hi", "Flo", "Fhi")
 FAN_NAN, FAN_UNREACHED, FAN_FLAT = 1, 2, 4
+SCORE_ROUND5 = 1                # include/hmcg_score.h
+SCORE_DRAWS_DEFAULT = 4096      # HMCG_SCORE_DRAWS_DEFAULT: used draws the default thinning leaves at most
+SCORE_STRIDE = 5                # HMCG_SCORE_STRIDE: doubles per (window, horizon)
+SCORE_FIELDS = ("crps", "e_abs", "e_pair", "pit", "pdf")
 
 
 def erg_cols(K):
@@ -165,6 +169,16 @@ class Fan(C.Structure):
 
 FAN_EXPORTS = ("hmcg_predictive_quantiles", "hmcg_predictive_quantiles_device")
 
+
+# include/hmcg_score.h:
+class Score(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("W", C.c_int32), ("K", C.c_int32), ("device", C.c_int32),
+                ("nd", C.c_int64), ("nd_ld", C.c_int64), ("n_h", C.c_int32), ("flags", C.c_int32),
+                ("horizons", C.c_int32 * HMCG_MAXH), ("stride", C.c_int64), ("reserved", C.c_int64)]
+
+
+SCORE_EXPORTS = ("hmcg_predictive_scores", "hmcg_predictive_scores_device")
+
 _LIB = None
 
 
@@ -213,7 +227,7 @@ def load():
                             "this package has no CPU fallback" % SO_PATH)
         _share_torch_hip_runtime()
         L = C.CDLL(SO_PATH)
-        for name in EXPORTS + ORDER_EXPORTS + ERGODIC_EXPORTS + FAN_EXPORTS:
+        for name in EXPORTS + ORDER_EXPORTS + ERGODIC_EXPORTS + FAN_EXPORTS + SCORE_EXPORTS:
             getattr(L, name).restype = C.c_int
         L.hmcg_last_error.restype, L.hmcg_shutdown.restype = C.c_char_p, None
         _LIB = L
@@ -876,6 +890,74 @@ def predictive_quantiles_device(fan, dmu, dsig2, dpi_end, dA, dout, drange, dfla
     horizon is 0); fan: make_fan(...).  Enqueued on `stream` (None: the library's own).  Returns the Timing struct when timed
     (the call then waits for completion), else None."""
     return _device_call(load().hmcg_predictive_quantiles_device, fan, (dmu, dsig2, dpi_end, dA, dout, drange, dflag), stream, timed)
+
+
+def score_thinning(nd, stride=0):
+    """(stride, n_u) of a score call over nd draws: the draws u * stride, u < n_u = ceil(nd / stride), are used; stride 0 is the
+    default, the smallest stride that leaves at most SCORE_DRAWS_DEFAULT draws."""
+    nd, stride = int(nd), int(stride)
+    if stride <= 0:
+        stride = max(1, -(-nd // SCORE_DRAWS_DEFAULT))
+    return stride, -(-nd // stride)
+
+
+def make_score(W, K, nd, nd_ld, horizons=(0,), stride=0, device=0, round5=True):
+    """hmcg_score of a call.  More than HMCG_MAXH horizons raise here; every other rule is the library's (HMCG_E_BADARG).
+    stride: every stride-th draw is used, 0 for the default thinning (at most 4 096 draws), 1 for the exact score."""
+    if len(horizons) > HMCG_MAXH:
+        raise ValueError("at most %d horizons" % HMCG_MAXH)
+    p = Score()
+    p.struct_size = C.sizeof(Score)
+    p.W, p.K, p.device, p.nd, p.nd_ld = int(W), int(K), int(device), int(nd), int(nd_ld)
+    p.n_h, p.flags, p.stride = len(horizons), SCORE_ROUND5 if round5 else 0, int(stride)
+    for j, h in enumerate(horizons):
+        p.horizons[j] = int(h)
+    return p
+
+
+def unpack_scores(out, yreal=None):
+    """The (W, n_h, 5) output block of hmcg_predictive_scores as a dict of (W, n_h) arrays: crps, e_abs = E|X - y|, e_pair =
+    E|X - X'| (the forecast's Gini mean difference), pit = F(y), pdf = F'(y); plus yreal (W, n_h) when given as (n_h, W)."""
+    out = np.asarray(out)
+    res = {name: out[..., i].copy() for i, name in enumerate(SCORE_FIELDS)}
+    if yreal is not None:
+        res["yreal"] = np.asarray(yreal).T.copy()
+    return res
+
+
+def _score_yreal(yreal, n_h, W):
+    """yreal as the (n_h, W) float64 block of the ABI; None: all unknown (NaN)."""
+    if yreal is None:
+        return np.full((n_h, W), np.nan)
+    yreal = np.ascontiguousarray(yreal, dtype=np.float64)
+    if yreal.shape != (n_h, W):
+        raise ValueError("yreal must have the shape (n_h, W) = (%d, %d)" % (n_h, W))
+    return yreal
+
+
+def predictive_scores(mu, sig2, pi_end, A, yreal, horizons=(0,), stride=0, nd=None, device=0, round5=True, timing=None):
+    """hmcg_predictive_scores over host (numpy) draw arrays in the C-ABI layouts -- mu/sig2/pi_end (W, K, nd), A (W, K, K, nd)
+    with A[w, j, i, d] = draw d of A[i, j] (None when every horizon is 0) -- as estimate_batch_host returns them, over their first
+    nd draws (default: all).  yreal (n_h, W): the realised value per horizon and window, NaN for unknown (None: all unknown).
+    Per window and horizon the continuous ranked probability score of the predictive law (the mixture of n_u * K normals whose
+    CDF predictive_cdf_host evaluates, n_u the draws the thinning leaves: score_thinning) against yreal, its two parts, the
+    probability integral transform and the predictive density at yreal.  round5 (default): every draw input is first rounded to
+    5 digits, as the cells of the per-draw CSV files are.  Returns the dict of unpack_scores.  timing: a Timing to fill."""
+    (mu, sig2, pi_end), A, (W, K, ld) = _state_draws(A, mu=mu, sig2=sig2, pi_end=pi_end)
+    nd = ld if nd is None else int(nd)
+    p = make_score(W, K, nd, ld, horizons, stride, device, round5)
+    yreal = _score_yreal(yreal, p.n_h, W)
+    out = np.zeros((W, p.n_h, SCORE_STRIDE))
+    _check(load().hmcg_predictive_scores(C.byref(p), _np_ptr(mu), _np_ptr(sig2), _np_ptr(pi_end), _np_ptr(A), _np_ptr(yreal),
+                                         _np_ptr(out), _tm(timing)))
+    return unpack_scores(out, yreal)
+
+
+def predictive_scores_device(score, dmu, dsig2, dpi_end, dA, dyreal, dout, stream=None, timed=False):
+    """hmcg_predictive_scores_device over raw device pointers (ints, e.g. torch tensor.data_ptr(); dA 0 / None when every horizon
+    is 0); score: make_score(...).  Enqueued on `stream` (None: the library's own).  Returns the Timing struct when timed (the
+    call then waits for completion), else None."""
+    return _device_call(load().hmcg_predictive_scores_device, score, (dmu, dsig2, dpi_end, dA, dyreal, dout), stream, timed)
 
 
 def format_float(x):

@@ -41,6 +41,7 @@
 #include "order.hpp"
 #include "ergodic.hpp"
 #include "fan.hpp"
+#include "score.hpp"
 
 namespace {
 
@@ -137,6 +138,7 @@ struct DeviceCtx {
     Arena acf;                     // device entry of the autocorrelations: the running lag sums, pivots and edge values
     Arena erg;                     // device entry of the ergodic moments: the slab sums and pivots
     Arena fan;                     // device entry of the predictive quantiles: the slab sums
+    Arena score;                   // device entry of the predictive scores: the components, weights, slab sums and pair partials
     hmcg_hostutil::ScatterPool pool;              // host entries: helpers for the scatter into the caller's arrays
 };
 DeviceCtx g_ctx[HMCG_MAXDEV];
@@ -240,6 +242,7 @@ void destroy_context(DeviceCtx& c)
     c.acf.release();
     c.erg.release();
     c.fan.release();
+    c.score.release();
     c.pool.stop();
     c.stream = c.copy = nullptr;
     c.ready = false;
@@ -1745,6 +1748,133 @@ int fan_host(DeviceCtx& c, const hmcg_fan* p, const double* mu, const double* si
     return ring.report(fan_shape(p), (int)ring.uploads + 1 + R);
 }
 
+// ---- proper scores of the predictive regime mixture (score.hip; thinning, tiles, work area, window groups, argument rules and
+// the per-term arithmetic: score_plan.hpp; ABI: include/hmcg_score.h) -----------------------------------------------------------
+
+hmcg_host::ScoreArgs score_args(const hmcg_score* p)
+{
+    hmcg_host::ScoreArgs a{};
+    a.K = p->K; a.n_h = p->n_h; a.n_u = score_used(*p);
+    for (int j = 0; j < HMCG_MAXH; ++j) a.horizons[j] = j < p->n_h ? p->horizons[j] : 0;
+    a.round5 = (p->flags & HMCG_SCORE_ROUND5) != 0;
+    a.yreal_ld = p->W;
+    return a;
+}
+
+StatShape score_shape(const hmcg_score* p) { return {p->W, SCORE_TP, (int32_t)score_lds_bytes(p->K, p->n_h, score_max_horizon(*p) > 0)}; }
+
+int score_launches(const hmcg_host::ScoreArgs& a, hipStream_t stream)
+{
+    HIP_TRY(launch_score_components(a, stream));
+    HIP_TRY(launch_score_pairs(a, stream));
+    HIP_TRY(launch_score_finish(a, stream));
+    return 0;
+}
+
+int score_device(DeviceCtx& c, const hmcg_score* p, const double* dmu, const double* dsig2, const double* dpi_end, const double* dA,
+                 const double* dyreal, double* dout, hipStream_t stream, hmcg_timing* timing)
+{
+    const size_t work = sizeof(double) * score_work_doubles(p->W, score_used(*p), p->K, p->n_h);
+    return stat_device(c, c.score, work, stream, timing, score_shape(p), 3, [&]() -> int {
+        hmcg_host::ScoreArgs a = score_args(p);
+        a.mu = dmu; a.sig2 = dsig2; a.pi_end = dpi_end; a.A = dA; a.yreal = dyreal; a.out = dout;
+        a.work = reinterpret_cast<double*>(c.score.base);
+        a.W = p->W; a.w0 = 0; a.stride = score_stride(p->nd, p->stride); a.nd_ld = p->nd_ld;
+        return score_launches(a, stream);
+    });
+}
+
+// Host entry on one device.  The pair pass needs a window's used draws resident, so this is not the draw-slab ring: only the
+// draws u * stride are read, packed with leading dimension n_u into pinned staging (per group: mu | sig2 | pi_end | A, each
+// [windows][columns][n_u]), and the windows go up in groups (score_plan.hpp), RING buffers deep: group g + 1 is packed and copied
+// while group g's kernels run.  Windows are independent and every group writes its own rows of out, fetched once at the end.
+int score_host(DeviceCtx& c, const hmcg_score* p, const double* mu, const double* sig2, const double* pi_end, const double* A,
+               const double* yreal, double* out, hmcg_timing* timing)
+{
+    const auto t_call = std::chrono::steady_clock::now();
+    const bool with_A = score_max_horizon(*p) > 0;
+    const long long n_u = score_used(*p), stride = score_stride(p->nd, p->stride);
+    const size_t K = (size_t)p->K, ld = (size_t)p->nd_ld;
+    const int ncol = score_columns(*p);
+    long long cap = 0;
+    if (const char* cenv = diag_env("HMCG_SCORE_GROUP_WINDOWS")) cap = atoll(cenv);
+    const int gw = score_group_windows(p->W, n_u, ncol, cap);
+    const int ngroups = (p->W + gw - 1) / gw;
+    const int nbuf = std::min<int>(RING, ngroups);
+    const size_t b_y = sizeof(double) * (size_t)p->n_h * (size_t)p->W, b_out = sizeof(double) * (size_t)p->W * (size_t)p->n_h * HMCG_SCORE_STRIDE;
+    Layout d, h;
+    const size_t o_y = d.add(b_y), o_out = d.add(b_out);
+    h.add(b_y); h.add(b_out);
+    const size_t o_work = d.add(sizeof(double) * score_work_doubles(gw, n_u, p->K, p->n_h));
+    size_t o_d[RING] = {}, o_p[RING] = {};
+    const size_t b_group = sizeof(double) * (size_t)gw * (size_t)ncol * (size_t)n_u;
+    for (int b = 0; b < nbuf; ++b) { o_d[b] = d.add(b_group); o_p[b] = h.add(b_group); }
+    if (c.dev.ensure(d.total) || c.pin.ensure(h.total)) {
+        set_err("workspace allocation failed (%zu B device, %zu B pinned)", d.total, h.total);
+        return HMCG_E_NOMEM;
+    }
+    memcpy(c.pin.base + o_y, yreal, b_y);
+    HIP_TRY(hipMemcpyAsync(c.dev.base + o_y, c.pin.base + o_y, b_y, hipMemcpyHostToDevice, c.stream));
+    Events tev;
+    hmcg_host::ScoreArgs a = score_args(p);
+    a.yreal = reinterpret_cast<const double*>(c.dev.base + o_y);
+    a.work = reinterpret_cast<double*>(c.dev.base + o_work);
+    a.stride = 1; a.nd_ld = n_u;
+    // every stride-th draw of `cols` columns from window w0 on, n windows of them
+    auto pack = [&](const double* src, size_t cols, int w0, int n, double* dst) {
+        for (size_t q = 0; q < (size_t)n * cols; ++q) {
+            const double* col = src + ((size_t)w0 * cols + q) * ld;
+            if (stride == 1) memcpy(dst, col, sizeof(double) * (size_t)n_u);
+            else for (long long u = 0; u < n_u; ++u) dst[u] = col[(size_t)u * (size_t)stride];
+            dst += n_u;
+        }
+        return dst;
+    };
+    int up = 0;
+    for (int w0 = 0; w0 < p->W; w0 += gw) {
+        const int n = std::min(gw, p->W - w0);
+        const int b = up % nbuf;
+        if (up >= nbuf) HIP_TRY(hipEventSynchronize(c.evk[b]));                 // the kernels that read this buffer pair are done
+        ++up;
+        double* pb = reinterpret_cast<double*>(c.pin.base + o_p[b]);
+        double* db = reinterpret_cast<double*>(c.dev.base + o_d[b]);
+        double* e = pack(mu, K, w0, n, pb);
+        e = pack(sig2, K, w0, n, e);
+        e = pack(pi_end, K, w0, n, e);
+        if (with_A) e = pack(A, K * K, w0, n, e);
+        HIP_TRY(hipMemcpyAsync(db, pb, sizeof(double) * (size_t)(e - pb), hipMemcpyHostToDevice, c.copy));
+        HIP_TRY(hipEventRecord(c.evc[b], c.copy));
+        HIP_TRY(hipStreamWaitEvent(c.stream, c.evc[b], 0));
+        hipEvent_t ev[2] = {};
+        if (timing) {
+            for (hipEvent_t& x : ev) { HIP_TRY(hipEventCreate(&x)); tev.ev.push_back(x); }
+            HIP_TRY(hipEventRecord(ev[0], c.stream));
+        }
+        const size_t o_col = (size_t)n * K * (size_t)n_u;
+        a.mu = db; a.sig2 = db + o_col; a.pi_end = db + 2 * o_col; a.A = with_A ? db + 3 * o_col : nullptr;
+        a.W = n; a.w0 = w0;
+        a.out = reinterpret_cast<double*>(c.dev.base + o_out) + (size_t)w0 * (size_t)p->n_h * HMCG_SCORE_STRIDE;
+        const int rc = score_launches(a, c.stream);
+        if (rc) return rc;
+        if (timing) HIP_TRY(hipEventRecord(ev[1], c.stream));
+        HIP_TRY(hipEventRecord(c.evk[b], c.stream));
+    }
+    HIP_TRY(hipMemcpyAsync(c.pin.base + o_out, c.dev.base + o_out, b_out, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    memcpy(out, c.pin.base + o_out, b_out);
+    if (timing) {
+        double kernel_ms = 0.0;
+        for (size_t i = 0; i + 1 < tev.ev.size(); i += 2) {
+            float ms = 0.f;
+            HIP_TRY(hipEventElapsedTime(&ms, tev.ev[i], tev.ev[i + 1]));
+            kernel_ms += ms;
+        }
+        const double call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
+        fill_stat_timing(timing, c, score_shape(p), kernel_ms, 3 * up, call_ms);
+    }
+    return 0;
+}
+
 // The prologue of a compute entry on one device.  The argument check comes first and needs no device: a caller on a machine
 // without one still gets the argument errors.  Then the context of p->device, its lock, the device made current, and body(context).
 template <class P, class Check, class Body>
@@ -1972,6 +2102,21 @@ int hmcg_predictive_quantiles(const hmcg_fan* p, const double* mu, const double*
 {
     return entry(p, [&](char* msg, size_t nmsg) { return check_fan(p, mu, sig2, pi_end, A, out, range, flag, msg, nmsg); },
                  [&](DeviceCtx& c) { return fan_host(c, p, mu, sig2, pi_end, A, out, range, flag, timing); });
+}
+
+int hmcg_predictive_scores_device(const hmcg_score* p, const double* dmu, const double* dsig2, const double* dpi_end, const double* dA,
+                                  const double* dyreal, double* dout, void* stream, hmcg_timing* timing)
+{
+    return entry(p, [&](char* msg, size_t nmsg) { return check_score(p, dmu, dsig2, dpi_end, dA, dyreal, dout, msg, nmsg); }, [&](DeviceCtx& c) {
+        return score_device(c, p, dmu, dsig2, dpi_end, dA, dyreal, dout, stream ? (hipStream_t)stream : c.stream, timing);
+    });
+}
+
+int hmcg_predictive_scores(const hmcg_score* p, const double* mu, const double* sig2, const double* pi_end, const double* A,
+                           const double* yreal, double* out, hmcg_timing* timing)
+{
+    return entry(p, [&](char* msg, size_t nmsg) { return check_score(p, mu, sig2, pi_end, A, yreal, out, msg, nmsg); },
+                 [&](DeviceCtx& c) { return score_host(c, p, mu, sig2, pi_end, A, yreal, out, timing); });
 }
 
 }  // extern "C"

@@ -245,6 +245,27 @@ class DevicePanel:
                                               out["range"].data_ptr(), out["flag"].data_ptr(), None, timed)
         return self._done(tm, timed, out)
 
+    def scores(self, horizons, yreal=None, stride=0, timed=False, round5=True):
+        """Proper scores of the predictive regime mixture from the panel's own HBM draws (hmcg_predictive_scores_device): per
+        window and horizon the continuous ranked probability score against yreal, its parts E|X - y| and E|X - X'|, the
+        probability integral transform F(y) and the predictive density at y.  yreal: (n_h, W), NaN for unknown (None: all
+        unknown, which leaves e_pair, the forecast's Gini mean difference).  stride: every stride-th kept draw is used; 0: the
+        default thinning to at most 4 096 draws, 1: the exact score, whose cost grows with the square of nrun * K.  Returns a
+        (W, n_h, 5) tensor = crps, e_abs, e_pair, pit, pdf; _lib.unpack_scores names the parts of its numpy copy.  Enqueued on
+        the library stream behind `run`; with timed=True the call waits and last_timing holds the HIP-event time, otherwise
+        call sync() before reading the tensor."""
+        self._draws("scores")
+        torch = self.torch
+        hz = tuple(int(h) for h in horizons)
+        sc = _lib.make_score(self.W, self.K, self.nrun, self.nrun, hz, stride, self.device_index, round5)
+        y = torch.from_numpy(_lib._score_yreal(yreal, sc.n_h, self.W)).to(self.dev)             # a blocking copy
+        out = torch.empty((self.W, sc.n_h, _lib.SCORE_STRIDE), dtype=torch.float64, device=self.dev)
+        tm = _lib.predictive_scores_device(sc, self.mu.data_ptr(), self.sig2.data_ptr(), self.pi_end.data_ptr(),
+                                           self.A.data_ptr() if any(h > 0 for h in hz) else 0, y.data_ptr(), out.data_ptr(), None, timed)
+        if not timed:                       # a timed call has waited; otherwise the enqueued kernels may still read it
+            self._held.append(y)
+        return self._done(tm, timed, out)
+
     def sync(self):
         """Wait for the library stream (untimed runs are asynchronous)."""
         self.torch.cuda.synchronize(self.dev)

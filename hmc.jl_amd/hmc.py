@@ -29,6 +29,10 @@ ABI.  Names, argument meaning and result layout follow the reference:
     calcfan             no reference script (calc_cdfs.jl only plots `finverse`): quantiles of the predictive regime mixture --
                         median, forecast bands, value at risk -- per end date and horizon (from the files or from the
                         device); write_fan
+    calcscores          no reference script (the reference verifies the point forecast alone): the continuous ranked probability
+                        score of the predictive regime mixture against the realised value, the probability integral transform
+                        and the predictive density, per end date and horizon (from the files or from the device);
+                        write_scores, scoresummary
 
 New (the reference batches by launching one SLURM task per window,
 slurmscripts/base_estimation.sh:5): `estimatewindows`, one call for many windows.
@@ -450,6 +454,7 @@ class BatchResult:
         self.quantiles = res.get("quantiles")  # with quantile_vars: {var: ChainQuantiles}
         self.ergodic = res.get("ergodic")      # with ergodic=True: the dict of _lib.unpack_ergodic, one row per window
         self.fan = res.get("fan")              # with fan_probs: the dict of _lib.unpack_fan plus probs, horizons, rounds
+        self.scores = res.get("scores")        # with score_horizons: the dict of _lib.unpack_scores plus horizons, stride
         self._res = res if keep_draws else None
 
     def samples(self, w):
@@ -471,7 +476,8 @@ def _draw_vars(name, vars_):
 def estimatewindows(rawdata, dates, endIndices, startIndex=1, keep_draws=False, device=0, window_ids=None, corr=False,
                     cdf_grid=None, cdf_horizons=(0,), bias_horizon=None, moment_horizons=None, density_vars=None,
                     density_cuts=None, density_bins=64, density_trace=(0, 1), acf_vars=None, acf_lags=255, quantile_vars=None,
-                    quantile_probs=(0.05, 0.5, 0.95), ergodic=False, fan_probs=None, fan_horizons=(0,), fan_rounds=0, **kwargs):
+                    quantile_probs=(0.05, 0.5, 0.95), ergodic=False, fan_probs=None, fan_horizons=(0,), fan_rounds=0,
+                    score_horizons=None, score_stride=0, **kwargs):
     """Batched estimatemodel over many expanding windows (one GPU call).
 
     Window w uses sampleRange = startIndex:endIndices[w], endIndex = endIndices[w]; the
@@ -508,7 +514,13 @@ def estimatewindows(rawdata, dates, endIndices, startIndex=1, keep_draws=False, 
     Flo, Fhi (W, n_h, n_p), range, flag) with probs, horizons and rounds: per window, horizon of fan_horizons and probability
     the quantile of the predictive regime mixture -- the median, the bands of a fan chart, value-at-risk levels --, the CDF of
     cdf_grid inverted on the device by fan_rounds rounds of grid refinement (0: the default, 4) from the 5-digit-rounded draws
-    (_lib.predictive_quantiles); its draw arrays are fetched and dropped likewise."""
+    (_lib.predictive_quantiles); its draw arrays are fetched and dropped likewise.
+    score_horizons: horizons -> BatchResult.scores, the dict of _lib.unpack_scores (crps, e_abs, e_pair, pit, pdf, yreal, each
+    (W, n_h)) with horizons and stride: per window and horizon h the continuous ranked probability score of the predictive
+    regime mixture against the realised value y[end - 1 + h] of the series itself (NaN past its end: crps, e_abs, pit and pdf are
+    then NaN), the probability integral transform and the predictive density there, computed on the device from the
+    5-digit-rounded draws (_lib.predictive_scores) over every score_stride-th draw (0: thinned to at most 4 096 draws, 1: every
+    draw, at a cost that grows with the square of Nrun * K); its draw arrays are fetched and dropped likewise."""
     if startIndex != 1:
         raise ValueError("windows must start at index 1 (see estopt)")
     acf_vars, density_vars = _draw_vars("acf_vars", acf_vars), _draw_vars("density_vars", density_vars)
@@ -547,6 +559,8 @@ def estimatewindows(rawdata, dates, endIndices, startIndex=1, keep_draws=False, 
             want += ("mu", "sig2", "A")
         if fan_probs is not None:
             want += ("mu", "sig2", "pi_end") + (("A",) if any(int(h) > 0 for h in fan_horizons) else ())
+        if score_horizons is not None:
+            want += ("mu", "sig2", "pi_end") + (("A",) if any(int(h) > 0 for h in score_horizons) else ())
         want = tuple(k for k in _lib.DRAW_KEYS if k in want) or False
     res = _lib.estimate_batch_host(Y, Tw, o0.D, o0.burnin, o0.Nrun, tuple(o0.horizons), yreal, seed=o0.seed,
                                    device=device, want_draws=want, window_ids=window_ids, want_corr=corr)
@@ -586,6 +600,12 @@ def estimatewindows(rawdata, dates, endIndices, startIndex=1, keep_draws=False, 
         res["fan"] = _lib.predictive_quantiles(res["mu"], res["sig2"], res["pi_end"], res.get("A") if any(h > 0 for h in hz) else None,
                                                fan_probs, hz, fan_rounds, device=device)
         res["fan"].update(probs=tuple(float(q) for q in fan_probs), horizons=hz, rounds=int(fan_rounds))
+    if score_horizons is not None:
+        hz = tuple(int(h) for h in score_horizons)
+        yr = np.array([_yreal_row(rawdata, o.endIndex, hz) for o in opts]).reshape(W, len(hz)).T
+        res["scores"] = _lib.predictive_scores(res["mu"], res["sig2"], res["pi_end"], res.get("A") if any(h > 0 for h in hz) else None,
+                                               yr, hz, score_stride, device=device)
+        res["scores"].update(horizons=hz, stride=int(score_stride))
     return BatchResult(opts, res, keep_draws)
 
 
@@ -1896,3 +1916,109 @@ def write_fan(path, dates, f):
             for w, d in enumerate(dates) for j, h in enumerate(f["horizons"]) for i, p in enumerate(f["probs"])]
     _write_csv(path, ["date", "horizon", "p", "quantile", "lo", "hi", "flag"], rows)
     return path
+
+
+# ------------------------------------------- proper scores of the predictive regime mixture: CRPS, PIT, density --
+
+def _erf(x):
+    """erf of a float64 array: scipy's where it is installed, math.erf element by element otherwise."""
+    try:
+        from scipy.special import erf
+    except ImportError:
+        return np.frompyfunc(math.erf, 1, 1)(x).astype(np.float64)
+    return erf(x)
+
+
+def _score_a(m, S2):
+    """a(m, S2) = E|N(m, S2)| with the steps of include/hmcg_score.h; S2 == 0 gives |m|."""
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        s = np.sqrt(S2)
+        t = m * (1.0 / (1.4142135623730951 * s))
+        a = m * _erf(t) + (s * 0.7978845608028654) * np.exp(-(t * t))
+    return np.where(S2 == 0.0, np.abs(m), a)
+
+
+def _scores_from_cells(means, vars_, pis, trans, horizons, yreal, stride, chunk=1 << 21):
+    """out (n_h, 5) of hmcg_predictive_scores from the cells of one date's files -- (n, K) each, trans (n, K * K) in the file's
+    column order -- by the formulas of include/hmcg_score.h in float64 numpy over every stride-th draw.  The pair sum runs over
+    blocks of rows of the component square of at most `chunk` pairs, so memory stays bounded."""
+    n, K = means.shape
+    st, n_u = _lib.score_thinning(n, stride)
+    means, vars_, pis = means[::st], vars_[::st], pis[::st]
+    trans = None if trans is None else trans[::st]
+    m, v = means.reshape(-1), vars_.reshape(-1)
+    N = m.size
+    ws = [_omega(pis, trans, h).reshape(-1) for h in horizons]
+    pair = np.zeros(len(horizons))
+    rows = max(1, int(chunk) // N)
+    for i0 in range(0, N, rows):
+        a = _score_a(m[i0:i0 + rows, None] - m[None, :], v[i0:i0 + rows, None] + v[None, :])
+        for j, w in enumerate(ws):
+            pair[j] += w[i0:i0 + rows] @ (a @ w)
+    out = np.empty((len(horizons), _lib.SCORE_STRIDE))
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        c = 1.0 / (1.4142135623730951 * np.sqrt(v))
+        for j, w in enumerate(ws):
+            y = float(yreal[j])
+            t = (y - m) * c
+            e_abs = float(np.sum(w * _score_a(y - m, v))) / n_u
+            e_pair = float(pair[j]) / (float(n_u) * float(n_u))
+            pit = float(np.sum(w * (0.5 * (1.0 + _erf(t))))) / n_u
+            pdf = float(np.sum(w * ((c * 0.5641895835477563) * np.exp(-(t * t))))) / n_u
+            out[j] = (e_abs - 0.5 * e_pair, e_abs, e_pair, pit, pdf)
+    return out
+
+
+def calcscores(datadir, dates, horizons, yreal, stride=0, result=None):
+    """How good the density forecasts were: per end date and horizon the continuous ranked probability score
+    CRPS(F, y) = E|X - y| - 0.5 E|X - X'| of the predictive law F -- the mixture of the regimes' normals pooled over the draws,
+    whose CDF calccdfs evaluates -- against the realised value y, with its two parts, the probability integral transform F(y)
+    and the predictive density F'(y).  horizons: 0 = the end date; h > 0 weights the states by pi_i A_i^h.  yreal
+    (n_dates, n_h): the realised values, NaN for unknown.  stride: every stride-th draw is used (0: thinned to at most 4 096
+    draws, 1: every draw); the pair sum costs (draws used * K)^2 / 2 terms per date.
+
+    result=None: every date's `filtered_means_`, `filtered_variances_`, `filtered_state_probs_<date>.csv` (and
+    `filtered_trans_probs_<date>.csv` with a horizon > 0) are read back and evaluated on the host in numpy; no GPU is touched.
+    result = a BatchResult of estimatewindows(..., score_horizons=horizons, score_stride=stride): the scores were computed on
+    the device from the rounded draws against the series' own values (yreal is then not read; the result's is returned); every
+    date must be one of the result's end dates.
+    Returns (dates, s): the dict of _lib.unpack_scores over the dates, with horizons and stride."""
+    dates = [str(d) for d in dates]
+    horizons = tuple(int(h) for h in horizons)
+    if result is not None:
+        sc = getattr(result, "scores", None)
+        if sc is None:
+            raise ValueError("result carries no scores (estimatewindows(..., score_horizons=horizons))")
+        if sc["horizons"] != horizons or sc["stride"] != int(stride):
+            raise ValueError("result was computed for other horizons or another stride")
+        idx = _rows_of(result, dates)
+        return dates, {k: (v[idx] if isinstance(v, np.ndarray) else v) for k, v in sc.items()}
+    if not 1 <= len(horizons) <= _lib.HMCG_MAXH or int(stride) < 0:
+        raise ValueError("horizons: 1..%d of them; stride >= 0" % _lib.HMCG_MAXH)
+    yreal = np.asarray(yreal, dtype=np.float64).reshape(len(dates), len(horizons))
+    outs = [_scores_from_cells(*_mixture_cells(datadir, d, horizons), horizons, yreal[w], stride) for w, d in enumerate(dates)]
+    sc = _lib.unpack_scores(np.array(outs).reshape(len(dates), len(horizons), _lib.SCORE_STRIDE), yreal.T)
+    sc.update(horizons=horizons, stride=int(stride))
+    return dates, sc
+
+
+def write_scores(path, dates, sc):
+    """`date,horizon,yreal,crps,e_abs,e_pair,pit,pdf`: one row per end date and horizon of the dict calcscores returns, float
+    text as in the other files (_fmt).  Our layout: the reference writes no such file."""
+    rows = [[str(d), str(int(h)), _fmt(sc["yreal"][w, j])] + [_fmt(sc[name][w, j]) for name in _lib.SCORE_FIELDS]
+            for w, d in enumerate(dates) for j, h in enumerate(sc["horizons"])]
+    _write_csv(path, ["date", "horizon", "yreal"] + list(_lib.SCORE_FIELDS), rows)
+    return path
+
+
+def scoresummary(sc, bins=10):
+    """Per horizon over the windows with a known realised value (a finite crps): mean_crps (n_h,), count (n_h,) int64 and
+    pit_hist (n_h, bins) int64, the PIT histogram on equal bins of [0, 1] (a PIT of 1 counts in the last), flat for a
+    calibrated forecast."""
+    crps, pit = np.asarray(sc["crps"], dtype=np.float64), np.asarray(sc["pit"], dtype=np.float64)
+    known = np.isfinite(crps)
+    count = known.sum(axis=0).astype(np.int64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        mean = np.where(known, crps, 0.0).sum(axis=0) / count
+    hist = np.array([np.histogram(pit[known[:, j], j], bins=int(bins), range=(0.0, 1.0))[0] for j in range(crps.shape[1])], dtype=np.int64)
+    return {"mean_crps": mean, "count": count, "pit_hist": hist.reshape(crps.shape[1], int(bins))}

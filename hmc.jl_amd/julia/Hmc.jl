@@ -25,7 +25,9 @@
 # Monte-Carlo standard error and split-R-hat of the draws (hmcg_chain_autocorr; no reference script).  calcquantiles /
 # chain_quantiles: the exact median and credible limits of the draws by selection (hmcg_chain_quantiles).  calcergodic /
 # ergodic_moments: the stationary regime law, durations and long-run moments of the draws (hmcg_ergodic_moments).  calcfan /
-# predictive_quantiles: the median, forecast bands and value-at-risk levels of the predictive mixture (hmcg_predictive_quantiles).  runaggregate /
+# predictive_quantiles: the median, forecast bands and value-at-risk levels of the predictive mixture (hmcg_predictive_quantiles).  calcscores /
+# predictive_scores: CRPS, probability integral transform and density of the predictive mixture at the realised value
+# (hmcg_predictive_scores; no reference script).  runaggregate /
 # calcdispersion of the reference work unchanged on the files written here (same names, columns and float text).
 #
 # Reference lines mirrored: estopt src/Hmc.jl:17-73, accessors :85-107, makedate :573-582,
@@ -202,6 +204,22 @@ struct hmcg_ergodic                   # include/hmcg_ergodic.h (a companion head
     nd_ld::Int64
     flags::Int32
     reserved::Int32
+end
+const HMCG_SCORE_ROUND5 = Int32(1)
+const HMCG_SCORE_DRAWS_DEFAULT = 4096
+const HMCG_SCORE_STRIDE = 5
+struct hmcg_score                     # include/hmcg_score.h (a companion header): proper scores of the predictive regime mixture
+    struct_size::Int32
+    W::Int32
+    K::Int32
+    device::Int32
+    nd::Int64
+    nd_ld::Int64
+    n_h::Int32
+    flags::Int32
+    horizons::NTuple{8,Int32}
+    stride::Int64
+    reserved::Int64
 end
 const HMCG_FAN_ROUND5 = Int32(1)
 const HMCG_FAN_MAXP = 16
@@ -850,6 +868,108 @@ function write_fan(path, dates, probs, horizons, out, flag)
         end
     end
     return path
+end
+
+# ---- proper scores of the predictive regime mixture: CRPS, PIT, density (include/hmcg_score.h; no reference script; not run) ----
+function _score(W, K, nd, ld, horizons, stride, device, round5)
+    length(horizons) <= 8 || error("at most 8 horizons")
+    hz = ntuple(j -> j <= length(horizons) ? Int32(horizons[j]) : Int32(0), 8)
+    return hmcg_score(Int32(sizeof(hmcg_score)), Int32(W), Int32(K), Int32(device), Int64(nd), Int64(ld), Int32(length(horizons)),
+                      round5 ? HMCG_SCORE_ROUND5 : Int32(0), hz, Int64(stride), Int64(0))
+end
+
+"(stride, n_u) of a score call over nd draws: stride 0 is the smallest stride that leaves at most 4 096 used draws."
+function score_thinning(nd::Integer, stride::Integer=0)
+    st = stride > 0 ? stride : max(1, cld(nd, HMCG_SCORE_DRAWS_DEFAULT))
+    return st, cld(nd, st)
+end
+
+"""
+    predictive_scores(μ, σ, πe, A, yreal; horizons=(0,), stride=0, device=0, round5=true) -> out (5, n_h, W)
+
+hmcg_predictive_scores over host draw arrays in the layouts estimatewindows fills -- μ, σ, πe (nrun, K, W), A (nrun, K, K, W) or
+nothing when every horizon is 0 -- and the realised values yreal (W, n_h), NaN for unknown: per window and horizon
+crps = E|X - y| - E|X - X'| / 2 of the predictive law (the mixture of the used draws' normals), e_abs, e_pair, pit = F(y) and
+pdf = F'(y).  stride: every stride-th draw is used (0: thinned to at most 4 096 draws, 1: the exact score).
+"""
+function predictive_scores(μ::Array{Float64,3}, σ::Array{Float64,3}, πe::Array{Float64,3}, A::Union{Array{Float64,4},Nothing},
+                           yreal::Matrix{Float64}; horizons=(0,), stride::Integer=0, device::Integer=0, round5::Bool=true)
+    nrun, K, W = size(μ)
+    size(yreal) == (W, length(horizons)) || error("yreal must be (W, n_h)")
+    out = Array{Float64}(undef, HMCG_SCORE_STRIDE, length(horizons), W)
+    pa = A === nothing ? Ptr{Float64}(C_NULL) : pointer(A)
+    rc = GC.@preserve μ σ πe A yreal out ccall((:hmcg_predictive_scores, LIBHMCG), Cint,
+        (Ref{hmcg_score}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}),
+        _score(W, K, nrun, nrun, horizons, stride, device, round5), μ, σ, πe, pa, yreal, out, C_NULL)
+    rc == 0 || error("libhmcgibbs rc=$rc: $(last_error())")
+    return out
+end
+
+"""
+    predictive_scores_device(W, K, nd, ld, dμ, dσ, dπe, dA, dyreal, dout; horizons=(0,), stride=0, device=0, round5=true,
+                             stream=C_NULL)
+
+hmcg_predictive_scores_device over device pointers (dA = C_NULL when every horizon is 0; dyreal [n_h][W], dout [W][n_h][5]);
+enqueued on `stream` (C_NULL: the library's own) and not waited for.
+"""
+function predictive_scores_device(W, K, nd, ld, dμ::Ptr{Float64}, dσ::Ptr{Float64}, dπe::Ptr{Float64}, dA::Ptr{Float64},
+                                  dyreal::Ptr{Float64}, dout::Ptr{Float64}; horizons=(0,), stride::Integer=0, device::Integer=0,
+                                  round5::Bool=true, stream::Ptr{Cvoid}=C_NULL)
+    rc = ccall((:hmcg_predictive_scores_device, LIBHMCG), Cint,
+               (Ref{hmcg_score}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Cvoid}, Ptr{Cvoid}),
+               _score(W, K, nd, ld, horizons, stride, device, round5), dμ, dσ, dπe, dA, dyreal, dout, stream, C_NULL)
+    rc == 0 || error("libhmcgibbs rc=$rc: $(last_error())")
+    return nothing
+end
+
+"""
+    calcscores(opts, rawdata; horizons=(0,), stride=0, device=0) -> (dates, yreal (W, n_h), out (5, n_h, W))
+
+Estimates the windows and scores their predictive laws on the device against the series' own values rawdata[endIndex + h]
+(NaN past its end).
+"""
+function calcscores(opts::Vector{estopt}, rawdata::Vector{Float64}; horizons=(0,), stride::Integer=0, device::Integer=0)
+    samples, _, _ = estimatewindows(opts; device=device)
+    cat3(f) = cat((f(s) for s in samples)...; dims=3)
+    A = any(h -> h > 0, horizons) ? cat((s.A for s in samples)...; dims=4) : nothing
+    μ, σ, πe = cat3(s -> s.μ), cat3(s -> s.σ), cat3(s -> s.πb[:, 1, :])
+    yreal = [o.endIndex + h <= length(rawdata) ? rawdata[o.endIndex + h] : NaN for o in opts, h in horizons]
+    return [enddate(o) for o in opts], yreal, predictive_scores(μ, σ, πe, A, yreal; horizons=horizons, stride=stride, device=device)
+end
+
+"""
+    write_scores(path, dates, horizons, yreal, out)
+
+`date,horizon,yreal,crps,e_abs,e_pair,pit,pdf`: one row per end date and horizon.
+"""
+function write_scores(path, dates, horizons, yreal, out)
+    open(path, "w") do io
+        println(io, "date,horizon,yreal,crps,e_abs,e_pair,pit,pdf")
+        for (w, d) in enumerate(dates), (j, h) in enumerate(horizons)
+            println(io, join((d, h, yreal[w, j], out[1, j, w], out[2, j, w], out[3, j, w], out[4, j, w], out[5, j, w]), ','))
+        end
+    end
+    return path
+end
+
+"""
+    scoresummary(out; bins=10) -> (mean_crps (n_h), count (n_h), pit_hist (bins, n_h))
+
+Per horizon over the windows with a known realised value (a finite crps): the mean CRPS, their count and the PIT histogram on
+equal bins of [0, 1] (a PIT of 1 counts in the last).
+"""
+function scoresummary(out::Array{Float64,3}; bins::Integer=10)
+    n_h = size(out, 2)
+    mean_crps, count, hist = fill(NaN, n_h), zeros(Int, n_h), zeros(Int, bins, n_h)
+    for j in 1:n_h
+        known = [w for w in 1:size(out, 3) if isfinite(out[1, j, w])]
+        count[j] = length(known)
+        isempty(known) || (mean_crps[j] = sum(out[1, j, w] for w in known) / length(known))
+        for w in known
+            hist[min(bins, 1 + floor(Int, out[4, j, w] * bins)), j] += 1
+        end
+    end
+    return mean_crps, count, hist
 end
 
 function _summary_rows(datadir, stem)
