@@ -7,11 +7,11 @@
 // with 129 points per (window, horizon) shared by every probability, then rounds of 31 interior points per (window, horizon,
 // probability), each dividing the bracket by 32.  Between two rounds the brackets live in `out` in HBM; nothing is read back.
 //
-// fan_eval_kernel has the tile shape of predictive_cdf_kernel: one block per (window, slab of PRED_SLAB draws, 128 items), a tile
-// of 64 draws staged in LDS as (mu, c) pairs with the weights of every horizon (HMCG_OMEGA_STEP), each thread walking the tile in
+// fan_eval_kernel is the tile of predictive_cdf_kernel (mixture_tile.hpp): one block per (window, slab of PRED_SLAB draws, 128
+// items), a tile of 64 draws staged in LDS as (mu, c) pairs with the weights of every horizon, each thread walking the tile in
 // draw order with ITS point: an item is (horizon, point) in round 1 and (horizon, probability, point) later, and its y comes from
-// the bracket table -- range[w] in round 1, out[w][j][i] later -- not from a grid.  The per-draw expression is predictive.hip's
-// to the letter, so an F computed here carries the bits hmcg_predictive_cdf gives for the same point.
+// the bracket table -- range[w] in round 1, out[w][j][i] later -- not from a grid.  Both kernels expand the one walk, so an F
+// computed here carries the bits hmcg_predictive_cdf gives for the same point.
 // fan_step_kernel, one block per (window, horizon): a thread per item adds the slab sums in slab order and divides by nd, then
 // a thread per probability chooses its cell and writes the next bracket; after the last round also q and the flag.
 // fan_range_kernel / fan_range_finalize_kernel: per-slab fmin / fmax of mu -+ 40 sd, then over the slabs.
@@ -20,15 +20,13 @@
 #include <stdint.h>
 
 #include "fan.hpp"
-#include "stat_device.hpp"
+#include "mixture_tile.hpp"
 
 namespace hmcg {
 
 using hmcg_host::FAN_M;
 using hmcg_host::FAN_M1;
 
-constexpr int FAN_TD = 64;           // draws per LDS tile
-constexpr int FAN_NT = 128;          // threads per block of the evaluation = items per block
 constexpr int FAN_RANGE_NT = 256;
 constexpr int FAN_STEP_NT = 256;
 constexpr int FAN_STEP_F = HMCG_FAN_MAXP * (FAN_M - 1);      // 496 >= 129: the most items of one (window, horizon)
@@ -99,16 +97,14 @@ struct FanEvalParams {
 };
 
 template <int K>
-__global__ __launch_bounds__(FAN_NT) void fan_eval_kernel(const FanEvalParams p)
+__global__ __launch_bounds__(MIXTILE_NT) void fan_eval_kernel(const FanEvalParams p)
 {
     extern __shared__ double fan_lds[];
     const int n_h = p.n_h;
-    double* MC = fan_lds;                                // [FAN_TD][K][2]: mu, c
-    double* Ws = MC + FAN_TD * K * 2;                    // [FAN_TD][n_h][K]: weights of every horizon
-    double* As = Ws + FAN_TD * n_h * K;                  // [K * K][FAN_TD]: transition draws (present with a horizon > 0)
+    HMCG_MIX_TILE_LDS(K, fan_lds, n_h, MC, Ws, As);
     const int tid = threadIdx.x;
     HMCG_STAT_SLAB(w, s, dbeg, dend, p.nslab, p.nd);
-    const int e = (int)blockIdx.y * FAN_NT + tid;        // this thread's item: horizon j, then the point within it
+    const int e = (int)blockIdx.y * MIXTILE_NT + tid;    // this thread's item: horizon j, then the point within it
     const bool live = e < p.items;
     const int j = live ? e / p.items_h : 0, l = live ? e - j * p.items_h : 0;
     double y;
@@ -125,55 +121,14 @@ __global__ __launch_bounds__(FAN_NT) void fan_eval_kernel(const FanEvalParams p)
     const double* pie = p.pi_end + (size_t)w * K * p.nd_ld;
     const double* At = p.A ? p.A + (size_t)w * K * K * p.nd_ld : nullptr;
     double acc = 0.0;
-    for (long long d0 = dbeg; d0 < dend; d0 += FAN_TD) {
-        const int nv = dend - d0 < FAN_TD ? (int)(dend - d0) : FAN_TD;
-        for (int q = tid; q < K * FAN_TD; q += FAN_NT) {
-            const int k = q / FAN_TD, dd = q - k * FAN_TD;
-            if (dd < nv) {
-                const size_t off = (size_t)k * p.nd_ld + (size_t)(d0 + dd);
-                MC[(dd * K + k) * 2] = stat_in(mu[off], p.round5);
-                MC[(dd * K + k) * 2 + 1] = 1.0 / (1.4142135623730951 * sqrt(stat_in(sig2[off], p.round5)));
-            }
-        }
-        if (At) {
-            for (int q = tid; q < K * K * FAN_TD; q += FAN_NT) {
-                const int c = q / FAN_TD, dd = q - c * FAN_TD;
-                if (dd < nv) As[q] = stat_in(At[(size_t)c * p.nd_ld + (size_t)(d0 + dd)], p.round5);
-            }
-        }
-        __syncthreads();
-        // weights: thread (draw dd, horizon jh) takes pi_end through hz[jh] products with the draw's A
-        for (int q = tid; q < n_h * FAN_TD; q += FAN_NT) {
-            const int jh = q / FAN_TD, dd = q - jh * FAN_TD;
-            if (dd >= nv) continue;
-            int h = 0;
-#pragma unroll
-            for (int i = 0; i < HMCG_MAXH; ++i) h = jh == i ? p.hz[i] : h;
-            double wv[K];
-#pragma unroll
-            for (int k = 0; k < K; ++k) wv[k] = stat_in(pie[(size_t)k * p.nd_ld + (size_t)(d0 + dd)], p.round5);
-            for (int step = 0; step < h; ++step) HMCG_OMEGA_STEP(K, wv, As + dd, FAN_TD);
-#pragma unroll
-            for (int k = 0; k < K; ++k) Ws[(dd * n_h + jh) * K + k] = wv[k];
-        }
-        __syncthreads();
-        if (live) {
-#pragma unroll 1
-            for (int dd = 0; dd < nv; ++dd) {
-                const double* mc = MC + dd * K * 2;
-                const double* wj = Ws + (dd * n_h + j) * K;
-                double F = 0.0;
-#pragma unroll
-                for (int k = 0; k < K; ++k) {
-                    const double t = (y - mc[2 * k]) * mc[2 * k + 1];
-                    const double ph = 0.5 * erfc(-t);
-                    F = k == 0 ? wj[0] * ph : fma(wj[k], ph, F);
-                }
-                acc += F;
-            }
-        }
+#define FAN_DRAW(dd) (size_t)(d0 + (dd))
+    for (long long d0 = dbeg; d0 < dend; d0 += MIXTILE_TD) {
+        const int nv = dend - d0 < MIXTILE_TD ? (int)(dend - d0) : MIXTILE_TD;
+        HMCG_MIX_TILE_STAGE(K, MC, Ws, As, mu, sig2, pie, At, p, FAN_DRAW, nv, n_h, tid);
+        if (live) HMCG_MIX_TILE_WALK(K, MC, Ws, nv, n_h, j, y, acc);
         __syncthreads();
     }
+#undef FAN_DRAW
     if (live) p.part[HMCG_STAT_ROW(w, p.nslab_total, p.slab0 + s, p.rowlen) + (size_t)e] = acc;
 }
 
@@ -226,11 +181,6 @@ __global__ __launch_bounds__(FAN_STEP_NT) void fan_step_kernel(const FanStepPara
 
 namespace hmcg_host {
 
-size_t fan_lds_bytes(int K, int n_h, bool with_A)
-{
-    return sizeof(double) * (size_t)hmcg::FAN_TD * (size_t)(2 * K + n_h * K + (with_A ? K * K : 0));
-}
-
 hipError_t launch_fan_range(const FanArgs& a, hipStream_t stream)
 {
     if (a.W <= 0 || a.nd <= 0) return hipSuccess;
@@ -260,21 +210,14 @@ hipError_t launch_fan_eval(const FanArgs& a, int round, hipStream_t stream)
     p.nd = a.nd; p.nd_ld = a.nd_ld; p.nslab = pred_slabs(a.nd); p.slab0 = a.slab0; p.nslab_total = a.nslab_total;
     p.n_h = a.n_h; p.n_p = a.n_p; p.items_h = fan_items_h(a.n_p, first); p.items = fan_items(a.n_h, a.n_p, first);
     p.rowlen = fan_max_items(a.n_h, a.n_p); p.first = first ? 1 : 0; p.round5 = a.round5 ? 1 : 0;
-    bool with_A = false;
-    for (int j = 0; j < HMCG_MAXH; ++j) { p.hz[j] = j < a.n_h ? a.horizons[j] : 0; with_A = with_A || p.hz[j] > 0; }
+    const bool with_A = fill_horizons(a.n_h, a.horizons, p.hz);
     if (with_A && !a.A) return hipErrorInvalidValue;
     if (!with_A) p.A = nullptr;
     // nd_ld >= nd is part of the rule; check_fan has enforced it ahead of every launch already
     if (!slab_range_ok(a.W, a.nd, a.nd_ld, a.slab0, a.nslab_total)) return hipErrorInvalidValue;
-    const size_t lds = fan_lds_bytes(a.K, a.n_h, with_A);
-    const dim3 grid((unsigned)((long long)a.W * p.nslab), (unsigned)((p.items + hmcg::FAN_NT - 1) / hmcg::FAN_NT)), block(hmcg::FAN_NT);
-#define HMCG_FAN_EVAL(K_)                                                                                                 \
-    {                                                                                                                     \
-        hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(hmcg::fan_eval_kernel<K_>),                     \
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                         \
-        if (e_ != hipSuccess) return e_;                                                                                   \
-        hipLaunchKernelGGL(hmcg::fan_eval_kernel<K_>, grid, block, lds, stream, p);                                        \
-    }
+    const size_t lds = mixture_lds_bytes(a.K, a.n_h, with_A);
+    const dim3 grid((unsigned)((long long)a.W * p.nslab), (unsigned)((p.items + hmcg::MIXTILE_NT - 1) / hmcg::MIXTILE_NT)), block(hmcg::MIXTILE_NT);
+#define HMCG_FAN_EVAL(K_) HMCG_LAUNCH_LDS(hmcg::fan_eval_kernel<K_>, grid, block, lds, stream, p)
     HMCG_SWITCH_K(a.K, HMCG_FAN_EVAL)
 #undef HMCG_FAN_EVAL
     return hipGetLastError();

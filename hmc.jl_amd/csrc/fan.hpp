@@ -21,7 +21,6 @@ struct FanArgs {
     double probs[HMCG_FAN_MAXP];
     bool round5;
 };
-size_t fan_lds_bytes(int K, int n_h, bool with_A);
 // per-slab min / max of mu -+ 40 sd over the block's draws, then range[w] = their fmin / fmax over the run's slabs
 hipError_t launch_fan_range(const FanArgs& a, hipStream_t stream);
 hipError_t launch_fan_range_finalize(const FanArgs& a, hipStream_t stream);

@@ -34,10 +34,6 @@ constexpr int fan_items(int n_h, int n_p, bool first) { return n_h * fan_items_h
 constexpr int fan_max_items(int n_h, int n_p) { return fan_items(n_h, n_p, true) > fan_items(n_h, n_p, false) ? fan_items(n_h, n_p, true) : fan_items(n_h, n_p, false); }
 // Work area: [W][nslab_total][max items] slab sums; the range pass keeps its per-slab (min, max) in the first two of a row.
 inline size_t fan_part_doubles(int W, long long nd, int n_h, int n_p) { return (size_t)W * (size_t)pred_slabs(nd) * (size_t)fan_max_items(n_h, n_p); }
-inline int fan_max_horizon(const hmcg_fan& p) { return max_horizon(p.n_h, p.horizons); }
-// Draw columns per window that a pass of the host entry uploads: the range pass mu and sig2, a round also pi_end and, with a
-// horizon > 0, A.
-inline int fan_columns(const hmcg_fan& p) { return 3 * p.K + (fan_max_horizon(p) > 0 ? p.K * p.K : 0); }
 
 // Argument rules shared by both entries; 0 or HMCG_E_BADARG with the reason in msg.  No pointer but p is followed.
 inline int check_fan(const hmcg_fan* p, const double* mu, const double* sig2, const double* pi_end, const double* A, const double* out,
@@ -53,7 +49,7 @@ inline int check_fan(const hmcg_fan* p, const double* mu, const double* sig2, co
     if (told(p->rounds < 0 || p->rounds > HMCG_FAN_MAXROUNDS, msg, nmsg, "rounds = %d outside 0..%d", p->rounds, HMCG_FAN_MAXROUNDS)) return HMCG_E_BADARG;
     if (bad_nd(p->nd, msg, nmsg) || bad_nd_ld(p->nd_ld, p->nd, msg, nmsg)) return HMCG_E_BADARG;
     if (told(!mu || !sig2 || !pi_end || !out || !range || !flag, msg, nmsg, "mu, sig2, pi_end, out, range and flag are required")) return HMCG_E_BADARG;
-    if (told(!A && fan_max_horizon(*p) > 0, msg, nmsg, "A is NULL with a horizon > 0")) return HMCG_E_BADARG;
+    if (told(!A && mixture_max_horizon(*p) > 0, msg, nmsg, "A is NULL with a horizon > 0")) return HMCG_E_BADARG;
     return 0;
 }
 

@@ -42,6 +42,7 @@
 #include "ergodic.hpp"
 #include "fan.hpp"
 #include "score.hpp"
+#include "mixture_tile.hpp"
 
 namespace {
 
@@ -974,7 +975,7 @@ int run_host_on_device(DeviceCtx& c, const hmcg_config* cfg, const int32_t* idx,
     return rc;
 }
 
-// ---- statistics of the draws: what the five pairs of entries below share --------------------------------------------------------
+// ---- statistics of the draws: what the nine pairs of entries below share --------------------------------------------------------
 
 // What a statistic's hmcg_timing says of its kernels beside the times and the launch count.
 struct StatShape { int windows, threads_per_window, lds_bytes; };
@@ -1017,7 +1018,29 @@ double* pack_columns(const double* src, size_t cols, size_t ld, long long d0, si
     return dst + cols * n;
 }
 
-// The upload ring of a statistic's host entry.  The draws go up in chunks of whole slabs (stat_plan.hpp): packed column by
+// The predictive mixture's draws [ch.d0, ch.d0 + ch.n) packed as its four features upload them: mu | sig2 | pi_end | A, each
+// [W][columns][ch.n] (WK = W * K); returns the end.  Fan's range pass goes without the last two.
+double* pack_mixture(const double* mu, const double* sig2, const double* pi_end, const double* A, size_t WK, size_t K, size_t ld,
+                     const PredChunk& ch, bool with_pi, bool with_A, double* dst)
+{
+    dst = pack_columns(mu, WK, ld, ch.d0, (size_t)ch.n, dst);
+    dst = pack_columns(sig2, WK, ld, ch.d0, (size_t)ch.n, dst);
+    if (with_pi) dst = pack_columns(pi_end, WK, ld, ch.d0, (size_t)ch.n, dst);
+    if (with_A) dst = pack_columns(A, WK * K, ld, ch.d0, (size_t)ch.n, dst);
+    return dst;
+}
+
+// ... and a launch's arguments (PredictiveArgs, MixArgs, FanArgs) pointed at that chunk on the device.
+template <class Args>
+void place_mixture(Args& a, const PredChunk& ch, double* db, size_t WK, bool with_A)
+{
+    const size_t o_col = WK * (size_t)ch.n;
+    a.mu = db; a.sig2 = db + o_col; a.pi_end = db + 2 * o_col; a.A = with_A ? db + 3 * o_col : nullptr;
+    a.nd = ch.n; a.nd_ld = ch.n; a.slab0 = ch.d0 / PRED_SLAB;
+}
+
+// The upload ring of a statistic's host entry.  The draws go up in chunks of whole slabs (stat_plan.hpp; the scores: the
+// windows in groups, a cut the entry makes itself): packed column by
 // column into pinned staging (leading dimension = the chunk's draws), copied on the copy stream, reduced on the compute stream,
 // RING buffers deep, so chunk c + 1 is packed and copied while chunk c's kernel runs.  Every chunk adds to the same sums in the
 // work area; the caller finalizes at the end.  Both arenas are laid out once, before any pointer is taken: `io` (results and
@@ -1027,9 +1050,9 @@ struct UploadRing {
     DeviceCtx& c;
     hmcg_timing* timing;
     const std::chrono::steady_clock::time_point t_call = std::chrono::steady_clock::now();
-    long long cdraws = 0;                            // draws of a full chunk
+    long long cdraws = 0;                            // draws of a full chunk (the ring's own cut)
     std::vector<PredChunk> chunks;
-    int nbuf = 0;
+    int nbuf = 0;                                    // after alloc(): buffer pairs in use
     char *dev = nullptr, *pin = nullptr, *work = nullptr;    // after alloc(): the arenas and the device's work area
     double *dbuf[RING] = {}, *pbuf[RING] = {};
     size_t uploads = 0;                              // chunks uploaded so far, over every run(): the ring position
@@ -1041,11 +1064,13 @@ struct UploadRing {
         if (const char* cenv = diag_env("HMCG_CHUNK_DRAWS")) cap = atoll(cenv);
         cdraws = pred_chunk_draws(nd, W, ncol, cap);
         chunks = pred_chunks(nd, cdraws);
-        nbuf = (int)std::min<size_t>(RING, chunks.size());
     }
+    // ... or over a cut the caller has made: `ready` goes up chunk by chunk, whatever a chunk's {d0, n} counts.
+    UploadRing(DeviceCtx& ctx, std::vector<PredChunk> ready, hmcg_timing* t) : c(ctx), timing(t), chunks(std::move(ready)) {}
 
     int alloc(const Layout& io, size_t work_bytes, size_t chunk_doubles)
     {
+        nbuf = (int)std::min<size_t>(RING, chunks.size());
         Layout d = io, p = io;
         const size_t o_work = d.add(work_bytes);
         size_t o_d[RING] = {}, o_p[RING] = {};
@@ -1124,13 +1149,13 @@ hmcg_host::PredictiveArgs predictive_args(const hmcg_predictive* p)
 {
     hmcg_host::PredictiveArgs a{};
     a.W = p->W; a.K = p->K; a.G = p->G; a.n_h = p->n_h;
-    for (int j = 0; j < HMCG_MAXH; ++j) a.horizons[j] = j < p->n_h ? p->horizons[j] : 0;
+    fill_horizons(p->n_h, p->horizons, a.horizons);
     a.round5 = (p->flags & HMCG_PRED_ROUND5) != 0;
     a.nslab_total = pred_slabs(p->nd);
     return a;
 }
 
-StatShape predictive_shape(const hmcg_predictive* p) { return {p->W, 0, (int32_t)predictive_lds_bytes(p->K, p->n_h, pred_max_horizon(*p) > 0)}; }
+StatShape predictive_shape(const hmcg_predictive* p) { return {p->W, 0, (int32_t)mixture_lds_bytes(p->K, p->n_h, mixture_max_horizon(*p) > 0)}; }
 
 int predictive_device(DeviceCtx& c, const hmcg_predictive* p, const double* dmu, const double* dsig2, const double* dpi_end,
                       const double* dA, const double* dgrid, double* dcdf, hipStream_t stream, hmcg_timing* timing)
@@ -1151,9 +1176,9 @@ int predictive_device(DeviceCtx& c, const hmcg_predictive* p, const double* dmu,
 int predictive_host(DeviceCtx& c, const hmcg_predictive* p, const double* mu, const double* sig2, const double* pi_end, const double* A,
                     const double* grid, double* cdf, hmcg_timing* timing)
 {
-    const bool with_A = pred_max_horizon(*p) > 0;
+    const bool with_A = mixture_max_horizon(*p) > 0;
     const size_t WK = (size_t)p->W * (size_t)p->K, ld = (size_t)p->nd_ld;
-    const int ncol = pred_columns(*p);
+    const int ncol = mixture_columns(p->K, with_A);
     UploadRing ring(c, p->nd, p->W, ncol, timing);
     const size_t b_grid = sizeof(double) * (size_t)p->G, b_cdf = sizeof(double) * (size_t)p->W * (size_t)p->n_h * (size_t)p->G;
     Layout io;
@@ -1166,19 +1191,10 @@ int predictive_host(DeviceCtx& c, const hmcg_predictive* p, const double* mu, co
     hmcg_host::PredictiveArgs a = predictive_args(p);
     a.grid = reinterpret_cast<double*>(ring.dev + o_grid); a.part = reinterpret_cast<double*>(ring.work);
     double* const dcdf = reinterpret_cast<double*>(ring.dev + o_cdf);
-    // packed chunk: mu | sig2 | pi_end | A, each [W][columns][ch.n]
     rc = ring.run(
-        [&](const PredChunk& ch, double* pb) {
-            double* e = pack_columns(mu, WK, ld, ch.d0, (size_t)ch.n, pb);
-            e = pack_columns(sig2, WK, ld, ch.d0, (size_t)ch.n, e);
-            e = pack_columns(pi_end, WK, ld, ch.d0, (size_t)ch.n, e);
-            if (with_A) e = pack_columns(A, WK * (size_t)p->K, ld, ch.d0, (size_t)ch.n, e);
-            return (size_t)(e - pb);
-        },
+        [&](const PredChunk& ch, double* pb) { return (size_t)(pack_mixture(mu, sig2, pi_end, A, WK, (size_t)p->K, ld, ch, true, with_A, pb) - pb); },
         [&](const PredChunk& ch, double* db, hipStream_t s) -> int {
-            const size_t o_col = WK * (size_t)ch.n;
-            a.mu = db; a.sig2 = db + o_col; a.pi_end = db + 2 * o_col; a.A = with_A ? db + 3 * o_col : nullptr;
-            a.nd = ch.n; a.nd_ld = ch.n; a.slab0 = ch.d0 / PRED_SLAB;
+            place_mixture(a, ch, db, WK, with_A);
             HIP_TRY(launch_predictive(a, s));
             return 0;
         });
@@ -1290,9 +1306,9 @@ int mix_host(DeviceCtx& c, const hmcg_mixmom* p, const double* mu, const double*
              hmcg_timing* timing)
 {
     const int K = p->K, W = p->W;
-    const bool with_A = mix_max_horizon(*p) > 0;
+    const bool with_A = mixture_max_horizon(*p) > 0;
     const size_t WK = (size_t)W * (size_t)K, ld = (size_t)p->nd_ld;
-    const int ncol = mix_columns(*p);
+    const int ncol = mixture_columns(K, with_A);
     UploadRing ring(c, p->nd, W, ncol, timing);
     const size_t b_out = sizeof(double) * (size_t)W * (size_t)p->n_h * (size_t)HMCG_MIX_STRIDE;
     Layout io;
@@ -1301,19 +1317,10 @@ int mix_host(DeviceCtx& c, const hmcg_mixmom* p, const double* mu, const double*
     if (rc) return rc;
     hmcg_host::MixArgs a = mix_args(p);
     a.part = reinterpret_cast<double*>(ring.work);
-    // packed chunk: mu | sig2 | pi_end | A, each [W][columns][ch.n]
     rc = ring.run(
-        [&](const PredChunk& ch, double* pb) {
-            double* e = pack_columns(mu, WK, ld, ch.d0, (size_t)ch.n, pb);
-            e = pack_columns(sig2, WK, ld, ch.d0, (size_t)ch.n, e);
-            e = pack_columns(pi_end, WK, ld, ch.d0, (size_t)ch.n, e);
-            if (with_A) e = pack_columns(A, WK * (size_t)K, ld, ch.d0, (size_t)ch.n, e);
-            return (size_t)(e - pb);
-        },
+        [&](const PredChunk& ch, double* pb) { return (size_t)(pack_mixture(mu, sig2, pi_end, A, WK, (size_t)K, ld, ch, true, with_A, pb) - pb); },
         [&](const PredChunk& ch, double* db, hipStream_t s) -> int {
-            const size_t o_col = WK * (size_t)ch.n;
-            a.mu = db; a.sig2 = db + o_col; a.pi_end = db + 2 * o_col; a.A = with_A ? db + 3 * o_col : nullptr;
-            a.nd = ch.n; a.nd_ld = ch.n; a.slab0 = ch.d0 / PRED_SLAB;
+            place_mixture(a, ch, db, WK, with_A);
             HIP_TRY(launch_mixmoments(a, s));
             return 0;
         });
@@ -1655,14 +1662,14 @@ hmcg_host::FanArgs fan_args(const hmcg_fan* p)
 {
     hmcg_host::FanArgs a{};
     a.W = p->W; a.K = p->K; a.n_h = p->n_h; a.n_p = p->n_p;
-    for (int j = 0; j < HMCG_MAXH; ++j) a.horizons[j] = j < p->n_h ? p->horizons[j] : 0;
+    fill_horizons(p->n_h, p->horizons, a.horizons);
     for (int i = 0; i < HMCG_FAN_MAXP; ++i) a.probs[i] = i < p->n_p ? p->probs[i] : 0.0;
     a.round5 = (p->flags & HMCG_FAN_ROUND5) != 0;
     a.nslab_total = pred_slabs(p->nd);
     return a;
 }
 
-StatShape fan_shape(const hmcg_fan* p) { return {p->W, 0, (int32_t)fan_lds_bytes(p->K, p->n_h, fan_max_horizon(*p) > 0)}; }
+StatShape fan_shape(const hmcg_fan* p) { return {p->W, 0, (int32_t)mixture_lds_bytes(p->K, p->n_h, mixture_max_horizon(*p) > 0)}; }
 
 int fan_device(DeviceCtx& c, const hmcg_fan* p, const double* dmu, const double* dsig2, const double* dpi_end, const double* dA, double* dout,
                double* drange, int32_t* dflag, hipStream_t stream, hmcg_timing* timing)
@@ -1690,9 +1697,9 @@ int fan_device(DeviceCtx& c, const hmcg_fan* p, const double* dmu, const double*
 int fan_host(DeviceCtx& c, const hmcg_fan* p, const double* mu, const double* sig2, const double* pi_end, const double* A, double* out,
              double* range, int32_t* flag, hmcg_timing* timing)
 {
-    const bool with_A = fan_max_horizon(*p) > 0;
+    const bool with_A = mixture_max_horizon(*p) > 0;
     const size_t WK = (size_t)p->W * (size_t)p->K, ld = (size_t)p->nd_ld;
-    const int ncol = fan_columns(*p), R = fan_rounds(*p);
+    const int ncol = mixture_columns(p->K, with_A), R = fan_rounds(*p);
     UploadRing ring(c, p->nd, p->W, ncol, timing);
     const size_t n_q = (size_t)p->W * (size_t)p->n_h * (size_t)p->n_p;
     const size_t b_out = sizeof(double) * n_q * HMCG_FAN_STRIDE, b_range = sizeof(double) * (size_t)p->W * 2, b_flag = sizeof(int32_t) * n_q;
@@ -1704,37 +1711,21 @@ int fan_host(DeviceCtx& c, const hmcg_fan* p, const double* mu, const double* si
     a.part = reinterpret_cast<double*>(ring.work);
     a.out = reinterpret_cast<double*>(ring.dev + o_out); a.range = reinterpret_cast<double*>(ring.dev + o_range);
     a.flag = reinterpret_cast<int32_t*>(ring.dev + o_flag);
-    auto place = [&](const PredChunk& ch, double* db) {
-        const size_t o_col = WK * (size_t)ch.n;
-        a.mu = db; a.sig2 = db + o_col; a.pi_end = db + 2 * o_col; a.A = with_A ? db + 3 * o_col : nullptr;
-        a.nd = ch.n; a.nd_ld = ch.n; a.slab0 = ch.d0 / PRED_SLAB;
-    };
-    // packed chunk of the range pass: mu | sig2, each [W][K][ch.n]
+    // the range pass uploads mu | sig2 alone
     rc = ring.run(
-        [&](const PredChunk& ch, double* pb) {
-            double* e = pack_columns(mu, WK, ld, ch.d0, (size_t)ch.n, pb);
-            e = pack_columns(sig2, WK, ld, ch.d0, (size_t)ch.n, e);
-            return (size_t)(e - pb);
-        },
+        [&](const PredChunk& ch, double* pb) { return (size_t)(pack_mixture(mu, sig2, pi_end, A, WK, (size_t)p->K, ld, ch, false, false, pb) - pb); },
         [&](const PredChunk& ch, double* db, hipStream_t s) -> int {
-            place(ch, db);
+            place_mixture(a, ch, db, WK, with_A);
             HIP_TRY(launch_fan_range(a, s));
             return 0;
         });
     if (rc) return rc;
     HIP_TRY(launch_fan_range_finalize(a, c.stream));
-    // packed chunk of a round: mu | sig2 | pi_end | A, each [W][columns][ch.n]
     for (int r = 1; r <= R; ++r) {
         rc = ring.run(
-            [&](const PredChunk& ch, double* pb) {
-                double* e = pack_columns(mu, WK, ld, ch.d0, (size_t)ch.n, pb);
-                e = pack_columns(sig2, WK, ld, ch.d0, (size_t)ch.n, e);
-                e = pack_columns(pi_end, WK, ld, ch.d0, (size_t)ch.n, e);
-                if (with_A) e = pack_columns(A, WK * (size_t)p->K, ld, ch.d0, (size_t)ch.n, e);
-                return (size_t)(e - pb);
-            },
+            [&](const PredChunk& ch, double* pb) { return (size_t)(pack_mixture(mu, sig2, pi_end, A, WK, (size_t)p->K, ld, ch, true, with_A, pb) - pb); },
             [&](const PredChunk& ch, double* db, hipStream_t s) -> int {
-                place(ch, db);
+                place_mixture(a, ch, db, WK, with_A);
                 HIP_TRY(launch_fan_eval(a, r, s));
                 return 0;
             });
@@ -1755,13 +1746,13 @@ hmcg_host::ScoreArgs score_args(const hmcg_score* p)
 {
     hmcg_host::ScoreArgs a{};
     a.K = p->K; a.n_h = p->n_h; a.n_u = score_used(*p);
-    for (int j = 0; j < HMCG_MAXH; ++j) a.horizons[j] = j < p->n_h ? p->horizons[j] : 0;
+    fill_horizons(p->n_h, p->horizons, a.horizons);
     a.round5 = (p->flags & HMCG_SCORE_ROUND5) != 0;
     a.yreal_ld = p->W;
     return a;
 }
 
-StatShape score_shape(const hmcg_score* p) { return {p->W, SCORE_TP, (int32_t)score_lds_bytes(p->K, p->n_h, score_max_horizon(*p) > 0)}; }
+StatShape score_shape(const hmcg_score* p) { return {p->W, SCORE_TP, (int32_t)score_lds_bytes(p->K, p->n_h, mixture_max_horizon(*p) > 0)}; }
 
 int score_launches(const hmcg_host::ScoreArgs& a, hipStream_t stream)
 {
@@ -1784,95 +1775,61 @@ int score_device(DeviceCtx& c, const hmcg_score* p, const double* dmu, const dou
     });
 }
 
-// Host entry on one device.  The pair pass needs a window's used draws resident, so this is not the draw-slab ring: only the
-// draws u * stride are read, packed with leading dimension n_u into pinned staging (per group: mu | sig2 | pi_end | A, each
-// [windows][columns][n_u]), and the windows go up in groups (score_plan.hpp), RING buffers deep: group g + 1 is packed and copied
-// while group g's kernels run.  Windows are independent and every group writes its own rows of out, fetched once at the end.
+// Host entry on one device.  The pair pass needs a window's used draws resident, so the upload ring goes over window groups
+// and not over draw slabs: only the draws u * stride are read, packed with leading dimension n_u into pinned staging (per
+// group: mu | sig2 | pi_end | A, each [windows][columns][n_u]); group g + 1 is packed and copied while group g's kernels run.
+// Windows are independent and every group writes its own rows of out, fetched once at the end.
 int score_host(DeviceCtx& c, const hmcg_score* p, const double* mu, const double* sig2, const double* pi_end, const double* A,
                const double* yreal, double* out, hmcg_timing* timing)
 {
-    const auto t_call = std::chrono::steady_clock::now();
-    const bool with_A = score_max_horizon(*p) > 0;
+    const bool with_A = mixture_max_horizon(*p) > 0;
     const long long n_u = score_used(*p), stride = score_stride(p->nd, p->stride);
     const size_t K = (size_t)p->K, ld = (size_t)p->nd_ld;
-    const int ncol = score_columns(*p);
+    const int ncol = mixture_columns(p->K, with_A);
     long long cap = 0;
     if (const char* cenv = diag_env("HMCG_SCORE_GROUP_WINDOWS")) cap = atoll(cenv);
     const int gw = score_group_windows(p->W, n_u, ncol, cap);
-    const int ngroups = (p->W + gw - 1) / gw;
-    const int nbuf = std::min<int>(RING, ngroups);
+    UploadRing ring(c, pred_chunks(p->W, gw), timing);           // a chunk {d0, n}: windows [d0, d0 + n)
     const size_t b_y = sizeof(double) * (size_t)p->n_h * (size_t)p->W, b_out = sizeof(double) * (size_t)p->W * (size_t)p->n_h * HMCG_SCORE_STRIDE;
-    Layout d, h;
-    const size_t o_y = d.add(b_y), o_out = d.add(b_out);
-    h.add(b_y); h.add(b_out);
-    const size_t o_work = d.add(sizeof(double) * score_work_doubles(gw, n_u, p->K, p->n_h));
-    size_t o_d[RING] = {}, o_p[RING] = {};
-    const size_t b_group = sizeof(double) * (size_t)gw * (size_t)ncol * (size_t)n_u;
-    for (int b = 0; b < nbuf; ++b) { o_d[b] = d.add(b_group); o_p[b] = h.add(b_group); }
-    if (c.dev.ensure(d.total) || c.pin.ensure(h.total)) {
-        set_err("workspace allocation failed (%zu B device, %zu B pinned)", d.total, h.total);
-        return HMCG_E_NOMEM;
-    }
-    memcpy(c.pin.base + o_y, yreal, b_y);
-    HIP_TRY(hipMemcpyAsync(c.dev.base + o_y, c.pin.base + o_y, b_y, hipMemcpyHostToDevice, c.stream));
-    Events tev;
+    Layout io;
+    const size_t o_y = io.add(b_y), o_out = io.add(b_out);
+    int rc = ring.alloc(io, sizeof(double) * score_work_doubles(gw, n_u, p->K, p->n_h), (size_t)gw * (size_t)ncol * (size_t)n_u);
+    if (rc) return rc;
+    memcpy(ring.pin + o_y, yreal, b_y);
+    HIP_TRY(hipMemcpyAsync(ring.dev + o_y, ring.pin + o_y, b_y, hipMemcpyHostToDevice, c.stream));
     hmcg_host::ScoreArgs a = score_args(p);
-    a.yreal = reinterpret_cast<const double*>(c.dev.base + o_y);
-    a.work = reinterpret_cast<double*>(c.dev.base + o_work);
+    a.yreal = reinterpret_cast<const double*>(ring.dev + o_y);
+    a.work = reinterpret_cast<double*>(ring.work);
     a.stride = 1; a.nd_ld = n_u;
-    // every stride-th draw of `cols` columns from window w0 on, n windows of them
-    auto pack = [&](const double* src, size_t cols, int w0, int n, double* dst) {
-        for (size_t q = 0; q < (size_t)n * cols; ++q) {
-            const double* col = src + ((size_t)w0 * cols + q) * ld;
+    // every stride-th draw of `cols` columns of the group's windows
+    auto pack = [&](const double* src, size_t cols, const PredChunk& g, double* dst) {
+        for (size_t q = 0; q < (size_t)g.n * cols; ++q) {
+            const double* col = src + ((size_t)g.d0 * cols + q) * ld;
             if (stride == 1) memcpy(dst, col, sizeof(double) * (size_t)n_u);
             else for (long long u = 0; u < n_u; ++u) dst[u] = col[(size_t)u * (size_t)stride];
             dst += n_u;
         }
         return dst;
     };
-    int up = 0;
-    for (int w0 = 0; w0 < p->W; w0 += gw) {
-        const int n = std::min(gw, p->W - w0);
-        const int b = up % nbuf;
-        if (up >= nbuf) HIP_TRY(hipEventSynchronize(c.evk[b]));                 // the kernels that read this buffer pair are done
-        ++up;
-        double* pb = reinterpret_cast<double*>(c.pin.base + o_p[b]);
-        double* db = reinterpret_cast<double*>(c.dev.base + o_d[b]);
-        double* e = pack(mu, K, w0, n, pb);
-        e = pack(sig2, K, w0, n, e);
-        e = pack(pi_end, K, w0, n, e);
-        if (with_A) e = pack(A, K * K, w0, n, e);
-        HIP_TRY(hipMemcpyAsync(db, pb, sizeof(double) * (size_t)(e - pb), hipMemcpyHostToDevice, c.copy));
-        HIP_TRY(hipEventRecord(c.evc[b], c.copy));
-        HIP_TRY(hipStreamWaitEvent(c.stream, c.evc[b], 0));
-        hipEvent_t ev[2] = {};
-        if (timing) {
-            for (hipEvent_t& x : ev) { HIP_TRY(hipEventCreate(&x)); tev.ev.push_back(x); }
-            HIP_TRY(hipEventRecord(ev[0], c.stream));
-        }
-        const size_t o_col = (size_t)n * K * (size_t)n_u;
-        a.mu = db; a.sig2 = db + o_col; a.pi_end = db + 2 * o_col; a.A = with_A ? db + 3 * o_col : nullptr;
-        a.W = n; a.w0 = w0;
-        a.out = reinterpret_cast<double*>(c.dev.base + o_out) + (size_t)w0 * (size_t)p->n_h * HMCG_SCORE_STRIDE;
-        const int rc = score_launches(a, c.stream);
-        if (rc) return rc;
-        if (timing) HIP_TRY(hipEventRecord(ev[1], c.stream));
-        HIP_TRY(hipEventRecord(c.evk[b], c.stream));
-    }
-    HIP_TRY(hipMemcpyAsync(c.pin.base + o_out, c.dev.base + o_out, b_out, hipMemcpyDeviceToHost, c.stream));
-    HIP_TRY(hipStreamSynchronize(c.stream));
-    memcpy(out, c.pin.base + o_out, b_out);
-    if (timing) {
-        double kernel_ms = 0.0;
-        for (size_t i = 0; i + 1 < tev.ev.size(); i += 2) {
-            float ms = 0.f;
-            HIP_TRY(hipEventElapsedTime(&ms, tev.ev[i], tev.ev[i + 1]));
-            kernel_ms += ms;
-        }
-        const double call_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_call).count();
-        fill_stat_timing(timing, c, score_shape(p), kernel_ms, 3 * up, call_ms);
-    }
-    return 0;
+    rc = ring.run(
+        [&](const PredChunk& g, double* pb) {
+            double* e = pack(mu, K, g, pb);
+            e = pack(sig2, K, g, e);
+            e = pack(pi_end, K, g, e);
+            if (with_A) e = pack(A, K * K, g, e);
+            return (size_t)(e - pb);
+        },
+        [&](const PredChunk& g, double* db, hipStream_t s) -> int {
+            const size_t o_col = (size_t)g.n * K * (size_t)n_u;
+            a.mu = db; a.sig2 = db + o_col; a.pi_end = db + 2 * o_col; a.A = with_A ? db + 3 * o_col : nullptr;
+            a.W = (int)g.n; a.w0 = g.d0;
+            a.out = reinterpret_cast<double*>(ring.dev + o_out) + (size_t)g.d0 * (size_t)p->n_h * HMCG_SCORE_STRIDE;
+            return score_launches(a, s);
+        });
+    if (rc) return rc;
+    if ((rc = ring.fetch(o_out, b_out))) return rc;
+    memcpy(out, ring.pin + o_out, b_out);
+    return ring.report(score_shape(p), 3 * (int)ring.uploads);
 }
 
 // The prologue of a compute entry on one device.  The argument check comes first and needs no device: a caller on a machine

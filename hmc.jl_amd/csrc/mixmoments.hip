@@ -55,7 +55,7 @@ struct MixParams {
     int hz[HMCG_MAXH], slot[HMCG_MAXH];      // the ascending walk (mixmoments_plan.hpp)
 };
 
-// a[i] for a per-thread i without indexing the kernel arguments by a register (predictive.hip has the ladder inline, started at 0)
+// a[i] for a per-thread i without indexing the kernel arguments by a register (mixture_tile.hpp has the ladder inline, started at 0)
 __device__ __forceinline__ int mix_pick(const int* a, int i)
 {
     int r = a[0];

@@ -18,9 +18,9 @@ constexpr int MIX_ITEMS = 9;
 // Filed per (window, horizon) for the later chunks of the host entry: the pivot c and a_0, the a of the window's draw 0.
 constexpr int MIX_PIVOTS = 2;
 
-inline int mix_max_horizon(const hmcg_mixmom& p) { return max_horizon(p.n_h, p.horizons); }
-// Draw columns per window that a call reads: mu, sig2, pi_end (K each) and A (K * K) with a horizon > 0.
-inline int mix_columns(const hmcg_mixmom& p) { return 3 * p.K + (mix_max_horizon(p) > 0 ? p.K * p.K : 0); }
+// The largest horizon and the draw columns per window of a checked call, under this feature's names (stat_plan.hpp).
+inline int mix_max_horizon(const hmcg_mixmom& p) { return mixture_max_horizon(p); }
+inline int mix_columns(const hmcg_mixmom& p) { return mixture_columns(p.K, mixture_max_horizon(p) > 0); }
 
 // The ascending walk: omega is carried along one chain of mix_max_horizon products, and at position i of the walk the chain
 // stands at hz[i] = horizons[slot[i]] (hz ascending; equal horizons keep their order).  Every horizon gets the bits it would get

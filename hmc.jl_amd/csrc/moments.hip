@@ -18,6 +18,7 @@
 
 #include "moments.hpp"
 #include "round5.hpp"
+#include "stat_device.hpp"
 
 namespace hmcg {
 
@@ -139,13 +140,7 @@ hipError_t launch_moments(const MomentsArgs& a, hipStream_t stream)
     const size_t lds = sizeof(double) * ((size_t)NCp * (hmcg::MOM_TD + 1) + (size_t)p.NC);
     const int ppt = (NP + hmcg::MOM_NT - 1) / hmcg::MOM_NT;
     const dim3 grid((unsigned)a.W), block(hmcg::MOM_NT);
-#define HMCG_MOM(PPT_)                                                                                                    \
-    do {                                                                                                                  \
-        hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(hmcg::draw_moments_kernel<PPT_>),               \
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                         \
-        if (e_ != hipSuccess) return e_;                                                                                   \
-        hipLaunchKernelGGL(hmcg::draw_moments_kernel<PPT_>, grid, block, lds, stream, p);                                  \
-    } while (0)
+#define HMCG_MOM(PPT_) HMCG_LAUNCH_LDS(hmcg::draw_moments_kernel<PPT_>, grid, block, lds, stream, p)
     if (ppt <= 1) HMCG_MOM(1);
     else if (ppt <= 2) HMCG_MOM(2);
     else if (ppt <= 4) HMCG_MOM(4);

@@ -9,7 +9,7 @@
 //
 // Shape: one block per (window, slab of PRED_SLAB draws, 128 (horizon, grid point) items).  A tile of 64 draws is staged in LDS --
 // per draw and state mu_k and c_k = 1 / (sqrt 2 * sqrt(sig2_k)) side by side, and the n_h * K weights, built per (draw, horizon) by
-// h successive row-vector x matrix products over the tile's transition draws (HMCG_OMEGA_STEP of stat_device.hpp).  Each thread then
+// h successive row-vector x matrix products over the tile's transition draws (the tile and its walk: mixture_tile.hpp).  Each thread then
 // owns one (horizon, grid point) and walks the tile in draw order: every lane reads the same mu, c (one broadcast ds_read_b128),
 // Phi = erfc(-(y - mu) c) / 2.  fp64 VALU work by construction: 8 (3K [+ K^2]) bytes read per draw against K * n_h * G erfc.
 //
@@ -20,12 +20,10 @@
 #include <stdint.h>
 
 #include "predictive.hpp"
-#include "stat_device.hpp"
+#include "mixture_tile.hpp"
 
 namespace hmcg {
 
-constexpr int PRED_TD = 64;          // draws per LDS tile
-constexpr int PRED_NT = 128;         // threads per block = (horizon, grid point) items per block
 constexpr int PRED_FIN_NT = 256;
 
 struct PredictiveParams {
@@ -38,16 +36,14 @@ struct PredictiveParams {
 };
 
 template <int K>
-__global__ __launch_bounds__(PRED_NT) void predictive_cdf_kernel(const PredictiveParams p)
+__global__ __launch_bounds__(MIXTILE_NT) void predictive_cdf_kernel(const PredictiveParams p)
 {
     extern __shared__ double pred_lds[];
     const int n_h = p.n_h;
-    double* MC = pred_lds;                               // [PRED_TD][K][2]: mu, c
-    double* Ws = MC + PRED_TD * K * 2;                   // [PRED_TD][n_h][K]: weights of every horizon
-    double* As = Ws + PRED_TD * n_h * K;                 // [K * K][PRED_TD]: transition draws (present with a horizon > 0)
+    HMCG_MIX_TILE_LDS(K, pred_lds, n_h, MC, Ws, As);
     const int tid = threadIdx.x;
     HMCG_STAT_SLAB(w, s, dbeg, dend, p.nslab, p.nd);
-    const int e = (int)blockIdx.y * PRED_NT + tid;       // this thread's item: horizon j, grid point g
+    const int e = (int)blockIdx.y * MIXTILE_NT + tid;    // this thread's item: horizon j, grid point g
     const bool live = e < p.items;
     const int j = live ? e / p.G : 0, g = live ? e - j * p.G : 0;
     const double y = stat_in(p.grid[g], p.round5);
@@ -56,55 +52,14 @@ __global__ __launch_bounds__(PRED_NT) void predictive_cdf_kernel(const Predictiv
     const double* pie = p.pi_end + (size_t)w * K * p.nd_ld;
     const double* At = p.A ? p.A + (size_t)w * K * K * p.nd_ld : nullptr;
     double acc = 0.0;
-    for (long long d0 = dbeg; d0 < dend; d0 += PRED_TD) {
-        const int nv = dend - d0 < PRED_TD ? (int)(dend - d0) : PRED_TD;
-        for (int q = tid; q < K * PRED_TD; q += PRED_NT) {
-            const int k = q / PRED_TD, dd = q - k * PRED_TD;
-            if (dd < nv) {
-                const size_t off = (size_t)k * p.nd_ld + (size_t)(d0 + dd);
-                MC[(dd * K + k) * 2] = stat_in(mu[off], p.round5);
-                MC[(dd * K + k) * 2 + 1] = 1.0 / (1.4142135623730951 * sqrt(stat_in(sig2[off], p.round5)));
-            }
-        }
-        if (At) {
-            for (int q = tid; q < K * K * PRED_TD; q += PRED_NT) {
-                const int c = q / PRED_TD, dd = q - c * PRED_TD;
-                if (dd < nv) As[q] = stat_in(At[(size_t)c * p.nd_ld + (size_t)(d0 + dd)], p.round5);
-            }
-        }
-        __syncthreads();
-        // weights: thread (draw dd, horizon jh) takes pi_end through hz[jh] products with the draw's A
-        for (int q = tid; q < n_h * PRED_TD; q += PRED_NT) {
-            const int jh = q / PRED_TD, dd = q - jh * PRED_TD;
-            if (dd >= nv) continue;
-            int h = 0;                                   // mix_pick of mixmoments.hip, begun at 0; neither kernel takes the other's form
-#pragma unroll
-            for (int i = 0; i < HMCG_MAXH; ++i) h = jh == i ? p.hz[i] : h;
-            double wv[K];
-#pragma unroll
-            for (int k = 0; k < K; ++k) wv[k] = stat_in(pie[(size_t)k * p.nd_ld + (size_t)(d0 + dd)], p.round5);
-            for (int step = 0; step < h; ++step) HMCG_OMEGA_STEP(K, wv, As + dd, PRED_TD);
-#pragma unroll
-            for (int k = 0; k < K; ++k) Ws[(dd * n_h + jh) * K + k] = wv[k];
-        }
-        __syncthreads();
-        if (live) {
-#pragma unroll 1
-            for (int dd = 0; dd < nv; ++dd) {
-                const double* mc = MC + dd * K * 2;
-                const double* wj = Ws + (dd * n_h + j) * K;
-                double F = 0.0;
-#pragma unroll
-                for (int k = 0; k < K; ++k) {
-                    const double t = (y - mc[2 * k]) * mc[2 * k + 1];
-                    const double ph = 0.5 * erfc(-t);
-                    F = k == 0 ? wj[0] * ph : fma(wj[k], ph, F);
-                }
-                acc += F;
-            }
-        }
+#define PRED_DRAW(dd) (size_t)(d0 + (dd))
+    for (long long d0 = dbeg; d0 < dend; d0 += MIXTILE_TD) {
+        const int nv = dend - d0 < MIXTILE_TD ? (int)(dend - d0) : MIXTILE_TD;
+        HMCG_MIX_TILE_STAGE(K, MC, Ws, As, mu, sig2, pie, At, p, PRED_DRAW, nv, n_h, tid);
+        if (live) HMCG_MIX_TILE_WALK(K, MC, Ws, nv, n_h, j, y, acc);
         __syncthreads();
     }
+#undef PRED_DRAW
     if (live) p.part[HMCG_STAT_ROW(w, p.nslab_total, p.slab0 + s, p.items) + (size_t)e] = acc;
 }
 
@@ -126,11 +81,6 @@ namespace hmcg_host {
 
 size_t predictive_part_doubles(int W, long long nd, int n_h, int G) { return (size_t)W * (size_t)pred_slabs(nd) * (size_t)n_h * (size_t)G; }
 
-size_t predictive_lds_bytes(int K, int n_h, bool with_A)
-{
-    return sizeof(double) * (size_t)hmcg::PRED_TD * (size_t)(2 * K + n_h * K + (with_A ? K * K : 0));
-}
-
 hipError_t launch_predictive(const PredictiveArgs& a, hipStream_t stream)
 {
     if (a.W <= 0 || a.nd <= 0) return hipSuccess;
@@ -138,21 +88,14 @@ hipError_t launch_predictive(const PredictiveArgs& a, hipStream_t stream)
     p.mu = a.mu; p.sig2 = a.sig2; p.pi_end = a.pi_end; p.A = a.A; p.grid = a.grid; p.part = a.part;
     p.nd = a.nd; p.nd_ld = a.nd_ld; p.nslab = pred_slabs(a.nd); p.slab0 = a.slab0; p.nslab_total = a.nslab_total;
     p.G = a.G; p.n_h = a.n_h; p.items = a.n_h * a.G; p.round5 = a.round5 ? 1 : 0;
-    bool with_A = false;
-    for (int j = 0; j < HMCG_MAXH; ++j) { p.hz[j] = j < a.n_h ? a.horizons[j] : 0; with_A = with_A || p.hz[j] > 0; }
+    const bool with_A = fill_horizons(a.n_h, a.horizons, p.hz);
     if (with_A && !a.A) return hipErrorInvalidValue;
     if (!with_A) p.A = nullptr;
     // nd_ld >= nd is part of the rule; check_predictive has enforced it ahead of every launch already
     if (!slab_range_ok(a.W, a.nd, a.nd_ld, a.slab0, a.nslab_total)) return hipErrorInvalidValue;
-    const size_t lds = predictive_lds_bytes(a.K, a.n_h, with_A);
-    const dim3 grid((unsigned)((long long)a.W * p.nslab), (unsigned)((p.items + hmcg::PRED_NT - 1) / hmcg::PRED_NT)), block(hmcg::PRED_NT);
-#define HMCG_PRED(K_)                                                                                                     \
-    {                                                                                                                     \
-        hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(hmcg::predictive_cdf_kernel<K_>),               \
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                         \
-        if (e_ != hipSuccess) return e_;                                                                                   \
-        hipLaunchKernelGGL(hmcg::predictive_cdf_kernel<K_>, grid, block, lds, stream, p);                                  \
-    }
+    const size_t lds = mixture_lds_bytes(a.K, a.n_h, with_A);
+    const dim3 grid((unsigned)((long long)a.W * p.nslab), (unsigned)((p.items + hmcg::MIXTILE_NT - 1) / hmcg::MIXTILE_NT)), block(hmcg::MIXTILE_NT);
+#define HMCG_PRED(K_) HMCG_LAUNCH_LDS(hmcg::predictive_cdf_kernel<K_>, grid, block, lds, stream, p)
     HMCG_SWITCH_K(a.K, HMCG_PRED)
 #undef HMCG_PRED
     return hipGetLastError();

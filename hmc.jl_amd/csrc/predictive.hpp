@@ -19,7 +19,6 @@ struct PredictiveArgs {
     bool round5;
 };
 size_t predictive_part_doubles(int W, long long nd, int n_h, int G);
-size_t predictive_lds_bytes(int K, int n_h, bool with_A);
 hipError_t launch_predictive(const PredictiveArgs& a, hipStream_t stream);
 // cdf[w][j][g] = (sum of the window's slab sums, in slab order) / nd_total
 hipError_t launch_predictive_finalize(const double* part, double* cdf, int W, int n_h, int G, long long nd_total, hipStream_t stream);

@@ -11,10 +11,9 @@
 
 namespace hmcg_host {
 
-// The largest horizon of a checked call (0: the transition draws are not read).
-inline int pred_max_horizon(const hmcg_predictive& p) { return max_horizon(p.n_h, p.horizons); }
-// Draw columns per window that a call reads: mu, sig2, pi_end (K each) and A (K * K) with a horizon > 0.
-inline int pred_columns(const hmcg_predictive& p) { return 3 * p.K + (pred_max_horizon(p) > 0 ? p.K * p.K : 0); }
+// The largest horizon and the draw columns per window of a checked call, under this feature's names (stat_plan.hpp).
+inline int pred_max_horizon(const hmcg_predictive& p) { return mixture_max_horizon(p); }
+inline int pred_columns(const hmcg_predictive& p) { return mixture_columns(p.K, mixture_max_horizon(p) > 0); }
 
 // Argument rules shared by both entries; 0 or HMCG_E_BADARG with the reason in msg.  host: the grid is host memory and must be finite.
 inline int check_predictive(const hmcg_predictive* p, const double* mu, const double* sig2, const double* pi_end, const double* A,

@@ -8,8 +8,9 @@
 // does not depend on the horizon -- only the weights do -- so one pass over the pairs serves every horizon.
 //
 // score_comp_kernel has the tile shape of predictive_cdf_kernel: one block per (window, slab of PRED_SLAB used draws), a tile of
-// 64 draws staged in LDS with the weights of every horizon (HMCG_OMEGA_STEP).  It writes the used draws' components (mu, sig2,
-// rounded if asked) and weights into the work area, and a thread per (draw, horizon) evaluates F, E|.| and the density at that
+// 64 draws staged in LDS with the weights of every horizon (the transition staging and the weights of mixture_tile.hpp).  It
+// writes the used draws' components (mu, sig2, rounded if asked) and weights into the work area, and a thread per (draw,
+// horizon) evaluates F, E|.| and the density at that
 // horizon's realised value with predictive.hip's per-draw expression; one thread per (value, horizon) adds them in draw order.
 // score_pair_kernel, the hot path: a block owns two rows of tiles of the component square (a short and a long one: equal work),
 // thread t one component of each row; the column tiles (mu, sig2, the n_h weights of a component, side by side) are staged in
@@ -21,14 +22,12 @@
 #include <stdint.h>
 
 #include "score.hpp"
-#include "stat_device.hpp"
+#include "mixture_tile.hpp"
 
 namespace hmcg {
 
 using hmcg_host::SCORE_TP;
 
-constexpr int SCORE_TD = 64;         // draws per LDS tile of the component pass
-constexpr int SCORE_NT = 128;        // threads per block of the component pass
 constexpr int SCORE_FIN_NT = 64;
 
 struct ScoreCompParams {
@@ -41,15 +40,15 @@ struct ScoreCompParams {
 };
 
 template <int K>
-__global__ __launch_bounds__(SCORE_NT) void score_comp_kernel(const ScoreCompParams p)
+__global__ __launch_bounds__(MIXTILE_NT) void score_comp_kernel(const ScoreCompParams p)
 {
     extern __shared__ double score_lds[];
     const int n_h = p.n_h;
-    double* MC = score_lds;                              // [SCORE_TD][K][3]: mu, sig2, c
-    double* Ws = MC + SCORE_TD * K * 3;                  // [SCORE_TD][n_h][K]: weights of every horizon
-    double* Vs = Ws + SCORE_TD * n_h * K;                // [3][n_h][SCORE_TD]: F, E, P of a (draw, horizon)
-    double* Ys = Vs + 3 * n_h * SCORE_TD;                // [HMCG_MAXH]: the window's realised values
-    double* As = Ys + HMCG_MAXH;                         // [K * K][SCORE_TD]: transition draws (present with a horizon > 0)
+    double* MC = score_lds;                              // [MIXTILE_TD][K][3]: mu, sig2, c
+    double* Ws = MC + MIXTILE_TD * K * 3;                // [MIXTILE_TD][n_h][K]: weights of every horizon
+    double* Vs = Ws + MIXTILE_TD * n_h * K;              // [3][n_h][MIXTILE_TD]: F, E, P of a (draw, horizon)
+    double* Ys = Vs + 3 * n_h * MIXTILE_TD;              // [HMCG_MAXH]: the window's realised values
+    double* As = Ys + HMCG_MAXH;                         // [K * K][MIXTILE_TD]: transition draws (present with a horizon > 0)
     const int tid = threadIdx.x;
     HMCG_STAT_SLAB(w, s, ubeg, uend, p.nslab, p.n_u);
     const double* mu = p.mu + (size_t)w * K * p.nd_ld;
@@ -60,12 +59,14 @@ __global__ __launch_bounds__(SCORE_NT) void score_comp_kernel(const ScoreCompPar
     const size_t N = (size_t)p.n_u * K;
     if (tid < n_h) Ys[tid] = p.yreal[(size_t)tid * (size_t)p.yreal_ld + (size_t)(p.w0 + w)];
     double acc = 0.0;
-    for (long long u0 = ubeg; u0 < uend; u0 += SCORE_TD) {
-        const int nv = uend - u0 < SCORE_TD ? (int)(uend - u0) : SCORE_TD;
-        for (int q = tid; q < K * SCORE_TD; q += SCORE_NT) {
-            const int k = q / SCORE_TD, dd = q - k * SCORE_TD;
+#define SCORE_DRAW(dd) (size_t)(u0 + (dd)) * (size_t)p.stride
+    for (long long u0 = ubeg; u0 < uend; u0 += MIXTILE_TD) {
+        const int nv = uend - u0 < MIXTILE_TD ? (int)(uend - u0) : MIXTILE_TD;
+        // HMCG_MIX_STAGE_MC of mixture_tile.hpp, three wide and with the work area's copy; neither kernel takes the other's form
+        for (int q = tid; q < K * MIXTILE_TD; q += MIXTILE_NT) {
+            const int k = q / MIXTILE_TD, dd = q - k * MIXTILE_TD;
             if (dd < nv) {
-                const size_t off = (size_t)k * p.nd_ld + (size_t)(u0 + dd) * (size_t)p.stride;
+                const size_t off = (size_t)k * p.nd_ld + SCORE_DRAW(dd);
                 const double m = stat_in(mu[off], p.round5), v = stat_in(sig2[off], p.round5);
                 MC[(dd * K + k) * 3] = m;
                 MC[(dd * K + k) * 3 + 1] = v;
@@ -75,33 +76,12 @@ __global__ __launch_bounds__(SCORE_NT) void score_comp_kernel(const ScoreCompPar
                 wk[p.lay.o_v + c] = v;
             }
         }
-        if (At) {
-            for (int q = tid; q < K * K * SCORE_TD; q += SCORE_NT) {
-                const int c = q / SCORE_TD, dd = q - c * SCORE_TD;
-                if (dd < nv) As[q] = stat_in(At[(size_t)c * p.nd_ld + (size_t)(u0 + dd) * (size_t)p.stride], p.round5);
-            }
-        }
+        HMCG_MIX_STAGE_A(K, As, At, p, SCORE_DRAW, nv, tid);
         __syncthreads();
-        // weights: thread (draw dd, horizon jh) takes pi_end through hz[jh] products with the draw's A
-        for (int q = tid; q < n_h * SCORE_TD; q += SCORE_NT) {
-            const int jh = q / SCORE_TD, dd = q - jh * SCORE_TD;
-            if (dd >= nv) continue;
-            int h = 0;
-#pragma unroll
-            for (int i = 0; i < HMCG_MAXH; ++i) h = jh == i ? p.hz[i] : h;
-            double wv[K];
-#pragma unroll
-            for (int k = 0; k < K; ++k) wv[k] = stat_in(pie[(size_t)k * p.nd_ld + (size_t)(u0 + dd) * (size_t)p.stride], p.round5);
-            for (int step = 0; step < h; ++step) HMCG_OMEGA_STEP(K, wv, As + dd, SCORE_TD);
-#pragma unroll
-            for (int k = 0; k < K; ++k) {
-                Ws[(dd * n_h + jh) * K + k] = wv[k];
-                wk[p.lay.o_w + (size_t)jh * N + (size_t)(u0 + dd) * K + k] = wv[k];
-            }
-        }
+        HMCG_MIX_WEIGHTS(K, Ws, As, pie, p, SCORE_DRAW, nv, n_h, tid, wk[p.lay.o_w + (size_t)jh_ * N + (size_t)(u0 + dd_) * K + k_] = wv_[k_]);
         __syncthreads();
-        for (int q = tid; q < n_h * SCORE_TD; q += SCORE_NT) {
-            const int jh = q / SCORE_TD, dd = q - jh * SCORE_TD;
+        for (int q = tid; q < n_h * MIXTILE_TD; q += MIXTILE_NT) {
+            const int jh = q / MIXTILE_TD, dd = q - jh * MIXTILE_TD;
             if (dd >= nv) continue;
             const double y = Ys[jh];
             const double* mc = MC + dd * K * 3;
@@ -115,17 +95,18 @@ __global__ __launch_bounds__(SCORE_NT) void score_comp_kernel(const ScoreCompPar
                 E = k == 0 ? wj[0] * ak : fma(wj[k], ak, E);
                 P = k == 0 ? wj[0] * dk : fma(wj[k], dk, P);
             }
-            Vs[jh * SCORE_TD + dd] = F;
-            Vs[(n_h + jh) * SCORE_TD + dd] = E;
-            Vs[(2 * n_h + jh) * SCORE_TD + dd] = P;
+            Vs[jh * MIXTILE_TD + dd] = F;
+            Vs[(n_h + jh) * MIXTILE_TD + dd] = E;
+            Vs[(2 * n_h + jh) * MIXTILE_TD + dd] = P;
         }
         __syncthreads();
         if (tid < 3 * n_h) {
-            const double* v = Vs + tid * SCORE_TD;
+            const double* v = Vs + tid * MIXTILE_TD;
 #pragma unroll 1
             for (int dd = 0; dd < nv; ++dd) acc += v[dd];
         }
     }
+#undef SCORE_DRAW
     if (tid < 3 * n_h) wk[p.lay.o_lin + (size_t)s * (size_t)(3 * n_h) + (size_t)tid] = acc;
 }
 
@@ -252,7 +233,7 @@ namespace hmcg_host {
 
 size_t score_lds_bytes(int K, int n_h, bool with_A)
 {
-    return sizeof(double) * ((size_t)hmcg::SCORE_TD * (size_t)(3 * K + n_h * K + 3 * n_h + (with_A ? K * K : 0)) + HMCG_MAXH);
+    return sizeof(double) * ((size_t)hmcg::MIXTILE_TD * (size_t)(3 * K + n_h * K + 3 * n_h + (with_A ? K * K : 0)) + HMCG_MAXH);
 }
 
 // What every launch needs to hold: the strided reads stay inside the arrays, the grids inside one launch.
@@ -273,19 +254,12 @@ hipError_t launch_score_components(const ScoreArgs& a, hipStream_t stream)
     p.n_u = a.n_u; p.stride = a.stride; p.nd_ld = a.nd_ld; p.nslab = pred_slabs(a.n_u); p.yreal_ld = a.yreal_ld; p.w0 = a.w0;
     p.lay = score_work(a.n_u, a.K, a.n_h);
     p.n_h = a.n_h; p.round5 = a.round5 ? 1 : 0;
-    bool with_A = false;
-    for (int j = 0; j < HMCG_MAXH; ++j) { p.hz[j] = j < a.n_h ? a.horizons[j] : 0; with_A = with_A || p.hz[j] > 0; }
+    const bool with_A = fill_horizons(a.n_h, a.horizons, p.hz);
     if (with_A && !a.A) return hipErrorInvalidValue;
     if (!with_A) p.A = nullptr;
     const size_t lds = score_lds_bytes(a.K, a.n_h, with_A);
-    const dim3 grid((unsigned)((long long)a.W * p.nslab)), block(hmcg::SCORE_NT);
-#define HMCG_SCORE_COMP(K_)                                                                                               \
-    {                                                                                                                     \
-        hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(hmcg::score_comp_kernel<K_>),                   \
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                         \
-        if (e_ != hipSuccess) return e_;                                                                                   \
-        hipLaunchKernelGGL(hmcg::score_comp_kernel<K_>, grid, block, lds, stream, p);                                      \
-    }
+    const dim3 grid((unsigned)((long long)a.W * p.nslab)), block(hmcg::MIXTILE_NT);
+#define HMCG_SCORE_COMP(K_) HMCG_LAUNCH_LDS(hmcg::score_comp_kernel<K_>, grid, block, lds, stream, p)
     HMCG_SWITCH_K(a.K, HMCG_SCORE_COMP)
 #undef HMCG_SCORE_COMP
     return hipGetLastError();

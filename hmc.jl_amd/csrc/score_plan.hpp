@@ -49,9 +49,6 @@ inline ScoreWork score_work(long long n_u, int K, int n_h)
 }
 inline size_t score_work_doubles(int W, long long n_u, int K, int n_h) { return (size_t)W * score_work(n_u, K, n_h).total; }
 
-inline int score_max_horizon(const hmcg_score& p) { return max_horizon(p.n_h, p.horizons); }
-// Draw columns per window that the host entry stages: mu, sig2, pi_end and, with a horizon > 0, A.
-inline int score_columns(const hmcg_score& p) { return 3 * p.K + (score_max_horizon(p) > 0 ? p.K * p.K : 0); }
 // Host entry: windows per upload group.  A staging buffer holds that many windows of ncol columns of n_u doubles; the default
 // keeps it near `target_bytes`; cap > 0 (HMCG_SCORE_GROUP_WINDOWS) lowers it.  At least one window.
 inline int score_group_windows(int W, long long n_u, int ncol, long long cap, size_t target_bytes = (size_t)64 << 20)
@@ -74,7 +71,7 @@ inline int check_score(const hmcg_score* p, const double* mu, const double* sig2
     if (told((long long)p->W * (nblk > nslab ? nblk : nslab) > 2147483647LL, msg, nmsg, "W * blocks per window exceeds one launch (2^31 - 1 blocks)"))
         return HMCG_E_BADARG;
     if (told(!mu || !sig2 || !pi_end || !yreal || !out, msg, nmsg, "mu, sig2, pi_end, yreal and out are required")) return HMCG_E_BADARG;
-    if (told(!A && score_max_horizon(*p) > 0, msg, nmsg, "A is NULL with a horizon > 0")) return HMCG_E_BADARG;
+    if (told(!A && mixture_max_horizon(*p) > 0, msg, nmsg, "A is NULL with a horizon > 0")) return HMCG_E_BADARG;
     return 0;
 }
 

@@ -1,7 +1,8 @@
 // stat_device.hpp -- the kernel pieces the draw statistics share (predictive.hip, bias.hip, mixmoments.hip, density.hip,
-// autocorr.hip): one copy of each, so that the next feature starts from parts and not from a paste.  Every piece is here in
-// the form under which every kernel that uses it compiles to the device assembly it had with its own copy (DESIGN.md
-// section 9, tools/isa_same.py); profiles/r10/README.md lists the forms that did not, and which copies stayed where they were.
+// autocorr.hip, order.hip, ergodic.hip, fan.hip, score.hip; the predictive mixture's LDS tile stands in mixture_tile.hpp):
+// one copy of each, so that the next feature starts from parts and not from a paste.  Every piece is here in the form under
+// which every kernel that uses it compiles to the device assembly it had with its own copy (DESIGN.md section 9,
+// tools/isa_same.py); profiles/r10/README.md lists the forms that did not, and which copies stayed where they were.
 // The macros are macros for that reason: as __forceinline__ functions the same statements compile to other code.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -81,3 +82,10 @@ static_assert(HMCG_MAXK == 8, "HMCG_SWITCH_K lists the cases");
         case 8: LAUNCH_(8); break;                                                                                        \
         default: return hipErrorInvalidValue;                                                                             \
     }
+// Host: launch kernel_ (one instance of a template) with lds_ bytes of dynamic LDS, raising the kernel's limit to that first.
+#define HMCG_LAUNCH_LDS(kernel_, grid_, block_, lds_, stream_, p_)                                                        \
+    do {                                                                                                                  \
+        hipError_t e_ = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel_), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds_)); \
+        if (e_ != hipSuccess) return e_;                                                                                  \
+        hipLaunchKernelGGL(kernel_, grid_, block_, lds_, stream_, p_);                                                    \
+    } while (0)

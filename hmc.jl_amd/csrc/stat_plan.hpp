@@ -1,6 +1,6 @@
-// stat_plan.hpp -- what the five draw statistics (predictive CDFs, bias moments, mixture moments, chain densities,
-// autocorrelation) share on the host: the cut of a window's draws into slabs and upload chunks, the argument rules every
-// check_* begins with, and the range rules of a launch.  Plain C++17 without a HIP header (in the manner of plan.hpp): a
+// stat_plan.hpp -- what the draw statistics share on the host: the cut of a window's draws into slabs and upload chunks, the
+// argument rules every check_* begins with, the horizon list and draw columns of the predictive mixture's four features, and
+// the range rules of a launch.  Plain C++17 without a HIP header (in the manner of plan.hpp): a
 // g++-compiled program runs exactly the code the library runs, on the CPU.
 //
 // Slabs: draws [s * PRED_SLAB, min((s + 1) * PRED_SLAB, nd)) of every window are reduced by one block in draw order; the
@@ -81,6 +81,19 @@ inline int max_horizon(int n_h, const int32_t* horizons)
     for (int j = 0; j < n_h; ++j) m = horizons[j] > m ? horizons[j] : m;
     return m;
 }
+// The horizon list as the kernels and launchers carry it: hz[HMCG_MAXH], zero from n_h on.  True when a horizon is > 0, that
+// is when the transition draws are read.
+inline bool fill_horizons(int n_h, const int32_t* horizons, int* hz)
+{
+    for (int j = 0; j < HMCG_MAXH; ++j) hz[j] = j < n_h ? horizons[j] : 0;
+    return max_horizon(HMCG_MAXH, hz) > 0;
+}
+// The four features of the predictive mixture.  S: hmcg_predictive, hmcg_mixmom, hmcg_fan or hmcg_score, which name n_h and
+// horizons alike: the largest horizon of a checked call ...
+template <class S>
+inline int mixture_max_horizon(const S& p) { return max_horizon(p.n_h, p.horizons); }
+// ... and the draw columns per window a call reads: mu, sig2, pi_end (K each) and A (K * K) with a horizon > 0.
+inline int mixture_columns(int K, bool with_A) { return 3 * K + (with_A ? K * K : 0); }
 
 // A launch over slabs [slab0, slab0 + pred_slabs(nd)) of a run of nslab_total: inside the run, the arrays long enough, one
 // block per (window, slab) within a grid.
