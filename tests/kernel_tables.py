@@ -7,10 +7,16 @@ that silently drops a row fails there.
 csrc/variants.hpp (HMCG_BIG_FORM: the K list) and the variants_big*.hip units (g_big_xyz = HMCG_BIG_FORM(sig, smooth, stream))
 define 8 forms x K = 2..8 = 56 separately compiled LDS-resident kernels; the variants_*.hip tables hold the register-resident
 rows: HMCG_V3(K, L, sig, smooth, ...) expands to three flavours, HMCG_V(K, L, NT, sig, smooth, NH, OCC, ...) is one kernel.  A
-new unit, row, K or form is picked up by everything derived here."""
+new unit, row, K or form is picked up by everything derived here.
+
+Below that, what the two per-instantiation contracts share (test_variant_coverage.py for the sampler, test_stat_coverage.py for
+the draw-statistic kernels): a test's parametrize list, the kernel symbols of the built library (read with nm from the file, not
+by loading it), and the launch rules of the statistic units parsed from their sources."""
 import glob
 import os
 import re
+import shutil
+import subprocess
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "hmc.jl_amd", "csrc")
@@ -117,3 +123,135 @@ def coverage_lengths(sig, smooth, stream, K):
     leaves on the same launch."""
     top = STREAM_T if stream else max(ladder_ceiling(K, sig, smooth), 2 * NT) + NT + 45
     return [top, 8 if sig else 2, 64, 65, 257]
+
+
+# ---- what the per-instantiation contracts share (tests/test_variant_coverage.py, tests/test_stat_coverage.py) ----
+def cases_of(test, argnames=None):
+    """The argument tuples of a test function's pytest.mark.parametrize: what the suite actually runs.  A test with several
+    parametrize marks names the one it means by its argnames."""
+    marks = [m for m in getattr(test, "pytestmark", []) if m.name == "parametrize" and (argnames is None or m.args[0] == argnames)]
+    assert len(marks) == 1, test.__name__
+    return list(marks[0].args[1])
+
+
+def library_symbols(pattern):
+    """The defined dynamic symbols of the built libhmcgibbs.so that match `pattern` (a regex over one symbol name), as a set.
+    Read with nm from the file: the library is not loaded."""
+    from hmc_jl_amd import _lib
+    nm = shutil.which("nm") or shutil.which("llvm-nm") or shutil.which("llvm-nm", path="/opt/rocm/llvm/bin")
+    assert nm, "no nm / llvm-nm to list the symbols of libhmcgibbs.so"
+    assert os.path.exists(_lib.SO_PATH), "libhmcgibbs.so is not built"
+    out = subprocess.run([nm, "-D", "--defined-only", _lib.SO_PATH], check=True, capture_output=True, text=True).stdout
+    return set(re.findall(r"\b(%s)\b" % pattern, out))
+
+
+def template_ints(field):
+    """The integer template arguments of an Itanium name's I...E field: its Li<int>E / Lb<0|1>E entries, in order."""
+    return [int(x) for x in re.findall(r"L[ib](\d+)E", field)]
+
+
+# The templated draw-statistic kernels: name -> (unit that launches it, number of integer template arguments).
+STAT_KERNELS = {
+    "predictive_cdf_kernel": ("predictive.hip", 1),
+    "fan_eval_kernel": ("fan.hip", 1),
+    "score_comp_kernel": ("score.hip", 1),
+    "score_pair_kernel": ("score.hip", 1),
+    "mixmoments_kernel": ("mixmoments.hip", 2),
+    "bias_moments_kernel": ("bias.hip", 1),
+    "ergodic_kernel": ("ergodic.hip", 1),
+    "draw_moments_kernel": ("moments.hip", 1),
+}
+
+
+def stat_instantiations():
+    """{kernel name: sorted list of template-argument tuples} of the draw-statistic kernels in the built library, from the kernel
+    handles of its dynamic symbol table (_ZN4hmcg<len><name>I<Li..E>+EEvNS_<len><Params>E; the __device_stub__ twins are other
+    names).  A handle of one of these kernels whose shape the pattern does not know fails here."""
+    names = library_symbols(r"_ZN4hmcg\d+(?:%s)I\w+" % "|".join(STAT_KERNELS))
+    out = {k: [] for k in STAT_KERNELS}
+    for name in sorted(names):
+        m = re.match(r"_ZN4hmcg(\d+)([a-z_]+)I((?:L[ib]\d+E)+)EEvNS_\d+\w+ParamsE$", name)
+        assert m and m.group(2) in STAT_KERNELS and int(m.group(1)) == len(m.group(2)), "kernel symbol of an unknown shape: " + name
+        args = tuple(template_ints(m.group(3)))
+        assert len(args) == STAT_KERNELS[m.group(2)][1], name
+        out[m.group(2)].append(args)
+    return {k: sorted(v) for k, v in out.items()}
+
+
+def switch_cases(text, selector, launch):
+    """{case value: launched template argument} of `switch (<selector>) { case n: <launch>(m); break; ... }` in a source text
+    without comments; the whole body up to the closing brace must consist of such lines (and a default)."""
+    m = re.search(r"switch\s*\(\s*%s\s*\)\s*\{(.*?)\}" % re.escape(selector), text, re.S)
+    assert m, "no switch (%s)" % selector
+    body = m.group(1).replace("\\\n", "\n")
+    rows = re.findall(r"case\s+(\d+)\s*:\s*%s\(\s*(\d+)\s*\)\s*;\s*break\s*;" % re.escape(launch), body)
+    rest = re.sub(r"case\s+\d+\s*:\s*%s\(\s*\d+\s*\)\s*;\s*break\s*;" % re.escape(launch), "", body)
+    rest = re.sub(r"default\s*:[^;]*;", "", rest).strip()
+    assert rows and not rest, "switch (%s): lines of another shape: %r" % (selector, rest)
+    out = {int(a): int(b) for a, b in rows}
+    assert len(out) == len(rows), "switch (%s): a case twice" % selector
+    return out
+
+
+def header_int(name, path=os.path.join(ROOT, "include", "hmcg.h")):
+    """#define <name> <int> of a header."""
+    m = re.search(r"^\s*#\s*define\s+%s\s+(\d+)\b" % name, open(path).read(), re.M)
+    assert m, name
+    return int(m.group(1))
+
+
+def stat_switch_k():
+    """HMCG_SWITCH_K of csrc/stat_device.hpp: {K: the K_ it launches}."""
+    text = _code(os.path.join(CSRC, "stat_device.hpp")).replace("\\\n", "\n")
+    m = re.search(r"#define\s+HMCG_SWITCH_K\(k_,\s*LAUNCH_\)\s*(switch.*?\})", text, re.S)
+    assert m, "HMCG_SWITCH_K"
+    return switch_cases(m.group(1), "k_", "LAUNCH_")
+
+
+def stat_launch_rules():
+    """How each draw-statistic unit picks its instantiation, parsed from the launch lines of its source (comments removed):
+      'K'     {K: K_}: HMCG_SWITCH_K, and that predictive / fan / score / mixmoments / bias / ergodic launch through it on a.K with
+              a macro whose kernel takes K_ first;
+      'pair'  {n_h: NH} of score.hip's switch (a.n_h);
+      'nhc'   (limit, small, large): mixmoments.hip launches <K_, small> if a.n_h <= limit, else <K_, large> (HMCG_MAXH resolved
+              from include/hmcg.h)."""
+    by_k = stat_switch_k()
+    for unit, kernel, macro in (("predictive.hip", "predictive_cdf_kernel", "HMCG_PRED"), ("fan.hip", "fan_eval_kernel", "HMCG_FAN_EVAL"),
+                                ("score.hip", "score_comp_kernel", "HMCG_SCORE_COMP"), ("mixmoments.hip", "mixmoments_kernel", "HMCG_MIX"),
+                                ("bias.hip", "bias_moments_kernel", "HMCG_BIAS"), ("ergodic.hip", "ergodic_kernel", "HMCG_ERG")):
+        text = _code(os.path.join(CSRC, unit))
+        assert re.search(r"HMCG_SWITCH_K\(\s*a\.K\s*,\s*%s\s*\)" % macro, text), (unit, "does not launch through HMCG_SWITCH_K(a.K, %s)" % macro)
+        d = re.search(r"#define\s+%s\(K_\)((?:[^\n]*\\\n)*[^\n]*)" % macro, text)
+        assert d, (unit, macro)
+        used = re.findall(r"hmcg::(\w+)<([^>]*)>", d.group(1))
+        assert used and all(k == kernel and a.split(",")[0].strip() == "K_" for k, a in used), (unit, used)
+    score = _code(os.path.join(CSRC, "score.hip"))
+    assert re.search(r"#define\s+HMCG_SCORE_PAIR\(NH_\)\s+hipLaunchKernelGGL\(\s*hmcg::score_pair_kernel<NH_>", score)
+    pair = switch_cases(score, "a.n_h", "HMCG_SCORE_PAIR")
+    mix = _code(os.path.join(CSRC, "mixmoments.hip")).replace("\\\n", "\n")
+    m = re.search(r"if\s*\(\s*a\.n_h\s*<=\s*(\d+)\s*\)\s*hipLaunchKernelGGL\(\(hmcg::mixmoments_kernel<K_,\s*(\w+)>\)[^;]*;\s*"
+                  r"else\s+hipLaunchKernelGGL\(\(hmcg::mixmoments_kernel<K_,\s*(\w+)>\)", mix)
+    assert m, "mixmoments.hip: the two launch lines of HMCG_MIX"
+    val = lambda s: int(s) if s.isdigit() else header_int(s)
+    return {"K": by_k, "pair": pair, "nhc": (int(m.group(1)), val(m.group(2)), val(m.group(3)))}
+
+
+def bias_constants():
+    """What csrc/bias.hip deals its items by, read from its source: 'waves' = BIAS_NT / 64, 'items' = bias_nitems as a function
+    of K (the constexpr one-liners bias_nv / bias_nc / bias_np / bias_nitems, evaluated as written), 'unroll_max' = the largest
+    K whose four sub-tiles are unrolled (UNR = K <= n ? BIAS_NW : 1)."""
+    text = _code(os.path.join(CSRC, "bias.hip"))
+    nt = int(re.search(r"constexpr\s+int\s+BIAS_NT\s*=\s*(\d+)\s*;", text).group(1))
+    assert re.search(r"constexpr\s+int\s+BIAS_NW\s*=\s*BIAS_NT\s*/\s*64\s*;", text)
+    fns = dict(re.findall(r"constexpr\s+int\s+(bias_n\w+)\(int K\)\s*\{\s*return\s+([^;]+);\s*\}", text))
+    assert set(fns) >= {"bias_nv", "bias_nc", "bias_np", "bias_nitems"}, sorted(fns)
+    assert all(re.fullmatch(r"[\w\s()+*]+", body) for body in fns.values()), fns      # sums and products of K and each other
+
+    def call(name, K):
+        env = {n: (lambda k, n=n: call(n, k)) for n in fns}
+        env["K"] = K
+        return eval(fns[name], {"__builtins__": {}}, env)
+    m = re.search(r"UNR\s*=\s*K\s*<=\s*(\d+)\s*\?\s*BIAS_NW\s*:\s*1\b", text)
+    assert m, "bias.hip: the unroll switch"
+    assert re.search(r"PPW\s*=\s*\(bias_nitems\(K\)\s*\+\s*BIAS_NW\s*-\s*1\)\s*/\s*BIAS_NW", text)
+    return {"waves": nt // 64, "items": lambda K: call("bias_nitems", K), "unroll_max": int(m.group(1))}

@@ -169,15 +169,36 @@ def used_counts(K):
     return (1, TP // K, TP // K + 1, 2 * TP // K, 2 * TP // K + 1, SLAB - 1, SLAB + 1)
 
 
+NEW_KS = (4, 5, 6, 7)                    # the K between: a draw's components straddle the 256-component tile edge at 5, 6, 7
+# horizon tuples of the K = 4..7 cases: every length the first table lacks, so that score_pair_kernel<2|4|5|6|7> run from here
+NEW_HZS = ((0, 12), (0, 1, 2, 12), (0, 1, 2, 3, 12), (0, 0, 1, 3, 5, 12), (0, 1, 2, 3, 5, 8, 12))
+# The long-double reference costs W N^2 evaluations of a(m, S2), N = n_u K.  The largest of the K in {2, 3, 8} table is K = 8 at
+# 1 025 used draws in one window: no case may cost more.
+PAIR_BUDGET = (8 * (SLAB + 1)) ** 2
+
+
+def pair_cost(K, n_u, W):
+    return W * (n_u * K) ** 2
+
+
 def _gpu_cases():
     """(K, n_u, stride, pad, round5, horizons, W): K in {2, 3, 8} crossed with used_counts(K), the other options dealt
-    round-robin; then the default-stride case."""
+    round-robin; then K = 4..7 crossed with used_counts(K) and the horizon tuples of NEW_HZS, dealt the same way -- a case whose
+    reference would exceed PAIR_BUDGET runs one window, and is dropped if it still does (none is: every K keeps its slab edges)."""
     strides, pads, r5 = (1, 2, 3), (0, 5), (True, False)
     hzs, Ws = ((0,), (0, 1, 12), H8), (1, 3)
     out, i = [], 0
     for K in (2, 3, 8):
         for n_u in used_counts(K):
             out.append((K, n_u, strides[i % 3], pads[i % 2], r5[(i // 2) % 2], hzs[(i + i // 3) % 3], Ws[(i // 3) % 2]))
+            i += 1
+    i = 0
+    for K in NEW_KS:
+        for n_u in used_counts(K):
+            W = Ws[(i // 3) % 2]
+            W = W if pair_cost(K, n_u, W) <= PAIR_BUDGET else 1
+            if pair_cost(K, n_u, W) <= PAIR_BUDGET:
+                out.append((K, n_u, strides[i % 3], pads[i % 2], r5[(i // 2) % 2], NEW_HZS[i % 5], W))
             i += 1
     return out
 

@@ -6,9 +6,10 @@ Per-cell absolute tolerance (bias_cases.tolerance, derived, not measured): cov (
 R = max |v - v_0| per column; mean, uncbias and totalbias follow from it.  NaN positions must match exactly.
 
 Largest differences an MI355X run of this module showed, as |diff| / its bound: cov 0.055 (K = 8, nd = 2, h = 12: 6.7e-16
-against 1.2e-14), the largest absolute one 1.06e-14 against 1.4e-10 (K = 8, nd = 2065, raw draws); uncbias 0.0065 (3.1e-15
-against 6.2e-13, K = 2, nd = 2); totalbias 0.12 (1.4e-16 against 1.1e-15, nd = 2); mean 0.79 in the offset case (8.8e-13 against
-1.1e-12: one rounding of a value near 1e4), 0.06 elsewhere.  Predictive CDF against mean[0:K] on a one-hot mixture: 3.3e-16
+against 1.2e-14), among K = 4..7 0.042 (K = 7, nd = 2, h = 12: 6.2e-16 against 1.5e-14), the largest absolute one 1.06e-14 against
+1.4e-10 (K = 8, nd = 2065, raw draws); uncbias 0.019 (2.4e-15 against 1.2e-13, K = 6, nd = 2, h = 0); totalbias 0.23 (1.1e-16
+against 4.9e-16, K = 4, nd = 2: one rounding); mean 0.79 in the offset case (8.8e-13 against 1.1e-12: one rounding of a value near
+1e4), in the case table 0.63 (K = 7, nd = 2, h = 12: 4.4e-16, one rounding, against 9.8e-16).  Predictive CDF against mean[0:K] on a one-hot mixture: 3.3e-16
 against 4.4e-13.  Device against file route on the inflation data (nd = 1500): cov 1.3e-17 and 2.9e-17 from the reference."""
 import datetime as dt
 
@@ -65,6 +66,23 @@ def _cases():
             (3, 1, 1, 12, 0, True, 1),                     # nd = 1 at the reference's own horizon
             (8, 2, 1, 12, 5, True, 2),
             (3, S, 1, 12, 0, False, 0)]
+    return out + _mid_k_cases()
+
+
+NEW_KS = (4, 5, 6, 7)             # the K between the three above: items mod 4 = 1, 2, 3, 0; K = 6, 7 on the non-unrolled path
+
+
+def _mid_k_cases():
+    """K = 4..7 at the smallest sizes that still meet every edge: two draws, one over a lane's first draw (a lane takes draws l,
+    l + 64, l + 128, l + 192 of the 256-draw tile), one over the tile, one over the slab, one over two slabs and a tile; horizon
+    0 (A = NULL) or 12, with or without the forecast-error column, nd_ld = nd or nd + 5 and round5 on / off dealt so that every
+    K meets each (tests/test_stat_coverage.py checks the deal)."""
+    out = []
+    idx = 0
+    for K in NEW_KS:
+        for nd in (2, 65, 257, 1025, 2065):
+            out.append((K, nd, 3 if nd <= 65 else 1, (0, 12)[idx % 2], 5 * ((idx // 2) % 2), (idx // 3) % 2 == 0, (1, 0)[((idx + 1) // 2) % 2]))
+            idx += 1
     return out
 
 
@@ -178,7 +196,7 @@ def test_same_omega_as_the_predictive_feature():
         assert (diff <= bound).all() and (cdf[:, 0, 0] > 0.01).all()
 
 
-@pytest.mark.parametrize("K,T,nrun", [(3, 200, 700), (8, 700, 200)])
+@pytest.mark.parametrize("K,T,nrun", [(3, 200, 700), (8, 700, 200), (5, 300, 200)])
 def test_device_panel_bias_moments(K, T, nrun):
     """DevicePanel.bias_moments on the draws `run` left in HBM (K = 8 / T = 700 runs the LDS-resident kernel, whose scratch
     shares the device context with the slab sums); the draws are unchanged afterwards."""

@@ -12,9 +12,11 @@ collapsed below the resolution of F, rounds = 10).  Without round5 the returned 
 as its grid, give Flo and Fhi back bit for bit.
 
 What an MI355X run of this module showed: the largest |F_ld(q) - p| / (B + 4 tolF) 0.656 on the hand-made draws (K = 2, one
-draw, one round) and 0.923 on the inflation data (nd = 1500, 4 rounds, the device and the file route alike: B is most of the
+draw, one round; in the case table 0.404 at K = 5, one draw, two rounds, then 0.335 at K = 3 and 0.323 at K = 6, one draw each;
+0.143 at K = 7, nd = 65; below 0.1 at nd = 1025 for every K) and 0.923 on the inflation data (nd = 1500, 4 rounds, the device and the file route alike: B is most of the
 bound there); every bracket the restatement's except 2 of 45 and 3 of 48 at rounds = 10, where a step is two ulps of y; the
-largest |q - q_ref| 1.1e-10 (K = 8, two rounds); the device and the file route 4.4e-16 apart on the inflation data."""
+largest |q - q_ref| 4.6e-10 (K = 4, nd = 1025, one round: a bracket of (hi0 - lo0) / 128) and 1.1e-10 (K = 8, two rounds), every
+bracket of the K = 4..7 cases the restatement's; the device and the file route 4.4e-16 apart on the inflation data."""
 import datetime as dt
 
 import numpy as np
@@ -100,6 +102,23 @@ def _cases():
             (3, 65, 3, fc.H8, fc.PROBS5, 4, 5, True),                    # HMCG_MAXH horizons, two of them equal
             (8, 65, 1, (0, 1, 2, 3, 5, 8, 12, 40), fc.PROBS16, 2, 0, False),     # the largest LDS tile, 3 968 items: 31 blocks of them
             (3, 63, 3, (0,), fc.PROBS16, 10, 0, False)]                  # the collapse of the bracket at every probability
+    return out + _mid_k_cases(nps)
+
+
+NEW_KS = (4, 5, 6, 7)             # the K between the three above: other staging remainders, LDS offsets and unrollings
+
+
+def _mid_k_cases(nps):
+    """K = 4..7 at the smallest sizes that still meet every edge: one draw, one over the 64-draw tile, one over the slab, with
+    the three probability sets, one or two rounds, horizons (0,) with A = NULL or (0, 1, 12), nd_ld = nd or nd + 5 and round5
+    on / off dealt so that every K meets each (tests/test_stat_coverage.py checks the deal)."""
+    out = []
+    idx = 0
+    for K in NEW_KS:
+        for nd in (1, 65, 1025):
+            out.append((K, nd, 3 if nd <= 65 else 1, (0,) if (idx // 2) % 2 == 0 else (0, 1, 12), nps[idx % 3], (1, 2)[idx % 2],
+                        5 * ((idx + idx // 3) % 2), ((idx + 1) // 2) % 2 == 0))
+            idx += 1
     return out
 
 
@@ -216,11 +235,13 @@ def test_runs_entries_and_chunkings_give_the_same_bits(monkeypatch):
     assert _same_bits(h0["quantile"][:, 0], out[:, 0, :, 0])
 
 
-def test_device_panel_fan():
-    """DevicePanel.fan on the draws `run` left in HBM; the draws are unchanged afterwards."""
+@pytest.mark.parametrize("K,T,nrun", [(3, 200, 700), (5, 300, 200)])
+def test_device_panel_fan(K, T, nrun):
+    """DevicePanel.fan on the draws `run` left in HBM (K = 5, T = 300: the sampler's own K = 5 draws -- from the LDS-resident
+    kernel, there are no register-resident rows above K = 4 -- feed fan_eval_kernel<5>); the draws are unchanged afterwards."""
     from hmc_jl_amd import _lib, synth
     from hmc_jl_amd.device import DevicePanel
-    K, T, nrun, W = 3, 200, 700, 3
+    W = 3
     Y, Tw, fut = synth.generate_panel(W, T, K)
     p = DevicePanel(Y, Tw, K, nrun, (12,), fut[:, 11:12])
     p.run(burnin=20, timed=False)

@@ -8,10 +8,12 @@ eps_omega = 2 K h u per weight, n-term sums about the pivot with R = max |mu - c
 polynomials and the divisions by var^1.5 and var^2.  NaN positions must match exactly.
 
 Largest differences an MI355X run of this module showed, as |diff| / its bound: mean 0.74 in the offset case (8.5e-13 against
-1.1e-12: one rounding of a value near 1e4), 0.01 elsewhere; variance 0.011 (4.5e-15 against 1.7e-11, K = 8, nd = 1, the eight
-horizons); skewness 0.00097 (1.9e-16 against 1.9e-13, K = 2, nd = 1); kurtosis 0.00072 (1.4e-15 against 5.4e-11); within 0.0044
-(2.3e-15 against 2.2e-12); between 0.0005 (2.4e-15 against 6.5e-12, nd = 2); draw_skewness 0.0024 (4.8e-16 against 1.3e-12);
-weight 0.16 (3.5e-16 against 2.5e-14, nd = 1).  The bound is a worst case over every summation order, so two to three digits of
+1.1e-12: one rounding of a value near 1e4), in the case table 0.029 (4.0e-16 against 1.4e-14; this and the next four at K = 6,
+nd = 1, horizons (0, 1, 12), raw draws); variance 0.011 (4.5e-15 against 1.7e-11, K = 8, nd = 1, the eight horizons), among K = 4..7
+0.0086 (K = 4, nd = 1, horizon 0); skewness 0.0030 (3.7e-16 against 1.2e-13); kurtosis 0.0011 (8.9e-16 against 1.5e-11); within
+0.0087 (1.6e-15 against 1.3e-12); between 0.0005 (2.4e-15 against 6.5e-12, K = 3, nd = 2), among K = 4..7 0.0003 (K = 7, nd = 2);
+draw_skewness 0.0024 (4.8e-16 against 1.3e-12, K = 3, nd = 1), among K = 4..7 0.0016 (K = 6, nd = 1); weight 0.16 (3.5e-16 against
+2.5e-14, K = 3, nd = 1), among K = 4..7 0.13 (K = 6, nd = 1).  The bound is a worst case over every summation order, so two to three digits of
 slack are its nature, not a sign of a loose derivation constant.  Mean weight against the predictive CDF at y = 1e6: 7.8e-16
 against 4.5e-13.  Pooled mean at h = 12 against the mean of the sampler's forecast draws: 8.0e-15 against 2.4e-12 (K = 3),
 1.1e-14 against 9.2e-12 (K = 8).  Identical draws: variance - within exactly 0."""
@@ -75,6 +77,22 @@ def _cases():
             (8, 1, 3, H8, 5, True),
             (2, 1, 1, (0, 1, 12), 0, False),
             (8, 2, 1, (0, 1, 12), 5, True)]
+    return out + _mid_k_cases()
+
+
+NEW_KS = (4, 5, 6, 7)             # the K between the three above; each in both builds, NHC = 2 (n_h <= 2) and NHC = HMCG_MAXH
+
+
+def _mid_k_cases():
+    """K = 4..7 at the smallest sizes that still meet every edge: one and two draws, one over the wave, the tile and the slab;
+    the four horizon sets in turn (five sizes per K: every K meets all four, (0,) with A = NULL and H8 among them), W, nd_ld and
+    round5 dealt as above (tests/test_stat_coverage.py checks the deal)."""
+    out = []
+    idx = 0
+    for K in NEW_KS:
+        for nd in (1, 2, 65, 257, 1025):
+            out.append((K, nd, (1, 3)[(idx // 2) % 2], HSETS[idx % 4], 5 * ((idx // 2) % 2), (idx // 3) % 2 == 0))
+            idx += 1
     return out
 
 
@@ -200,7 +218,7 @@ def test_same_omega_as_the_predictive_feature():
     assert (diff <= bound).all() and (np.abs(got["weight"] - 1.0) < 1e-3).all()
 
 
-@pytest.mark.parametrize("K,T,nrun", [(3, 200, 700), (8, 700, 200)])
+@pytest.mark.parametrize("K,T,nrun", [(3, 200, 700), (8, 700, 200), (5, 300, 200)])
 def test_device_panel_mixture_moments(K, T, nrun):
     """DevicePanel.mixture_moments on the draws `run` left in HBM (K = 8 / T = 700 runs the LDS-resident kernel, whose scratch
     shares the device context with the slab sums); the draws are unchanged afterwards.  With round5 off the pooled mean at h = 12

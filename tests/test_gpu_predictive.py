@@ -6,8 +6,11 @@ vector-matrix products, Phi via math.erfc, np.mean.  Absolute tolerance (predict
 (nd + 64 + 2 K h_max) 2^-52.  NaN positions must match exactly.
 
 Largest difference an MI355X run of this module showed: 2.442e-15 = 11 * 2^-52 (K = 2, nd = 1023, horizons (0, 1, 12), raw draws,
-and K = 8, nd = 1025, horizons (12, 0)) against tolerances of 2.5e-13 and 2.8e-13 there; 2.3e-15 between the device and the
-file route on the inflation data (nd = 1500)."""
+and K = 8, nd = 1025, horizons (12, 0)) against tolerances of 2.5e-13 and 2.8e-13 there; among the K = 4..7 cases 1.776e-15 =
+8 * 2^-52 (K = 7, nd = 1025, horizons (0, 1, 12)) against 2.8e-13, and at each K's largest LDS tile (eight horizons, nd = 65) 2 to
+3 * 2^-52 (6.7e-16 at K = 7) against 1.0e-13 to 1.5e-13.  As |diff| / tolerance the largest is 0.023 (K = 4, nd = 65, G = 65, raw draws: 6.7e-16 against
+2.9e-14; K = 7, one draw: 3.3e-16 against 1.4e-14).  2.3e-15 between the device and the file route on the inflation data
+(nd = 1500)."""
 import datetime as dt
 
 import numpy as np
@@ -60,7 +63,26 @@ def _cases():
             (8, S + 1, 64, 1, (12, 0), 0, True),               # horizons in another order
             (3, 65, 81, 3, (0, 0, 1, 2, 3, 5, 8, 12), 5, True),    # HMCG_MAXH horizons: more than one block of items
             (8, 65, 65, 1, (0, 1, 2, 3, 5, 8, 12, 40), 0, False)]  # the largest LDS tile (73.7 KB)
-    return out
+    return out + _mid_k_cases()
+
+
+NEW_KS = (4, 5, 6, 7)             # the K between the three above: other staging remainders, LDS offsets and unrollings
+H8 = (0, 1, 2, 3, 5, 8, 12, 40)
+
+
+def _mid_k_cases():
+    """K = 4..7 at the smallest sizes that still meet every edge: one draw, one over the 64-draw tile, one over the slab, with
+    G in {1, 65}, horizons (0,) with A = NULL or (0, 1, 12), nd_ld = nd or nd + 5 and round5 on / off dealt so that every K
+    meets each (tests/test_stat_coverage.py checks the deal); then per K its largest LDS tile: eight horizons with A, a partial
+    grid block, a partial draw tile (K = 7: 60 928 B, past the 48 KB that need the attribute call of HMCG_LAUNCH_LDS)."""
+    out = []
+    idx = 0
+    for K in NEW_KS:
+        for nd in (1, 65, 1025):
+            out.append((K, nd, (1, 65)[idx % 2], 3 if nd <= 65 else 1, (0,) if (idx // 2) % 2 == 0 else (0, 1, 12),
+                        5 * ((idx + idx // 3) % 2), ((idx + 1) // 2) % 2 == 0))
+            idx += 1
+    return out + [(K, 65, 65, 1, H8, 5 * (K % 2), K % 2 == 0) for K in NEW_KS]
 
 
 @pytest.mark.parametrize("K,nd,G,W,horizons,pad,round5", _cases())
@@ -141,7 +163,7 @@ def test_host_entry_equals_device_entry_bit_for_bit(monkeypatch):
     assert np.array_equal(h0[:, 0], dev[:, 0])
 
 
-@pytest.mark.parametrize("K,T,nrun", [(3, 200, 700), (8, 700, 200)])
+@pytest.mark.parametrize("K,T,nrun", [(3, 200, 700), (8, 700, 200), (5, 300, 200)])
 def test_device_panel_predictive_cdf(K, T, nrun):
     """DevicePanel.predictive_cdf on the draws `run` left in HBM (K = 8 / T = 700 runs the LDS-resident kernel, whose scratch
     shares the device context with the slab sums); the draws are unchanged afterwards."""

@@ -12,8 +12,11 @@ law, unknown, and 40 standard deviations out on either side.  Bits: two runs, bo
 windows per group, equal horizons, identical windows; without rounding and thinning pit is hmcg_predictive_cdf_device's value
 at yreal bit for bit, at horizons > 0 too, so the weights hold the siblings' bits.
 
-What an MI355X run of this module showed: the largest |device - ref| / bound 0.016 (K = 2, 129 used draws, eight horizons, in
-e_abs), e_pair never above 0.002 of its bound at more than one draw; on the inflation data (1 500 draws, horizons 0 and 12) the
+What an MI355X run of this module showed, as the largest |device - ref| / bound per field and its case: crps and e_abs 0.016
+(K = 2, 129 used draws, eight horizons), e_pair 0.011 (K = 3, one draw) and 0.002 at more than one draw (K = 5, 52 used draws:
+the draw that straddles the tile edge), pit 0.0085 (K = 5, 52 used draws, seven horizons), pdf 0.0068 (K = 3, one draw); among
+the K = 4..7 cases e_abs 0.013 (K = 4, 129 used draws, seven horizons), crps 0.009 (K = 5, 103 used draws), e_pair 0.0035 and
+pdf 0.0023 (K = 4, one draw); on the inflation data (1 500 draws, horizons 0 and 12) the
 device 0.0041 and the file route 0.0005 of the bound from the reference, 0.0023 of twice the bound from each other.
 Measured at 460 windows x 250 000 draws, horizons (0, 12), default thinning (4 033 used draws), tools/score_bench.py: 156 ms at
 K = 3 (3.44e10 pair terms, 2.20e11 /s) and 1 058 ms at K = 8 (2.28e11 /s) beside hmcg_predictive_cdf_device's 185 ms (3.02e11
@@ -215,12 +218,14 @@ def test_edge_inputs():
     assert np.isnan(blind[..., [0, 1, 3, 4]]).all() and _same_bits(blind[..., 2], known[..., 2]) and (known[..., 2] > 0.0).all()
 
 
-def test_device_panel_scores():
-    """DevicePanel.scores on the draws `run` left in HBM (K = 3, T = 200, 700 draws, 3 windows) against the reference from the
-    read-back draws; the draws are unchanged afterwards; a panel without draws refuses as `fan` does."""
+@pytest.mark.parametrize("K,T,nrun", [(3, 200, 700), (5, 300, 200)])
+def test_device_panel_scores(K, T, nrun):
+    """DevicePanel.scores on the draws `run` left in HBM (K = 3, T = 200, 700 draws; K = 5, T = 300, 200 draws: the
+    sampler's own K = 5 draws, from the LDS-resident kernel, feed score_comp_kernel<5>; 3 windows) against the reference from the read-back draws;
+    the draws are unchanged afterwards; a panel without draws refuses as `fan` does."""
     from hmc_jl_amd import _lib, synth
     from hmc_jl_amd.device import DevicePanel
-    K, T, nrun, W = 3, 200, 700, 3
+    W = 3
     Y, Tw, fut = synth.generate_panel(W, T, K)
     p = DevicePanel(Y, Tw, K, nrun, (12,), fut[:, 11:12])
     p.run(burnin=20, timed=False)
@@ -237,7 +242,7 @@ def test_device_panel_scores():
     assert _same_bits(out, timed.cpu().numpy())
     ref, bound = sc.reference(before["mu"], before["sig2"], before["pi_end"], before["A"], y, horizons, 1, True)
     _check(out, ref, bound, "panel")
-    blind = p.scores(horizons)                                 # no realised values: the sharpness alone; default thinning = all 700
+    blind = p.scores(horizons)                                 # no realised values: the sharpness alone; default thinning = every draw
     p.sync()
     assert _same_bits(blind.cpu().numpy()[..., 2], out[..., 2]) and np.isnan(blind.cpu().numpy()[..., 0]).all()
     for n in _lib.DRAW_KEYS:

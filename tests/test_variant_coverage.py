@@ -10,10 +10,7 @@ parsed tables: every smoothing-capable form has a case there.
 
 The device entry's contract is held the same way: every pointer member of hmcg_extras (parsed from include/hmcg.h) is passed by
 some case of tests/test_gpu_device_entry.py, and its split-chain table covers every kernel form."""
-import os
 import re
-import shutil
-import subprocess
 
 import device_entry
 import kernel_tables as kt
@@ -37,25 +34,18 @@ def fmt_big(b):
     return "gibbs_sweeps_kernel_big<K=%d, 256, SM=%d, ST=%d, SIG=%d> (form %d%d%d)" % (K, sm, st, sig, sig, sm, st)
 
 
-def cases_of(test):
-    """The argument tuples of a test function's pytest.mark.parametrize: what the suite actually runs."""
-    marks = [m for m in getattr(test, "pytestmark", []) if m.name == "parametrize"]
-    assert len(marks) == 1, test.__name__
-    return list(marks[0].args[1])
+cases_of = kt.cases_of                                                  # a test's parametrize list: what the suite actually runs
 
 
 def library_kernels():
     """The instantiations in the built library, from its kernel symbols (Itanium names: the template arguments are the
     Li<int>E / Lb<0|1>E fields, as tools/isa_lint.py reads them)."""
-    nm = shutil.which("nm") or shutil.which("llvm-nm") or shutil.which("llvm-nm", path="/opt/rocm/llvm/bin")
-    assert nm, "no nm / llvm-nm to list the symbols of libhmcgibbs.so"
-    assert os.path.exists(_lib.SO_PATH), "libhmcgibbs.so is not built"
-    names = set(re.findall(r"\b(_ZN4hmcg\d+gibbs_sweeps_kernel(?:_big)?I\w+)", subprocess.run([nm, "-D", "--defined-only", _lib.SO_PATH], check=True, capture_output=True, text=True).stdout))
+    names = kt.library_symbols(r"_ZN4hmcg\d+gibbs_sweeps_kernel(?:_big)?I\w+")
     regs, bigs = [], []
     for name in sorted(names):
         m = re.match(r"_ZN4hmcg\d+gibbs_sweeps_kernel(_big)?I((?:L[ib]\d+E)+)EEvNS_12KernelParamsE", name)
         assert m, "kernel symbol of an unknown shape: " + name
-        a = [int(x) for x in re.findall(r"L[ib](\d+)E", m.group(2))]
+        a = kt.template_ints(m.group(2))
         if m.group(1):
             K, nt, sm, st, sig = a
             assert nt == 256, name
