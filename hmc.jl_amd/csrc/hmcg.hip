@@ -218,6 +218,7 @@ void destroy_context(DeviceCtx& c)
     (void)hipSetDevice(c.phys);
     (void)hipStreamSynchronize(c.stream);        // nothing of ours may still be running when the streams go
     (void)hipStreamSynchronize(c.copy);
+    (void)hipEventSynchronize(c.ev_scr);         // ... nor a device entry's work on a caller's stream: it may be using the arenas freed below
     (void)hipStreamDestroy(c.stream);
     (void)hipStreamDestroy(c.copy);
     (void)hipEventDestroy(c.ev0);
@@ -999,7 +1000,10 @@ int stat_device(DeviceCtx& c, Arena& work, size_t work_bytes, hipStream_t stream
     if (rc) return rc;
     HIP_TRY(hipStreamWaitEvent(stream, c.ev_scr, 0));
     if (timing) HIP_TRY(hipEventRecord(c.ev0, stream));
-    if ((rc = body())) return rc;
+    if ((rc = body())) {
+        (void)hipEventRecord(c.ev_scr, stream);          // what body did enqueue before it failed may be using the arena
+        return rc;
+    }
     HIP_TRY(hipEventRecord(c.ev_scr, stream));
     if (timing) {
         HIP_TRY(hipEventRecord(c.ev1, stream));

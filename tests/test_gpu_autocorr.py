@@ -21,38 +21,19 @@ import numpy as np
 import pytest
 
 import autocorr_cases as ac
+import stat_device_entry as sde
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = -7.25
 S = ac.SLAB
 CS = (1, 3, 9, 64)
 BUDGET = 2e7           # long-double multiply-adds of one case's reference
 
 
 def _device_autocorr(x, nd, L, round5=True, timed=True):
-    """The device entry over torch buffers: x (W, C, ld) with ld >= nd.  Both outputs carry a sentinel window before and after
-    their block, checked here.  Returns the unpacked output."""
-    import torch
-    from hmc_jl_amd import _lib
-    _lib.load()
-    dev = torch.device("cuda", 0)
-    W, Cn, ld = x.shape
-    tx = torch.from_numpy(np.array(x, dtype=np.float64, order="C")).to(dev)          # a copy: the shared AR(1) suite is read-only
-    f64 = dict(dtype=torch.float64, device=dev)
-    acov = torch.full((W + 2, Cn, L + 1), SENTINEL, **f64)
-    diag = torch.full((W + 2, Cn, _lib.ACF_STRIDE), SENTINEL, **f64)
-    torch.cuda.synchronize(dev)
-    p = _lib.make_autocorr(W, Cn, nd, ld, L, 0, round5)
-    tm = _lib.chain_autocorr_device(p, tx.data_ptr(), acov[1:].data_ptr(), diag[1:].data_ptr(), None, timed)
-    if timed:
-        assert tm.kernel_ms > 0.0 and tm.launches == 2
-    else:
-        torch.cuda.synchronize(dev)
-    raw = [t.cpu().numpy() for t in (acov, diag)]
-    for a in raw:
-        assert (a[0] == SENTINEL).all() and (a[-1] == SENTINEL).all(), "wrote outside its block"
-    return _lib.unpack_chain_autocorr(raw[0][1:-1], raw[1][1:-1])
+    """The device entry over torch buffers (stat_device_entry.run): x (W, C, ld) with ld >= nd.  Both outputs carry a sentinel
+    window before and after their block, checked there.  Returns the unpacked output."""
+    return sde.run("chain_autocorr", dict(x=x, nd=nd, L=L, round5=round5), timed)
 
 
 def _cases():

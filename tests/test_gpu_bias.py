@@ -17,36 +17,15 @@ import numpy as np
 import pytest
 
 import bias_cases as bc
+import stat_device_entry as sde
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = -7.25
-
 
 def _device_bias(mu, pi, A, fc, horizon, nd, round5=True, timed=True):
-    """The device entry over torch buffers: arrays with leading dimension mu.shape[2] >= nd.  Returns the unpacked output; the
-    buffer carries a sentinel row before and after the [W][stride] block, checked here."""
-    import torch
-    from hmc_jl_amd import _lib
-    _lib.load()
-    dev = torch.device("cuda", 0)
-    W, K, ld = mu.shape
-    up = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    tmu, tp, tA, tf = up(mu), up(pi), up(A if horizon > 0 else None), up(fc)
-    stride = _lib.bias_stride(K)
-    buf = torch.full((W + 2, stride), SENTINEL, dtype=torch.float64, device=dev)
-    torch.cuda.synchronize(dev)
-    H = 0 if fc is None else fc.shape[1] // 2
-    b = _lib.make_bias(W, K, nd, ld, horizon, H, 0, round5)
-    tm = _lib.bias_moments_device(b, tmu.data_ptr(), tp.data_ptr(), 0 if tA is None else tA.data_ptr(), 0 if tf is None else tf.data_ptr(),
-                                  buf[1:].data_ptr(), None, timed)
-    if timed:
-        assert tm.kernel_ms > 0.0 and tm.launches == 2
-    else:
-        torch.cuda.synchronize(dev)
-    out = buf.cpu().numpy()
-    assert (out[0] == SENTINEL).all() and (out[-1] == SENTINEL).all(), "wrote outside [W][stride]"
-    return _lib.unpack_bias(out[1:-1], K), out[1:-1].copy()
+    """The device entry over torch buffers (stat_device_entry.run): arrays with leading dimension mu.shape[2] >= nd.  Returns
+    the unpacked output and the raw [W][stride] block; the sentinel rows before and after it are checked there."""
+    return sde.run("bias_moments", dict(mu=mu, pi=pi, A=A, fc=fc, horizon=horizon, nd=nd, round5=round5), timed)
 
 
 def _cases():

@@ -21,46 +21,18 @@ import numpy as np
 import pytest
 
 import density_cases as dc
+import stat_device_entry as sde
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = -7.25
-ISENTINEL = -7
 CS = (1, 3, 9, 16, 64)
 BS = (1, 2, 64, 512)
 
 
 def _device_density(x, nd, cuts, bins, lo_hi=None, trace=(0, 1), round5=True, timed=True):
-    """The device entry over torch buffers: x (W, C, ld) with ld >= nd.  Every output carries a sentinel window before and after
-    its block, checked here.  Returns the unpacked output and the four raw blocks."""
-    import torch
-    from hmc_jl_amd import _lib
-    _lib.load()
-    dev = torch.device("cuda", 0)
-    W, Cn, ld = x.shape
-    nc, tl = len(cuts), int(trace[0])
-    tx = torch.from_numpy(np.ascontiguousarray(x)).to(dev)
-    tlh = None if lo_hi is None else torch.from_numpy(np.ascontiguousarray(lo_hi, dtype=np.float64)).to(dev)
-    f64 = dict(dtype=torch.float64, device=dev)
-    rng = torch.full((W + 2, Cn, 2), SENTINEL, **f64)
-    cnt = torch.full((W + 2, Cn, nc, bins + 3), ISENTINEL, dtype=torch.int64, device=dev)
-    st = torch.full((W + 2, Cn, nc, 2), SENTINEL, **f64)
-    tr = torch.full((W + 2, Cn, max(tl, 1)), SENTINEL, **f64)
-    torch.cuda.synchronize(dev)
-    p = _lib.make_density(W, Cn, nd, ld, cuts, bins, trace, 0, round5)
-    tm = _lib.chain_density_device(p, tx.data_ptr(), 0 if tlh is None else tlh.data_ptr(), rng[1:].data_ptr(), cnt[1:].data_ptr(),
-                                   st[1:].data_ptr(), tr[1:].data_ptr() if tl else 0, None, timed)
-    if timed:
-        assert tm.kernel_ms > 0.0 and tm.launches == (4 if lo_hi is None else 3)
-    else:
-        torch.cuda.synchronize(dev)
-    raw = [t.cpu().numpy() for t in (rng, cnt, st, tr)]
-    for a, s in zip(raw, (SENTINEL, ISENTINEL, SENTINEL, SENTINEL)):
-        assert (a[0] == s).all() and (a[-1] == s).all(), "wrote outside its block"
-    if tl == 0:
-        assert (raw[3] == SENTINEL).all()
-    blocks = [raw[0][1:-1].copy(), raw[1][1:-1].copy(), raw[2][1:-1].copy(), raw[3][1:-1, :, :tl].copy()]
-    return _lib.unpack_chain_density(*blocks), blocks
+    """The device entry over torch buffers (stat_device_entry.run): x (W, C, ld) with ld >= nd.  Every output carries a sentinel
+    window before and after its block, checked there.  Returns the unpacked output and the four raw blocks."""
+    return sde.run("chain_density", dict(x=x, nd=nd, cuts=cuts, bins=bins, lo_hi=lo_hi, trace=trace, round5=round5), timed)
 
 
 def _cases():

@@ -9,41 +9,18 @@ import numpy as np
 import pytest
 
 import ergodic_cases as ec
+import stat_device_entry as sde
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = -7.25
 S = ec.SLAB
 
 
 def _device_ergodic(mu, sig2, A, nd, round5=True, cols=True, timed=True):
-    """The device entry over torch buffers: mu, sig2 (W, K, ld), A (W, K, K, ld) with ld >= nd.  Every output carries a sentinel
-    window before and after its block, checked here.  Returns (cols (W, C, ld) or None, out (W, C, 2), n (W, 2))."""
-    import torch
-    from hmc_jl_amd import _lib
-    _lib.load()
-    dev = torch.device("cuda", 0)
-    W, K, ld = mu.shape
-    Cn = _lib.erg_cols(K)
-    t = [torch.from_numpy(np.array(a, dtype=np.float64, order="C")).to(dev) for a in (mu, sig2, A)]
-    tc = torch.full((W + 2, Cn, ld), SENTINEL, dtype=torch.float64, device=dev)
-    to = torch.full((W + 2, Cn, 2), SENTINEL, dtype=torch.float64, device=dev)
-    tn = torch.full((W + 2, 2), -7, dtype=torch.int64, device=dev)
-    torch.cuda.synchronize(dev)
-    p = _lib.make_ergodic(W, K, nd, ld, 0, round5)
-    tm = _lib.ergodic_moments_device(p, t[0].data_ptr(), t[1].data_ptr(), t[2].data_ptr(), tc[1:].data_ptr() if cols else 0,
-                                     to[1:].data_ptr(), tn[1:].data_ptr(), None, timed)
-    if timed:
-        assert tm.kernel_ms > 0.0 and tm.launches == 2
-    else:
-        torch.cuda.synchronize(dev)
-    rc, ro, rn = tc.cpu().numpy(), to.cpu().numpy(), tn.cpu().numpy()
-    for r, s in ((rc, SENTINEL), (ro, SENTINEL), (rn, -7)):
-        assert (r[0] == s).all() and (r[-1] == s).all(), "wrote outside its block"
-    assert (rc[1:-1, :, nd:] == SENTINEL).all(), "wrote into the padding of cols"
-    if not cols:
-        assert (rc == SENTINEL).all()
-    return (rc[1:-1] if cols else None), ro[1:-1], rn[1:-1]
+    """The device entry over torch buffers (stat_device_entry.run): mu, sig2 (W, K, ld), A (W, K, K, ld) with ld >= nd.  Every
+    output carries a sentinel window before and after its block, checked there, as is the padding of cols.  Returns (cols
+    (W, C, ld) or None, out (W, C, 2), n (W, 2))."""
+    return sde.run("ergodic_moments", dict(mu=mu, sig2=sig2, A=A, nd=nd, round5=round5, cols=cols), timed)
 
 
 def _places(nd, W, turn):

@@ -24,45 +24,21 @@ import pytest
 
 import fan_cases as fc
 import predictive_cases as pc
+import stat_device_entry as sde
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = -7.0
+SENTINEL = sde.SENTINEL
 
 
 def _device_fan(mu, sig2, pi, A, probs, horizons, rounds, nd, round5=True):
-    """The device entry over torch buffers: arrays with leading dimension mu.shape[2] >= nd; outputs prefilled with a sentinel."""
-    import torch
-    from hmc_jl_amd import _lib
-    _lib.load()
-    dev = torch.device("cuda", 0)
-    W, K, ld = mu.shape
-    up = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    tmu, ts, tp, tA = up(mu), up(sig2), up(pi), up(A)
-    out = torch.full((W, len(horizons), len(probs), 5), SENTINEL, dtype=torch.float64, device=dev)
-    rng = torch.full((W, 2), SENTINEL, dtype=torch.float64, device=dev)
-    flag = torch.full((W, len(horizons), len(probs)), -7, dtype=torch.int32, device=dev)
-    torch.cuda.synchronize(dev)
-    fan = _lib.make_fan(W, K, nd, ld, probs, horizons, rounds, 0, round5)
-    tm = _lib.predictive_quantiles_device(fan, tmu.data_ptr(), ts.data_ptr(), tp.data_ptr(), 0 if tA is None else tA.data_ptr(),
-                                          out.data_ptr(), rng.data_ptr(), flag.data_ptr(), None, True)
-    assert tm.kernel_ms > 0.0 and tm.launches == 2 + 2 * fc.rounds_of(rounds)
-    return out.cpu().numpy(), rng.cpu().numpy(), flag.cpu().numpy()
+    """The device entry over torch buffers (stat_device_entry.run): arrays with leading dimension mu.shape[2] >= nd; outputs
+    prefilled with a sentinel, framed by a sentinel window on either side."""
+    return sde.run("predictive_quantiles", dict(mu=mu, sig2=sig2, pi=pi, A=A, probs=probs, horizons=horizons, rounds=rounds, nd=nd, round5=round5))
 
 
 def _device_cdf(mu, sig2, pi, A, grid, horizons, nd, round5):
-    import torch
-    from hmc_jl_amd import _lib
-    dev = torch.device("cuda", 0)
-    W, K, ld = mu.shape
-    up = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    tmu, ts, tp, tA, tg = up(mu), up(sig2), up(pi), up(A), up(np.asarray(grid, dtype=np.float64))
-    out = torch.full((W, len(horizons), len(grid)), SENTINEL, dtype=torch.float64, device=dev)
-    torch.cuda.synchronize(dev)
-    pred = _lib.make_predictive(W, K, nd, ld, len(grid), horizons, 0, round5)
-    _lib.predictive_cdf_device(pred, tmu.data_ptr(), ts.data_ptr(), tp.data_ptr(), 0 if tA is None else tA.data_ptr(), tg.data_ptr(),
-                               out.data_ptr(), None, True)
-    return out.cpu().numpy()
+    return sde.run("predictive_cdf", dict(mu=mu, sig2=sig2, pi=pi, A=A, grid=grid, horizons=horizons, nd=nd, round5=round5))
 
 
 def _same_bits(a, b):
@@ -70,14 +46,7 @@ def _same_bits(a, b):
     return a.shape == b.shape and np.array_equal(a.view(np.uint64) if a.dtype == np.float64 else a, b.view(np.uint64) if b.dtype == np.float64 else b)
 
 
-def _flags_agree(got, exp_flag, exp_out, probs, tol):
-    """Flags equal to the reference's wherever its decision has a margin (module docstring)."""
-    p = np.asarray(probs, dtype=np.float64)
-    with np.errstate(invalid="ignore"):
-        Flo, Fhi = exp_out[..., 3], exp_out[..., 4]
-        shaky = (np.abs(Fhi - Flo) <= 2.0 * tol) | (np.abs(p - Fhi) <= tol)
-    nan_same = np.array_equal((got & fc.NAN_) != 0, (exp_flag & fc.NAN_) != 0)
-    return nan_same and np.array_equal(got[~shaky], exp_flag[~shaky]), int(shaky.sum())
+_flags_agree = sde.flags_agree             # flags equal to the reference's wherever its decision has a margin (module docstring)
 
 
 def _cases():

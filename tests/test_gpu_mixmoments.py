@@ -23,38 +23,19 @@ import numpy as np
 import pytest
 
 import mixmoments_cases as mc
+import stat_device_entry as sde
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = -7.25
 H8 = (12, 0, 3, 1, 12, 7, 2, 5)
 HSETS = ((0,), (12,), (0, 1, 12), H8)
 U = 2.0 ** -53
 
 
 def _device_mix(mu, sig2, pi, A, hz, nd, round5=True, timed=True):
-    """The device entry over torch buffers: arrays with leading dimension mu.shape[2] >= nd.  Returns the unpacked output and the
-    raw block; the buffer carries a sentinel window before and after the [W][n_h][8] block, checked here."""
-    import torch
-    from hmc_jl_amd import _lib
-    _lib.load()
-    dev = torch.device("cuda", 0)
-    W, K, ld = mu.shape
-    need_A = any(h > 0 for h in hz)
-    up = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    tmu, ts, tp, tA = up(mu), up(sig2), up(pi), up(A if need_A else None)
-    buf = torch.full((W + 2, len(hz), _lib.MIX_STRIDE), SENTINEL, dtype=torch.float64, device=dev)
-    torch.cuda.synchronize(dev)
-    p = _lib.make_mixmom(W, K, nd, ld, hz, 0, round5)
-    tm = _lib.mixture_moments_device(p, tmu.data_ptr(), ts.data_ptr(), tp.data_ptr(), 0 if tA is None else tA.data_ptr(),
-                                     buf[1:].data_ptr(), None, timed)
-    if timed:
-        assert tm.kernel_ms > 0.0 and tm.launches == 2
-    else:
-        torch.cuda.synchronize(dev)
-    out = buf.cpu().numpy()
-    assert (out[0] == SENTINEL).all() and (out[-1] == SENTINEL).all(), "wrote outside [W][n_h][8]"
-    return _lib.unpack_mixture_moments(out[1:-1]), out[1:-1].copy()
+    """The device entry over torch buffers (stat_device_entry.run): arrays with leading dimension mu.shape[2] >= nd.  Returns
+    the unpacked output and the raw [W][n_h][8] block; the sentinel windows before and after it are checked there."""
+    return sde.run("mixture_moments", dict(mu=mu, sig2=sig2, pi=pi, A=A, hz=hz, nd=nd, round5=round5), timed)
 
 
 def _cases():

@@ -17,6 +17,7 @@ import numpy as np
 import pytest
 
 import predictive_cases as pc
+import stat_device_entry as sde
 
 pytestmark = pytest.mark.gpu
 
@@ -27,21 +28,8 @@ def _slab():
 
 
 def _device_cdf(mu, sig2, pi, A, grid, horizons, nd, round5=True):
-    """The device entry over torch buffers: arrays with leading dimension mu.shape[2] >= nd."""
-    import torch
-    from hmc_jl_amd import _lib
-    _lib.load()
-    dev = torch.device("cuda", 0)
-    W, K, ld = mu.shape
-    up = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    tmu, ts, tp, tA, tg = up(mu), up(sig2), up(pi), up(A), up(np.asarray(grid, dtype=np.float64))
-    out = torch.full((W, len(horizons), len(grid)), -7.0, dtype=torch.float64, device=dev)
-    torch.cuda.synchronize(dev)
-    pred = _lib.make_predictive(W, K, nd, ld, len(grid), horizons, 0, round5)
-    tm = _lib.predictive_cdf_device(pred, tmu.data_ptr(), ts.data_ptr(), tp.data_ptr(), 0 if tA is None else tA.data_ptr(),
-                                    tg.data_ptr(), out.data_ptr(), None, True)
-    assert tm.kernel_ms > 0.0 and tm.launches == 2
-    return out.cpu().numpy()
+    """The device entry over torch buffers (stat_device_entry.run): arrays with leading dimension mu.shape[2] >= nd."""
+    return sde.run("predictive_cdf", dict(mu=mu, sig2=sig2, pi=pi, A=A, grid=grid, horizons=horizons, nd=nd, round5=round5))
 
 
 def _cases():

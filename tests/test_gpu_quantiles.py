@@ -10,34 +10,17 @@ import numpy as np
 import pytest
 
 import quantile_cases as qc
+import stat_device_entry as sde
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = -7.25
 S = 1024
 
 
 def _device_quantiles(x, nd, probs, round5=True, timed=True):
-    """The device entry over torch buffers: x (W, C, ld) with ld >= nd.  Both outputs carry a sentinel window before and after
-    their block, checked here.  Returns the unpacked output."""
-    import torch
-    from hmc_jl_amd import _lib
-    _lib.load()
-    dev = torch.device("cuda", 0)
-    W, Cn, ld = x.shape
-    tx = torch.from_numpy(np.array(x, dtype=np.float64, order="C")).to(dev)
-    q = torch.full((W + 2, Cn, len(probs), _lib.ORD_STRIDE), SENTINEL, dtype=torch.float64, device=dev)
-    n = torch.full((W + 2, Cn, 2), -7, dtype=torch.int64, device=dev)
-    torch.cuda.synchronize(dev)
-    p = _lib.make_quantiles(W, Cn, nd, ld, probs, 0, round5)
-    tm = _lib.chain_quantiles_device(p, tx.data_ptr(), q[1:].data_ptr(), n[1:].data_ptr(), None, timed)
-    if timed:
-        assert tm.kernel_ms > 0.0 and tm.launches == 1
-    else:
-        torch.cuda.synchronize(dev)
-    rq, rn = q.cpu().numpy(), n.cpu().numpy()
-    assert (rq[0] == SENTINEL).all() and (rq[-1] == SENTINEL).all() and (rn[0] == -7).all() and (rn[-1] == -7).all(), "wrote outside its block"
-    return _lib.unpack_chain_quantiles(rq[1:-1], rn[1:-1])
+    """The device entry over torch buffers (stat_device_entry.run): x (W, C, ld) with ld >= nd.  Both outputs carry a sentinel
+    window before and after their block, checked there.  Returns the unpacked output."""
+    return sde.run("chain_quantiles", dict(x=x, nd=nd, probs=probs, round5=round5), timed)
 
 
 def _edge_cases():

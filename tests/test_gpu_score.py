@@ -30,43 +30,21 @@ import pytest
 
 import fan_cases as fc
 import score_cases as sc
+import stat_device_entry as sde
 
 pytestmark = pytest.mark.gpu
 
-SENTINEL = -7.0
+SENTINEL = sde.SENTINEL
 
 
 def _device_scores(mu, sig2, pi, A, yreal, horizons, stride, nd, round5=True):
-    """The device entry over torch buffers: arrays with leading dimension mu.shape[2] >= nd; out prefilled with a sentinel."""
-    import torch
-    from hmc_jl_amd import _lib
-    _lib.load()
-    dev = torch.device("cuda", 0)
-    W, K, ld = mu.shape
-    up = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    tmu, ts, tp, tA, ty = up(mu), up(sig2), up(pi), up(A), up(np.asarray(yreal, dtype=np.float64))
-    out = torch.full((W, len(horizons), 5), SENTINEL, dtype=torch.float64, device=dev)
-    torch.cuda.synchronize(dev)
-    p = _lib.make_score(W, K, nd, ld, horizons, stride, 0, round5)
-    tm = _lib.predictive_scores_device(p, tmu.data_ptr(), ts.data_ptr(), tp.data_ptr(), 0 if tA is None else tA.data_ptr(), ty.data_ptr(),
-                                       out.data_ptr(), None, True)
-    assert tm.kernel_ms > 0.0 and tm.launches == 3
-    return out.cpu().numpy()
+    """The device entry over torch buffers (stat_device_entry.run): arrays with leading dimension mu.shape[2] >= nd; out
+    prefilled with a sentinel, framed by a sentinel window on either side."""
+    return sde.run("predictive_scores", dict(mu=mu, sig2=sig2, pi=pi, A=A, yreal=yreal, horizons=horizons, stride=stride, nd=nd, round5=round5))
 
 
 def _device_cdf(mu, sig2, pi, A, grid, horizons, nd, round5):
-    import torch
-    from hmc_jl_amd import _lib
-    dev = torch.device("cuda", 0)
-    W, K, ld = mu.shape
-    up = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-    tmu, ts, tp, tA, tg = up(mu), up(sig2), up(pi), up(A), up(np.asarray(grid, dtype=np.float64))
-    out = torch.full((W, len(horizons), len(grid)), SENTINEL, dtype=torch.float64, device=dev)
-    torch.cuda.synchronize(dev)
-    pred = _lib.make_predictive(W, K, nd, ld, len(grid), horizons, 0, round5)
-    _lib.predictive_cdf_device(pred, tmu.data_ptr(), ts.data_ptr(), tp.data_ptr(), 0 if tA is None else tA.data_ptr(), tg.data_ptr(),
-                               out.data_ptr(), None, True)
-    return out.cpu().numpy()
+    return sde.run("predictive_cdf", dict(mu=mu, sig2=sig2, pi=pi, A=A, grid=grid, horizons=horizons, nd=nd, round5=round5))
 
 
 def _same_bits(a, b):
